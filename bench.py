@@ -18,6 +18,15 @@ the largest single-GPU configuration; configs[1] (1024 x 64) rides along as ``wo
 owns its own 4096 x 256 envs (configs[3]: 32768 x 256 over 8 GPUs; envs never interact, no data-path
 collective): weak scaling, ``value`` = env-sub-steps of ALL ranks per second of the slowest rank.
 
+A plain run sets up, warms up, times the K steps and prints the line (plus ``roofline``, which reuses the timed launches).
+Everything that needs runs of its own -- ``cpu_baseline``, ``roofline.hbm_copy_measured``, ``end_to_end``,
+``episode_inclusive``, the other workload, ``tbptt``, ``burgers_fno`` and, for N > 1, the data-parallel ``tbptt`` step --
+runs only with ``--full``; the ``--no-*`` options then leave single legs out.
+
+``--dump-outputs DIR`` writes what the last timed step handed its caller (see ``dump_outputs``) as DIR/<name>.npy.  The
+inputs are seeded (initial states by env index, actions by rank), so two builds run with the same arguments can be
+compared output for output.
+
 Extra objects in the JSON line:
   roofline      HBM-model roofline of SURVEY.md 8(d): algorithmic bytes = 20*N per env-sub-step
                 (read u fp64, write u fp64, read phi fp32), achieved = bytes per launch / average
@@ -295,6 +304,17 @@ class KSRun:
         torch.cuda.synchronize(self.dev)
         assert int(self.st_acc.sum()) == 0, "non-finite state during the benchmark"
         return elapsed, e0.elapsed_time(e1) / K
+
+
+def dump_outputs(run, out_dir):
+    """``--dump-outputs``: the arrays the last timed step handed its caller -- fp32 observations [E, N], fp64 reward sums of
+    squares [E], status flags [E] (as fp64) -- and the fp64 state it left in HBM [E, N]: 12.6 MB at 4096 x 256.  Called
+    after timed(), which has synchronised the device, and before any other leg touches the stepper."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"obs": run.d_obs.cpu().numpy(), "ssq": run.d_ssq.cpu().numpy(),
+              "status": run.d_st.cpu().numpy().astype(np.float64), "state": run.stepper.get_state()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def end_to_end_leg(run, K=20, W=3):
@@ -575,6 +595,11 @@ def main():
     ap.add_argument("--workload", choices=list(WORKLOADS), default="c3")
     ap.add_argument("--mode", choices=["fast", "exact"], default="fast")
     ap.add_argument("--variant", default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (CPU baselines, HBM copy rate, end_to_end / episode legs, "
+                         "the other workload, surrogate TBPTT, Burgers / FNO); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0's envs when N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tbptt", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
@@ -594,7 +619,7 @@ def main():
 
     # ---- CPU baselines first: nothing has touched the GPU yet, so starting worker processes is safe ----
     cpu_ks, cpu_tbptt = None, None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu_ks = cpu_baseline(E, N, L)
         except Exception as exc:
@@ -636,6 +661,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(run, args.dump_outputs)
 
     lay = run.stepper.layout()
     total_substeps = n_gpus * E * CFG_STEPS * K
@@ -665,7 +692,7 @@ def main():
         if backend_note:
             ranks.update(backend_note)
         out["ranks"] = ranks
-    if rank == 0 and n_gpus == 1:
+    if rank == 0 and n_gpus == 1 and args.full:
         try:
             out["roofline"]["hbm_copy_measured"] = {"value": measured_hbm_copy_gbs(dev), "unit": "GB/s",
                                                     "what": "1 GiB device-to-device copy, read + write bytes"}
@@ -715,7 +742,7 @@ def main():
                 out["burgers_fno"] = burgers_fno_leg(dev)
             except Exception as exc:
                 out["burgers_fno"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if dist is not None and not args.no_tbptt:
+    if dist is not None and args.full and not args.no_tbptt:
         # data-parallel surrogate step at N = 256: B = 64 sequences per rank, one flat-bucket all-reduce per step
         ddp, err = None, None
         try:

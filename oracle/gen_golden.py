@@ -28,8 +28,14 @@ import types
 
 sys.dont_write_bytecode = True  # never write __pycache__ into /root/reference
 
-import numpy as np
-import torch
+import cpu_math  # noqa: E402
+
+cpu_math.pin_env()  # the arithmetic tests/conftest.py checks the fixtures with; before torch is imported
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+cpu_math.pin_torch()
 
 REF = "/root/reference"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")

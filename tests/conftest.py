@@ -10,6 +10,12 @@ for p in (ROOT, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+# the fixtures are bit-for-bit records: pin the CPU arithmetic they were recorded with (before anything imports torch)
+from oracle import cpu_math  # noqa: E402
+
+cpu_math.pin_env()
+cpu_math.pin_torch()
+
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 # (tag -> (L, N)) of the configurations the golden fixtures were generated for
@@ -28,6 +34,20 @@ def ks_golden():
 @pytest.fixture(scope="session")
 def sur_golden():
     return np.load(os.path.join(GOLDEN, "surrogate_golden.npz"))
+
+
+def require_fma_sgemm(tag):
+    """Skips the calling test where torch's CPU matmul cannot reproduce the forcing products of the fixtures: they hold
+    actions @ F as one fma chain (MKL on an Intel CPU); MKL on other vendors' CPUs runs a generic sgemm that rounds some
+    of them differently (oracle/cpu_math.py).  Checked on configuration ``tag``'s actions against the oracle's fma chain,
+    before the test does any work."""
+    import torch
+    from oracle import ks_oracle as ko
+    g = np.load(os.path.join(GOLDEN, "ks_golden.npz"))
+    a, F = g[f"{tag}_actions"], g[f"{tag}_F"]    # one [1, 4] action at a time, as the env's transform multiplies
+    got = np.concatenate([(torch.from_numpy(x) @ torch.from_numpy(F)).numpy() for x in a])
+    if not np.array_equal(got, ko.phi_from_actions(a, F)):
+        pytest.skip("needs MKL's fma sgemm (an Intel CPU): this CPU's MKL runs its generic sgemm")
 
 
 @pytest.fixture(autouse=True)

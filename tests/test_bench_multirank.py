@@ -37,7 +37,7 @@ def test_direct_multi_gpu_invocation_starts_its_own_ranks():
 
 @pytest.mark.gpu
 def test_two_ranks_started_by_bench_itself():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], 900)
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], 900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -9,7 +9,7 @@ from pdegym._gym import gym
 from pdegym.kuramoto import KuramotoSivashinskyEnv, make, make_vec, shard_envs
 from _oracle_stepper import OracleStepper
 
-from conftest import KS_CONFIGS
+from conftest import KS_CONFIGS, require_fma_sgemm
 
 
 def new_env(**cfg):
@@ -34,6 +34,7 @@ def test_constants_spaces_scenario(ks_golden):
 
 @pytest.mark.parametrize("tag", list(KS_CONFIGS))
 def test_forcing_transform_matches_reference(ks_golden, tag):
+    require_fma_sgemm(tag)
     L, N = KS_CONFIGS[tag]
     env = new_env(L=L, N=N)
     np.testing.assert_array_equal(env.forcing.forcing.numpy(), ks_golden[f"{tag}_F"])

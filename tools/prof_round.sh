@@ -10,6 +10,6 @@ for W in c3 c2; do
   tools/prof_sq.sh ${TAG}_$W --workload $W > /dev/null
   python3 tools/update_ks_profiles.py $W ${TAG}_$W
 done
-tools/prof_bench.sh ${TAG}_bench --no-cpu-baseline > /dev/null
+tools/prof_bench.sh ${TAG}_bench --full --no-cpu-baseline > /dev/null
 cp gpurun_out/prof_${TAG}_bench/summary.txt gpurun_out/${TAG}_bench_default_kernel_stats.txt
 head -12 gpurun_out/${TAG}_bench_default_kernel_stats.txt
