@@ -52,6 +52,15 @@ typedef enum ks_status {
  *                   reference CPU stepper.  ~3-4x slower; used as the parity anchor. */
 typedef enum ks_mode { KS_MODE_FAST = 0, KS_MODE_EXACT = 1 } ks_mode;
 
+/* Reward objective of the step entries (kuramoto.py:64-73): what the per-env accumulator ssq_sum collects.
+ *   KS_OBJECTIVE_L2CONTROL   : sum_i u_i^2                                   (reward -(1/N) ||u||^2)
+ *   KS_OBJECTIVE_DISSIPATION : sum_i (u_xx,i^2 + u_x,i^2 + u_i * phi_i)      (reward -(mean(u_xx^2) + mean(u_x^2)
+ *                              + mean(u * phi))), u_x the upwind derivative of u^2 that rhs forms (ks_rhs's ux),
+ *                              u_xx the 7-point second derivative, phi the fp32 forcing widened to fp64.
+ * Either way the reward of a step is -(1/N) * ssq_sum / cfg_steps, every term taken at the pre-update state of each
+ * sub-step.  The reference selects dissipation only for a falsy objective string. */
+typedef enum ks_objective { KS_OBJECTIVE_L2CONTROL = 0, KS_OBJECTIVE_DISSIPATION = 1 } ks_objective;
+
 /* Kernel layout / halo-exchange variant.  KS_VARIANT_AUTO picks per (N, num_envs). */
 typedef enum ks_variant {
     KS_VARIANT_AUTO = 0,
@@ -76,6 +85,10 @@ int ks_destroy(ks_handle* h);
 /* Run on a caller-provided hipStream_t (e.g. torch's current stream) instead of the handle's own. */
 int ks_set_stream(ks_handle* h, void* hip_stream);
 int ks_set_mode(ks_handle* h, int mode /* ks_mode */);
+/* Handle state like the mode: applies to every step entry (ks_step, _actions, _rows, _begin/_end, _device).  Default
+ * KS_OBJECTIVE_L2CONTROL.  A step that is given no reward buffer runs the l2control kernels whatever the objective.
+ * KS_VARIANT_WAVE64_HYBRID / HYBRID1 have no dissipation form: a step with a reward buffer returns KS_ERR_UNSUPPORTED. */
+int ks_set_objective(ks_handle* h, int objective /* ks_objective */);
 int ks_set_variant(ks_handle* h, int variant /* ks_variant */);
 /* Threads per workgroup of the fused kernels (64, 128 or 256; 0 = default). */
 int ks_set_block_size(ks_handle* h, int threads);
@@ -107,9 +120,10 @@ int ks_state_device_ptr(ks_handle* h, double** d_u);
  * times for every env: reward term, then one classical RK4 update of u' = rhs(u, phi).
  *   phi_host   fp32 [num_envs, N] forcing field, or NULL for phi = 0 (reset burn-in, :108-109)
  *   obs_f32    out, fp32 [num_envs, N] copy of the new state (gym observation dtype), or NULL
- *   ssq_sum    out, fp64 [num_envs]: sum over the n_substeps of sum_i u_i^2 taken BEFORE each
- *              update; the l2control reward of kuramoto.py:64-65,84,96 is
- *              -(1/N) * ssq_sum / cfg_steps.  May be NULL.
+ *   ssq_sum    out, fp64 [num_envs]: the reward accumulator, summed over the n_substeps and taken
+ *              BEFORE each update -- sum_i u_i^2 under KS_OBJECTIVE_L2CONTROL, sum_i (u_xx,i^2 +
+ *              u_x,i^2 + u_i phi_i) under KS_OBJECTIVE_DISSIPATION (ks_objective); the reward of
+ *              kuramoto.py:64-73,84,96 is -(1/N) * ssq_sum / cfg_steps either way.  May be NULL.
  *   status     out, int [num_envs]: 1 if the env's state is non-finite after the call (the
  *              reference raises FloatingPointError via np.seterr(over="raise"), kuramoto.py:12).
  * Synchronous: results are in the host buffers on return. */
@@ -146,6 +160,14 @@ int ks_step_end(ks_handle* h, float* obs_f32, double* ssq_sum, int* status);
 int ks_step_device(ks_handle* h, const float* d_phi, const float* d_actions, const int* d_env_ids,
                    int n_rows, long n_substeps, float* d_obs_f32, double* d_ssq_sum, int* d_status);
 int ks_sync(ks_handle* h);
+
+/* Replaces: reward_func evaluated sample by sample over a batch of observations (pdecontrol/mbrl/world/world.py:170,
+ * kuramoto.py:64-70) -- the world model's per-row reward.  d_obs fp32 [n_rows, N], d_phi fp32 [n_rows, N] (NULL = 0),
+ * d_reward fp64 [n_rows] out: -(mean(u_xx^2) + mean(u_x^2) + mean(u * phi)) per row for KS_OBJECTIVE_DISSIPATION, in
+ * fp64 with the reference's stencil order; -(1/N) sum u^2 for KS_OBJECTIVE_L2CONTROL.  Uses the handle's N and dx,
+ * not its state.  Enqueued on the handle's stream; on the CPU twin host pointers, synchronous. */
+int ks_reward_rows_device(ks_handle* h, int objective, const float* d_obs, const float* d_phi, int n_rows,
+                          double* d_reward);
 
 /* ---- test hooks -------------------------------------------------------------------------- */
 

@@ -45,6 +45,7 @@ struct ks_handle {
     int E = 0, N = 0;
     double L = 0, dt = 0, dx = 0;
     int mode = KS_MODE_FAST;
+    int objective = KS_OBJECTIVE_L2CONTROL;
     int variant = KS_VARIANT_AUTO;
     int block_threads = 0;
     int n_act = 0;
@@ -221,13 +222,18 @@ int do_step(ks_handle* h, const float* d_phi, const float* d_actions, const int*
         p.hdt = a.hdt;
         p.dt6 = a.dt6;
         p.dt3 = a.dt3;
-        kscpu::step(p, h->mode, h->d_u, d_phi, d_actions, h->d_F, h->n_act, d_env_ids, rows, n_substeps, d_obs, d_ssq,
+        p.r_dx2 = a.r_dx2;
+        p.r_dx4 = a.r_dx4;
+        kscpu::step(p, h->mode, h->objective, h->d_u, d_phi, d_actions, h->d_F, h->n_act, d_env_ids, rows, n_substeps, d_obs, d_ssq,
                     d_status, h->cpu_threads);
         return KS_OK;
     }
     ks::Layout lay;
     int rc = choose_layout(h, rows, lay);
     if (rc != KS_OK) return rc;
+    if (h->objective == KS_OBJECTIVE_DISSIPATION && d_ssq &&
+        (lay.variant == KS_VARIANT_WAVE64_HYBRID || lay.variant == KS_VARIANT_WAVE64_HYBRID1))
+        return fail(KS_ERR_UNSUPPORTED, "kernel variant %d has no dissipation-objective form", lay.variant);
     a.u = h->d_u;
     a.phi = d_phi;
     a.actions = d_actions;
@@ -237,7 +243,7 @@ int do_step(ks_handle* h, const float* d_phi, const float* d_actions, const int*
     a.status = d_status;
     a.n_rows = rows;
     a.n_substeps = n_substeps;
-    KS_HIP(ks::launch_step(lay, h->mode, a, h->stream));
+    KS_HIP(ks::launch_step(lay, h->mode, h->objective, a, h->stream));
     return KS_OK;
 }
 
@@ -353,6 +359,14 @@ int ks_set_mode(ks_handle* h, int mode) {
     if (!h) return fail(KS_ERR_INVALID, "NULL handle");
     if (mode != KS_MODE_FAST && mode != KS_MODE_EXACT) return fail(KS_ERR_INVALID, "unknown mode %d", mode);
     h->mode = mode;
+    return KS_OK;
+}
+
+int ks_set_objective(ks_handle* h, int objective) {
+    if (!h) return fail(KS_ERR_INVALID, "NULL handle");
+    if (objective != KS_OBJECTIVE_L2CONTROL && objective != KS_OBJECTIVE_DISSIPATION)
+        return fail(KS_ERR_INVALID, "unknown objective %d", objective);
+    h->objective = objective;
     return KS_OK;
 }
 
@@ -644,6 +658,23 @@ int ks_step_device(ks_handle* h, const float* d_phi, const float* d_actions, con
     KS_NOT_PENDING(h);
     DeviceGuard g(h->device);   // (on the CPU twin "device pointers" are host pointers and the call is synchronous)
     return do_step(h, d_phi, d_actions, d_env_ids, n_rows, n_substeps, d_obs_f32, d_ssq_sum, d_status);
+}
+
+int ks_reward_rows_device(ks_handle* h, int objective, const float* d_obs, const float* d_phi, int n_rows,
+                          double* d_reward) {
+    if (!h) return fail(KS_ERR_INVALID, "NULL handle");
+    if (objective != KS_OBJECTIVE_L2CONTROL && objective != KS_OBJECTIVE_DISSIPATION)
+        return fail(KS_ERR_INVALID, "unknown objective %d", objective);
+    if (n_rows < 0) return fail(KS_ERR_INVALID, "n_rows < 0");
+    if (n_rows > 0 && (!d_obs || !d_reward)) return fail(KS_ERR_INVALID, "NULL argument");
+    if ((size_t)n_rows * (size_t)h->N > (size_t)1 << 31) return fail(KS_ERR_INVALID, "n_rows * N too large");
+    if (h->cpu) {
+        kscpu::reward_rows(h->N, h->dx, objective, d_obs, d_phi, n_rows, d_reward);
+        return KS_OK;
+    }
+    DeviceGuard g(h->device);
+    KS_HIP(ks::launch_reward_rows(objective, d_obs, d_phi, n_rows, h->N, h->dx, d_reward, h->stream));
+    return KS_OK;
 }
 
 int ks_sync(ks_handle* h) {

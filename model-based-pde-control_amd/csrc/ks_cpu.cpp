@@ -21,8 +21,8 @@ namespace kscpu {
 namespace {
 
 struct Scratch {
-    std::vector<double> w, q, k, acc, us, phi;
-    explicit Scratch(int N) : w(N + 8), q(N + 8), k(N), acc(N), us(N), phi(N) {}
+    std::vector<double> w, q, k, acc, us, phi, t1, t2;
+    explicit Scratch(int N) : w(N + 8), q(N + 8), k(N), acc(N), us(N), phi(N), t1(N), t2(N) {}
 };
 
 // w[4 + i] = x[i], halo of 4 on both sides wrapped periodically; q = w * w
@@ -71,8 +71,12 @@ inline void rhs_exact(const Params& p, const double* w, const double* q, const d
     }
 }
 
-// merged linear stencil + both upwind sums sharing the centre term, FMA chains in the order of rhs_tile_fast
-inline void rhs_fast(const Params& p, const double* w, const double* q, const double* phi, int N, double* out) {
+// merged linear stencil + both upwind sums sharing the centre term, FMA chains in the order of rhs_tile_fast.
+// TERMS (dissipation objective): also the unscaled reward terms of rhs_tile_fast -- sel (the selected upwind sum) and
+// lap (the 7-point u_xx stencil) per point.
+template <bool TERMS = false>
+inline void rhs_fast(const Params& p, const double* w, const double* q, const double* phi, int N, double* out,
+                     double* sel_out = nullptr, double* lap_out = nullptr) {
     const double c0 = p.c_lin[0], c1 = p.c_lin[1], c2 = p.c_lin[2], c3 = p.c_lin[3], c4 = p.c_lin[4];
     const double m = p.mh_inv_dx;
     for (int i = 0; i < N; ++i) {
@@ -93,10 +97,18 @@ inline void rhs_fast(const Params& p, const double* w, const double* q, const do
         bw = __builtin_fma(0.25, q[c - 4], bw);
         const double sel = (w[c] < 0.0) ? fw : bw;       // u == 0 selects the backward stencil
         out[i] = __builtin_fma(m, sel, lin);
+        if constexpr (TERMS) {
+            double lap = (-49.0 / 18) * w[c];
+            lap = __builtin_fma(3.0 / 2, w[c - 1] + w[c + 1], lap);
+            lap = __builtin_fma(-3.0 / 20, w[c - 2] + w[c + 2], lap);
+            lap_out[i] = __builtin_fma(1.0 / 90, w[c - 3] + w[c + 3], lap);
+            sel_out[i] = sel;
+        }
     }
 }
 
-template <bool EXACT>
+// DISS: the reward accumulator collects the dissipation terms (kspde.h ks_objective) instead of sum u^2
+template <bool EXACT, bool DISS>
 void advance_env(const Params& p, double* u, const double* phi, long n_substeps, Scratch& s, double* ssq_out) {
     const int N = p.N;
     double* w = s.w.data();
@@ -104,16 +116,28 @@ void advance_env(const Params& p, double* u, const double* phi, long n_substeps,
     double* k = s.k.data();
     double* acc = s.acc.data();
     double* us = s.us.data();
+    double* t1 = s.t1.data();
+    double* t2 = s.t2.data();
     const double dt = p.dt;
     double racc = 0.0;
+    double rx = 0.0, rxx = 0.0;   // fast-mode dissipation: unscaled sel^2 / lap^2 sums
     for (long step = 0; step < n_substeps; ++step) {
         // stage 1 + the reward term of this sub-step (taken BEFORE the update, kuramoto.py:84)
         window(u, N, w, q);
-        double row = 0.0;
-        for (int i = 0; i < N; ++i) row += q[4 + i];
-        racc += row;
+        if constexpr (!DISS) {
+            double row = 0.0;
+            for (int i = 0; i < N; ++i) row += q[4 + i];
+            racc += row;
+        }
         if constexpr (EXACT) {
-            rhs_exact(p, w, q, phi, N, k, nullptr, nullptr, nullptr);
+            if constexpr (DISS) {
+                rhs_exact(p, w, q, phi, N, k, t1, t2, nullptr);
+                double row = 0.0;
+                for (int i = 0; i < N; ++i) row += (t2[i] * t2[i] + t1[i] * t1[i]) + w[4 + i] * phi[i];
+                racc += row;
+            } else {
+                rhs_exact(p, w, q, phi, N, k, nullptr, nullptr, nullptr);
+            }
             for (int i = 0; i < N; ++i) {
                 acc[i] = k[i];
                 us[i] = u[i] + dt * k[i] / 2.0;
@@ -137,7 +161,16 @@ void advance_env(const Params& p, double* u, const double* phi, long n_substeps,
                 u[i] = u[i] + dt * acc[i] / 6.0;
             }
         } else {
-            rhs_fast(p, w, q, phi, N, k);
+            if constexpr (DISS) {
+                rhs_fast<true>(p, w, q, phi, N, k, t1, t2);
+                for (int i = 0; i < N; ++i) {
+                    racc = __builtin_fma(w[4 + i], phi[i], racc);
+                    rx = __builtin_fma(t1[i], t1[i], rx);
+                    rxx = __builtin_fma(t2[i], t2[i], rxx);
+                }
+            } else {
+                rhs_fast(p, w, q, phi, N, k);
+            }
             for (int i = 0; i < N; ++i) {
                 acc[i] = __builtin_fma(p.dt6, k[i], u[i]);
                 us[i] = __builtin_fma(p.hdt, k[i], u[i]);
@@ -159,11 +192,12 @@ void advance_env(const Params& p, double* u, const double* phi, long n_substeps,
             for (int i = 0; i < N; ++i) u[i] = __builtin_fma(p.dt6, k[i], acc[i]);
         }
     }
+    if constexpr (DISS && !EXACT) racc = __builtin_fma(rxx, p.r_dx4, __builtin_fma(rx, p.r_dx2, racc));
     *ssq_out = racc;
 }
 
-void run_rows(const Params& p, int mode, double* u, const float* phi, const float* actions, const float* F, int n_act,
-              const int* env_ids, int lo, int hi, long n_substeps, float* obs, double* ssq_sum, int* status) {
+void run_rows(const Params& p, int mode, int objective, double* u, const float* phi, const float* actions, const float* F,
+              int n_act, const int* env_ids, int lo, int hi, long n_substeps, float* obs, double* ssq_sum, int* status) {
     const int N = p.N;
     Scratch s(N);
     for (int r = lo; r < hi; ++r) {
@@ -183,10 +217,16 @@ void run_rows(const Params& p, int mode, double* u, const float* phi, const floa
             std::fill(s.phi.begin(), s.phi.end(), 0.0);
         }
         double ssq = 0.0;
-        if (mode == 1)
-            advance_env<true>(p, ue, s.phi.data(), n_substeps, s, &ssq);
+        // without a reward buffer the objective is irrelevant (the GPU runs its l2control kernels then, too)
+        const bool diss = objective == 1 && ssq_sum;
+        if (mode == 1 && diss)
+            advance_env<true, true>(p, ue, s.phi.data(), n_substeps, s, &ssq);
+        else if (mode == 1)
+            advance_env<true, false>(p, ue, s.phi.data(), n_substeps, s, &ssq);
+        else if (diss)
+            advance_env<false, true>(p, ue, s.phi.data(), n_substeps, s, &ssq);
         else
-            advance_env<false>(p, ue, s.phi.data(), n_substeps, s, &ssq);
+            advance_env<false, false>(p, ue, s.phi.data(), n_substeps, s, &ssq);
         int bad = 0;
         for (int i = 0; i < N; ++i) bad |= !std::isfinite(ue[i]);
         if (obs)
@@ -209,14 +249,14 @@ int default_threads() {
     return n;
 }
 
-void step(const Params& p, int mode, double* u, const float* phi, const float* actions, const float* F, int n_act,
-          const int* env_ids, int n_rows, long n_substeps, float* obs, double* ssq_sum, int* status, int n_threads) {
+void step(const Params& p, int mode, int objective, double* u, const float* phi, const float* actions, const float* F,
+          int n_act, const int* env_ids, int n_rows, long n_substeps, float* obs, double* ssq_sum, int* status, int n_threads) {
     if (n_rows <= 0) return;
     // a thread is worth starting for >= ~1e6 point-sub-steps of its own
     const double work = (double)n_rows * (double)p.N * (double)std::max<long>(n_substeps, 1);
     int T = std::max(1, std::min({n_threads, n_rows, (int)(work / 1e6) + 1}));
     if (T == 1) {
-        run_rows(p, mode, u, phi, actions, F, n_act, env_ids, 0, n_rows, n_substeps, obs, ssq_sum, status);
+        run_rows(p, mode, objective, u, phi, actions, F, n_act, env_ids, 0, n_rows, n_substeps, obs, ssq_sum, status);
         return;
     }
     std::vector<std::thread> pool;
@@ -226,10 +266,10 @@ void step(const Params& p, int mode, double* u, const float* phi, const float* a
     for (int t = 0; t < T; ++t) {
         const int hi = lo + per + (t < extra ? 1 : 0);
         if (t + 1 < T)
-            pool.emplace_back(run_rows, std::cref(p), mode, u, phi, actions, F, n_act, env_ids, lo, hi, n_substeps, obs,
-                              ssq_sum, status);
+            pool.emplace_back(run_rows, std::cref(p), mode, objective, u, phi, actions, F, n_act, env_ids, lo, hi,
+                              n_substeps, obs, ssq_sum, status);
         else
-            run_rows(p, mode, u, phi, actions, F, n_act, env_ids, lo, hi, n_substeps, obs, ssq_sum, status);
+            run_rows(p, mode, objective, u, phi, actions, F, n_act, env_ids, lo, hi, n_substeps, obs, ssq_sum, status);
         lo = hi;
     }
     for (auto& th : pool) th.join();
@@ -249,6 +289,34 @@ void rhs(int N, double dx, double dx2, double dx4, const double* u, const float*
         window(u + off, N, s.w.data(), s.q.data());
         rhs_exact(p, s.w.data(), s.q.data(), s.phi.data(), N, out + off, ux ? ux + off : nullptr,
                   uxx ? uxx + off : nullptr, uxxxx ? uxxxx + off : nullptr);
+    }
+}
+
+void reward_rows(int N, double dx, int objective, const float* obs, const float* phi, int n_rows, double* out) {
+    Params p{};
+    p.N = N;
+    p.dx = dx;
+    p.dx2 = dx * dx;
+    p.dx4 = std::pow(dx, 4.0);
+    Scratch s(N);
+    std::vector<double> uu(N), rhs(N), zero(N, 0.0);
+    for (int r = 0; r < n_rows; ++r) {
+        const size_t off = (size_t)r * N;
+        for (int i = 0; i < N; ++i) uu[i] = (double)obs[off + i];
+        double sxx = 0.0, sx = 0.0, sup = 0.0;
+        if (objective == 1) {
+            window(uu.data(), N, s.w.data(), s.q.data());
+            rhs_exact(p, s.w.data(), s.q.data(), zero.data(), N, rhs.data(), s.t1.data(), s.t2.data(), nullptr);
+            for (int i = 0; i < N; ++i) {
+                sxx += s.t2[i] * s.t2[i];
+                sx += s.t1[i] * s.t1[i];
+                if (phi) sup += uu[i] * (double)phi[off + i];
+            }
+            out[r] = (-1.0) * ((sxx / N + sx / N) + sup / N);
+        } else {
+            for (int i = 0; i < N; ++i) sup += uu[i] * uu[i];
+            out[r] = (-1.0) * (1.0 / N) * sup;
+        }
     }
 }
 

@@ -15,6 +15,7 @@ struct Params {
     double c_lin[5];             // fast mode: merged linear stencil -(D4_k/dx^4 + D2_k/dx^2)
     double mh_inv_dx;            // -0.5 / dx
     double hdt, dt6, dt3;        // dt/2, dt/6, dt/3
+    double r_dx2, r_dx4;         // fast-mode dissipation: scale of the sel^2 / lap^2 sums (1/dx^2, 1/dx^4)
 };
 
 // Advance the n_rows envs listed in env_ids (nullptr = rows 0..n_rows-1) by n_substeps RK4 sub-steps.
@@ -22,12 +23,16 @@ struct Params {
 //   actions  [E,n_act] fp32 or nullptr    F        [n_act,N] fp32 (needed iff actions)
 //   obs / ssq_sum / status  outputs indexed by env id, any may be nullptr
 // mode: 0 = fast (merged stencil, FMA), 1 = exact (reference operation order, true divisions, no contraction).
-void step(const Params& p, int mode, double* u, const float* phi, const float* actions, const float* F, int n_act,
-          const int* env_ids, int n_rows, long n_substeps, float* obs, double* ssq_sum, int* status, int n_threads);
+// objective: 0 = l2control (ssq_sum collects sum u^2), 1 = dissipation (sum u_xx^2 + u_x^2 + u*phi); see kspde.h.
+void step(const Params& p, int mode, int objective, double* u, const float* phi, const float* actions, const float* F,
+          int n_act, const int* env_ids, int n_rows, long n_substeps, float* obs, double* ssq_sum, int* status, int n_threads);
 
 // rhs test hook in the reference's operation order; u, phi and outputs [n_rows, N]; ux / uxx / uxxxx may be nullptr.
 void rhs(int N, double dx, double dx2, double dx4, const double* u, const float* phi, int n_rows, double* out,
          double* ux, double* uxx, double* uxxxx);
+
+// Per-row reward of fp32 obs [n_rows, N] with fp32 phi (nullptr = 0) -> out [n_rows] (ks_reward_rows_device).
+void reward_rows(int N, double dx, int objective, const float* obs, const float* phi, int n_rows, double* out);
 
 // Host threads the twin uses by default: the affinity mask, capped by KSPDE_CPU_THREADS.
 int default_threads();

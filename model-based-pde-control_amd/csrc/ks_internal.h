@@ -26,7 +26,7 @@ struct StepArgs {
     double dt;
     // exact mode: the reference's divisors and their correctly rounded reciprocals (div_const in ks_kernels.hip)
     double dx, dx2, dx4;
-    double r_dx, r_dx2, r_dx4;
+    double r_dx, r_dx2, r_dx4;   // (also the fast-mode dissipation scale factors of the sel^2 / lap^2 sums)
 };
 
 struct Layout {
@@ -40,8 +40,13 @@ struct Layout {
 
 // Returns false if (variant, N) has no instantiated kernel.
 bool layout_supported(int variant, int N);
-// Launch the fused stepper described by `lay` on `stream`.
-hipError_t launch_step(const Layout& lay, int mode, const StepArgs& a, hipStream_t stream);
+// Launch the fused stepper described by `lay` on `stream`.  objective (ks_objective) selects what a.ssq_sum
+// accumulates; without a reward buffer the l2control kernels run.  The hybrid layouts have no dissipation form
+// (hipErrorNotSupported).
+hipError_t launch_step(const Layout& lay, int mode, int objective, const StepArgs& a, hipStream_t stream);
+// per-row reward of fp32 obs [n,N] with fp32 phi [n,N] (phi may be null) -> fp64 out [n] (device pointers)
+hipError_t launch_reward_rows(int objective, const float* obs, const float* phi, int n_rows, int N, double dx,
+                              double* out, hipStream_t stream);
 // rhs test hook: u [n,N], phi [n,N] -> outputs [n,N] (device pointers; ux/uxx/uxxxx may be null)
 hipError_t launch_rhs(const double* u, const float* phi, int n_rows, int N, double dx, double dx2,
                       double dx4, double* rhs, double* ux, double* uxx, double* uxxxx,

@@ -173,9 +173,13 @@ __device__ __forceinline__ double div_const(double x, double d, double r) {
 // rhs at one grid point.  w[] is the lane's window of u (4 halo + P + 4 halo), q[] = w[]^2,
 // c the index of the point inside the window.
 // ------------------------------------------------------------------------------------------
+//
+// t1 / t2 (dissipation objective, may be null): EXACT -> the reference's u_x (upwind derivative of u^2) and u_xx;
+// FAST -> the same two terms unscaled: the selected upwind sum (= u_x * dx up to sign) and the 7-point u_xx stencil
+// (= u_xx * dx^2), scaled once per launch by the caller.
 template <bool EXACT>
 __device__ __forceinline__ double rhs_point(const double* w, const double* q, int c, double phi,
-                                            const StepArgs& a) {
+                                            const StepArgs& a, double* t1 = nullptr, double* t2 = nullptr) {
     if constexpr (EXACT) {
         // scipy correlate1d summation order (ni_filters.c): see oracle/ks_oracle.c
         double fwd = q[c + 4] * (-1.0 / 4);
@@ -202,6 +206,8 @@ __device__ __forceinline__ double rhs_point(const double* w, const double* q, in
         d4 += (w[c - 2] + w[c + 2]) * (169.0 / 60);
         d4 += (w[c - 1] + w[c + 1]) * (-122.0 / 15);
         d4 = div_const(d4, a.dx4, a.r_dx4);
+        if (t1) *t1 = d1;
+        if (t2) *t2 = d2;
         return ((-d4 - d2) - 0.5 * d1) + phi;
     } else {
         double lin = __builtin_fma(a.c_lin[0], w[c], phi);
@@ -220,6 +226,13 @@ __device__ __forceinline__ double rhs_point(const double* w, const double* q, in
         fw = __builtin_fma(-4.0 / 3, q[c + 3], fw);
         fw = __builtin_fma(0.25, q[c + 4], fw);
         const double sel = (w[c] < 0.0) ? -fw : bw;  // u == 0 selects the backward stencil
+        if (t1) *t1 = sel;
+        if (t2) {
+            double lap = (-49.0 / 18) * w[c];
+            lap = __builtin_fma(3.0 / 2, w[c - 1] + w[c + 1], lap);
+            lap = __builtin_fma(-3.0 / 20, w[c - 2] + w[c + 2], lap);
+            *t2 = __builtin_fma(1.0 / 90, w[c - 3] + w[c + 3], lap);
+        }
         return __builtin_fma(a.mh_inv_dx, sel, lin);
     }
 }
@@ -228,10 +241,15 @@ __device__ __forceinline__ double rhs_point(const double* w, const double* q, in
 // FAST-mode rhs for a tile of TJ consecutive points, written op-major ("vector across the tile") so that
 // consecutive instructions are independent: one wave per SIMD cannot hide the fp64 dependent-issue
 // latency by switching waves, the instruction stream itself has to.
-template <int TJ>
+//
+// DISS (stage 1 of the dissipation objective): also accumulates r[0] += u*phi, r[1] += sel^2 and r[2] += lap^2, with
+// lap the 7-point u_xx stencil built from the same pair sums s1..s3 (u_x^2 = sel^2 / dx^2, u_xx^2 = lap^2 / dx^4: the
+// caller scales once per launch).
+template <int TJ, bool DISS = false>
 __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, int c0, const double* phi,
-                                              const StepArgs& a, double* k) {
+                                              const StepArgs& a, double* k, double* r = nullptr) {
     double lin[TJ], s1[TJ], s2[TJ], s3[TJ], s4[TJ], bw[TJ], fw[TJ];
+    [[maybe_unused]] double lap[TJ];
 #pragma unroll
     for (int t = 0; t < TJ; ++t) s1[t] = w[c0 + t - 1] + w[c0 + t + 1];
 #pragma unroll
@@ -240,6 +258,10 @@ __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, 
     for (int t = 0; t < TJ; ++t) lin[t] = __builtin_fma(a.c_lin[0], w[c0 + t], phi[t]);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) bw[t] = (25.0 / 12) * q[c0 + t];
+    if constexpr (DISS) {
+#pragma unroll
+        for (int t = 0; t < TJ; ++t) lap[t] = (-49.0 / 18) * w[c0 + t];
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) s3[t] = w[c0 + t - 3] + w[c0 + t + 3];
@@ -249,6 +271,10 @@ __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, 
     for (int t = 0; t < TJ; ++t) fw[t] = __builtin_fma(4.0, q[c0 + t + 1], -bw[t]);  // fw holds MINUS the forward sum
 #pragma unroll
     for (int t = 0; t < TJ; ++t) bw[t] = __builtin_fma(-4.0, q[c0 + t - 1], bw[t]);
+    if constexpr (DISS) {
+#pragma unroll
+        for (int t = 0; t < TJ; ++t) lap[t] = __builtin_fma(3.0 / 2, s1[t], lap[t]);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) s4[t] = w[c0 + t - 4] + w[c0 + t + 4];
@@ -258,6 +284,10 @@ __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, 
     for (int t = 0; t < TJ; ++t) fw[t] = __builtin_fma(-3.0, q[c0 + t + 2], fw[t]);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) bw[t] = __builtin_fma(3.0, q[c0 + t - 2], bw[t]);
+    if constexpr (DISS) {
+#pragma unroll
+        for (int t = 0; t < TJ; ++t) lap[t] = __builtin_fma(-3.0 / 20, s2[t], lap[t]);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) lin[t] = __builtin_fma(a.c_lin[3], s3[t], lin[t]);
@@ -265,6 +295,10 @@ __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, 
     for (int t = 0; t < TJ; ++t) fw[t] = __builtin_fma(4.0 / 3, q[c0 + t + 3], fw[t]);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) bw[t] = __builtin_fma(-4.0 / 3, q[c0 + t - 3], bw[t]);
+    if constexpr (DISS) {
+#pragma unroll
+        for (int t = 0; t < TJ; ++t) lap[t] = __builtin_fma(1.0 / 90, s3[t], lap[t]);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) lin[t] = __builtin_fma(a.c_lin[4], s4[t], lin[t]);
@@ -277,6 +311,11 @@ __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, 
     for (int t = 0; t < TJ; ++t) {
         const double sel = (w[c0 + t] < 0.0) ? fw[t] : bw[t];  // u == 0 selects the backward stencil
         k[t] = __builtin_fma(a.mh_inv_dx, sel, lin[t]);
+        if constexpr (DISS) {
+            r[0] = __builtin_fma(w[c0 + t], phi[t], r[0]);
+            r[1] = __builtin_fma(sel, sel, r[1]);
+            r[2] = __builtin_fma(lap[t], lap[t], r[2]);
+        }
     }
 }
 
@@ -344,6 +383,34 @@ __device__ __forceinline__ void eval_rhs(const double* w, const double* q, const
     }
 }
 
+// Stage 1 under the dissipation objective: the rhs plus the reward terms of the pre-update state.
+//   EXACT: r[0] += (u_xx^2 + u_x^2) + u*phi per point, u_x / u_xx exactly as rhs_point forms them
+//   FAST : r[0] += u*phi, r[1] += sel^2, r[2] += lap^2 (unscaled, see rhs_tile_fast)
+template <int P, bool EXACT>
+__device__ __forceinline__ void eval_rhs_dissipation(const double* w, const double* q, const double (&phi)[P],
+                                                     const StepArgs& a, double (&kk)[P], double (&r)[3]) {
+    if constexpr (EXACT) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            double ux, uxx;
+            kk[j] = rhs_point<true>(w, q, 4 + j, phi[j], a, &ux, &uxx);
+            r[0] += (uxx * uxx + ux * ux) + w[4 + j] * phi[j];
+        }
+    } else {
+        constexpr int TJ = tile_of<P>();
+#pragma unroll
+        for (int jb = 0; jb < P; jb += TJ) rhs_tile_fast<TJ, true>(w, q, 4 + jb, &phi[jb], a, &kk[jb], r);
+    }
+}
+
+// Per-lane reward accumulator -> the launch's per-env sum of the objective's per-sub-step terms (before the cross-lane
+// reduction).  FAST dissipation scales its two derivative sums here, once.
+template <bool EXACT, bool DISS>
+__device__ __forceinline__ double reward_partial(const double (&r)[3], const StepArgs& a) {
+    if constexpr (DISS && !EXACT) return __builtin_fma(r[2], a.r_dx4, __builtin_fma(r[1], a.r_dx2, r[0]));
+    return r[0];
+}
+
 // ------------------------------------------------------------------------------------------
 // fused register-resident stepper
 // ------------------------------------------------------------------------------------------
@@ -394,8 +461,11 @@ __device__ __forceinline__ void build_window(const Halo<G, HALO>& halo, const do
     }
 }
 
-template <int P, int G, int HALO, bool EXACT>
+// DISS: the reward accumulator collects the dissipation objective's terms instead of sum u^2 (the hybrid layouts have
+// no dissipation instantiation).
+template <int P, int G, int HALO, bool EXACT, bool DISS>
 __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
+    static_assert(!(DISS && (HALO == HALO_HYBRID || HALO == HALO_HYBRID1)), "no dissipation form of the hybrid layouts");
     constexpr int EPW = 64 / G;  // envs per wavefront
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -431,6 +501,7 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
     }
 
     double racc = 0.0;
+    [[maybe_unused]] double rd[3] = {0.0, 0.0, 0.0};   // dissipation partial sums (see eval_rhs_dissipation)
     for (long s = 0; s < a.n_substeps; ++s) {
         double acc[P], us[P], usn[P], w[P + 8], q[P + 8], kk[P];
         // ---- stage 1 (k1 at u) + reward term of this sub-step ----
@@ -442,9 +513,13 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
             build_window<P, G, HALO, EXACT>(halo, u, w);
 #pragma unroll
             for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
+            if constexpr (DISS) {
+                eval_rhs_dissipation<P, EXACT>(w, q, phi, a, kk, rd);
+            } else {
 #pragma unroll
-            for (int j = 0; j < P; ++j) racc += q[4 + j];
-            eval_rhs<P, EXACT>(w, q, phi, a, kk);
+                for (int j = 0; j < P; ++j) racc += q[4 + j];
+                eval_rhs<P, EXACT>(w, q, phi, a, kk);
+            }
         }
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -528,6 +603,7 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
     }
 
     // ---- epilogue: state, fp32 observation, reward sum, non-finite flag ----
+    if constexpr (DISS) racc = reward_partial<EXACT, DISS>(rd, a);
     int bad = 0;
 #pragma unroll
     for (int j = 0; j < P; ++j) bad |= !__builtin_isfinite(u[j]);
@@ -556,7 +632,7 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ int wrap_idx(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
 
-template <bool EXACT>
+template <bool EXACT, bool DISS>
 __global__ void __launch_bounds__(256) ks_rk4_lds(const StepArgs a) {
     extern __shared__ __align__(16) double lds[];
     const int N = a.N, tid = threadIdx.x, T = blockDim.x;
@@ -589,6 +665,7 @@ __global__ void __launch_bounds__(256) ks_rk4_lds(const StepArgs a) {
     __syncthreads();
 
     double racc = 0.0;
+    [[maybe_unused]] double rd[3] = {0.0, 0.0, 0.0};
     for (long s = 0; s < a.n_substeps; ++s) {
         const double* src = U;
         double* dst = S0;
@@ -601,8 +678,22 @@ __global__ void __launch_bounds__(256) ks_rk4_lds(const StepArgs a) {
                     w[k + 4] = src[wrap_idx(i + k, N)];
                     q[k + 4] = w[k + 4] * w[k + 4];
                 }
-                if (stage == 0) racc += q[4];
-                const double k = rhs_point<EXACT>(w, q, 4, PHI[i], a);
+                if constexpr (!DISS) {
+                    if (stage == 0) racc += q[4];
+                }
+                double t1 = 0.0, t2 = 0.0;   // (formed at every stage under DISS: a runtime choice of pointer spills)
+                const double k = rhs_point<EXACT>(w, q, 4, PHI[i], a, DISS ? &t1 : nullptr, DISS ? &t2 : nullptr);
+                if constexpr (DISS) {
+                    if (stage == 0) {
+                        if constexpr (EXACT) {
+                            rd[0] += (t2 * t2 + t1 * t1) + w[4] * PHI[i];
+                        } else {
+                            rd[0] = __builtin_fma(w[4], PHI[i], rd[0]);
+                            rd[1] = __builtin_fma(t1, t1, rd[1]);
+                            rd[2] = __builtin_fma(t2, t2, rd[2]);
+                        }
+                    }
+                }
                 const double u0 = U[i];
                 if constexpr (EXACT) {
                     if (stage == 0) { ACC[i] = k; dst[i] = u0 + a.dt * k / 2.0; }
@@ -632,6 +723,7 @@ __global__ void __launch_bounds__(256) ks_rk4_lds(const StepArgs a) {
         a.u[off + i] = v;
         if (a.obs) a.obs[off + i] = (float)v;
     }
+    if constexpr (DISS) racc = reward_partial<EXACT, DISS>(rd, a);
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) racc += __shfl_xor(racc, m, 64);
     if ((tid & 63) == 0) red[tid >> 6] = racc;
@@ -695,6 +787,71 @@ __global__ void ks_rhs_kernel(const double* __restrict__ u, const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------
+// per-row reward of a batch of fp32 observations (the world model's batched reward_func): one row per group of G lanes,
+// lane gl takes the points gl, gl + G, ...; the partial sums are reduced by xor shuffles inside the group.
+//   DISS : -(mean(u_xx^2) + mean(u_x^2) + mean(u*phi)), u_x / u_xx in the reference's operation order
+//          (kuramoto.py:67-70; u_x is the upwind derivative of u^2, as rhs returns it)
+//   else : -(1/N) * sum u^2 (l2control, kuramoto.py:64-65)
+// obs / phi fp32 [n_rows, N] (phi may be null: 0), out fp64 [n_rows].
+// ------------------------------------------------------------------------------------------
+template <int G, bool DISS>
+__global__ void __launch_bounds__(256) ks_reward_rows_kernel(const float* __restrict__ obs, const float* __restrict__ phi,
+                                                             int n_rows, int N, double dx, double r_dx, double dx2,
+                                                             double r_dx2, double* __restrict__ out) {
+    const int gl = threadIdx.x & (G - 1);
+    const int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) / G);
+    const bool active = row < n_rows;     // inactive groups still take part in the shuffles
+    const float* ur = obs + (size_t)(active ? row : 0) * N;
+    const float* pr = phi ? phi + (size_t)(active ? row : 0) * N : nullptr;
+    double sxx = 0.0, sx = 0.0, sup = 0.0;
+    for (int i = gl; active && i < N; i += G) {
+        double w[9], q[9];
+#pragma unroll
+        for (int k = -4; k <= 4; ++k) {
+            w[k + 4] = (double)ur[wrap_idx(i + k, N)];
+            q[k + 4] = w[k + 4] * w[k + 4];
+        }
+        const int c = 4;
+        if constexpr (DISS) {
+            double fwd = q[c + 4] * (-1.0 / 4);
+            fwd += q[c] * (-25.0 / 12);
+            fwd += q[c + 1] * 4.0;
+            fwd += q[c + 2] * (-3.0);
+            fwd += q[c + 3] * (4.0 / 3);
+            double bwd = q[c - 4] * (1.0 / 4);
+            bwd += q[c - 3] * (-4.0 / 3);
+            bwd += q[c - 2] * 3.0;
+            bwd += q[c - 1] * (-4.0);
+            bwd += q[c] * (25.0 / 12);
+            const double f = div_const(fwd, dx, r_dx), b = div_const(bwd, dx, r_dx), u = w[c];
+            const double d1 = (u < 0.0 ? 1.0 : 0.0) * f + (u >= 0.0 ? 1.0 : 0.0) * b;
+            double d2 = u * (-49.0 / 18);
+            d2 += (w[c - 3] + w[c + 3]) * (1.0 / 90);
+            d2 += (w[c - 2] + w[c + 2]) * (-3.0 / 20);
+            d2 += (w[c - 1] + w[c + 1]) * (3.0 / 2);
+            d2 = div_const(d2, dx2, r_dx2);
+            sxx += d2 * d2;
+            sx += d1 * d1;
+            if (pr) sup += u * (double)pr[i];
+        } else {
+            sup += q[c];
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) {
+        sxx += __shfl_xor(sxx, m, 64);
+        sx += __shfl_xor(sx, m, 64);
+        sup += __shfl_xor(sup, m, 64);
+    }
+    if (active && gl == 0) {
+        if constexpr (DISS)
+            out[row] = (-1.0) * ((sxx / N + sx / N) + sup / N);
+        else
+            out[row] = (-1.0) * (1.0 / N) * sup;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // cross-lane self test: every primitive moves the lane id and must deliver the defined source
 // ------------------------------------------------------------------------------------------
 template <int G, int HALO>
@@ -734,24 +891,33 @@ __global__ void ks_selftest_kernel(unsigned* out) {
 // host-side dispatch
 // ------------------------------------------------------------------------------------------
 template <int P, int G, int HALO>
-static hipError_t launch_fused(const Layout& lay, int mode, const StepArgs& a, hipStream_t st) {
+static hipError_t launch_fused(const Layout& lay, int mode, bool diss, const StepArgs& a, hipStream_t st) {
+    if constexpr (HALO == HALO_HYBRID || HALO == HALO_HYBRID1) {
+        if (diss) return hipErrorNotSupported;
+    } else if (diss) {
+        if (mode == KS_MODE_EXACT)
+            hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, true, true>), dim3(lay.grid), dim3(lay.block), 0, st, a);
+        else
+            hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, false, true>), dim3(lay.grid), dim3(lay.block), 0, st, a);
+        return hipGetLastError();
+    }
     if (mode == KS_MODE_EXACT)
-        hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, true>), dim3(lay.grid), dim3(lay.block), 0, st, a);
+        hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, true, false>), dim3(lay.grid), dim3(lay.block), 0, st, a);
     else
-        hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, false>), dim3(lay.grid), dim3(lay.block), 0, st, a);
+        hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, false, false>), dim3(lay.grid), dim3(lay.block), 0, st, a);
     return hipGetLastError();
 }
 
 #define KS_P_CASES(G_, HALO_)                                              \
     switch (lay.P) {                                                       \
-        case 1: return launch_fused<1, G_, HALO_>(lay, mode, a, st);       \
-        case 2: return launch_fused<2, G_, HALO_>(lay, mode, a, st);       \
-        case 3: return launch_fused<3, G_, HALO_>(lay, mode, a, st);       \
-        case 4: return launch_fused<4, G_, HALO_>(lay, mode, a, st);       \
-        case 6: return launch_fused<6, G_, HALO_>(lay, mode, a, st);       \
-        case 8: return launch_fused<8, G_, HALO_>(lay, mode, a, st);       \
-        case 12: return launch_fused<12, G_, HALO_>(lay, mode, a, st);     \
-        case 16: return launch_fused<16, G_, HALO_>(lay, mode, a, st);     \
+        case 1: return launch_fused<1, G_, HALO_>(lay, mode, diss, a, st);       \
+        case 2: return launch_fused<2, G_, HALO_>(lay, mode, diss, a, st);       \
+        case 3: return launch_fused<3, G_, HALO_>(lay, mode, diss, a, st);       \
+        case 4: return launch_fused<4, G_, HALO_>(lay, mode, diss, a, st);       \
+        case 6: return launch_fused<6, G_, HALO_>(lay, mode, diss, a, st);       \
+        case 8: return launch_fused<8, G_, HALO_>(lay, mode, diss, a, st);       \
+        case 12: return launch_fused<12, G_, HALO_>(lay, mode, diss, a, st);     \
+        case 16: return launch_fused<16, G_, HALO_>(lay, mode, diss, a, st);     \
         default: return hipErrorInvalidValue;                              \
     }
 
@@ -773,21 +939,27 @@ bool layout_supported(int variant, int N) {
     }
 }
 
-hipError_t launch_step(const Layout& lay, int mode, const StepArgs& a, hipStream_t st) {
+hipError_t launch_step(const Layout& lay, int mode, int objective, const StepArgs& a, hipStream_t st) {
     if (a.n_rows <= 0) return hipSuccess;
+    // without a reward buffer (e.g. the reset burn-in) the objective is irrelevant: the l2control kernels run
+    const bool diss = objective == KS_OBJECTIVE_DISSIPATION && a.ssq_sum != nullptr;
     switch (lay.variant) {
         case KS_VARIANT_ROW16_DPP: KS_P_CASES(16, HALO_DPP_ROW)
         case KS_VARIANT_ROW16_BPERM: KS_P_CASES(16, HALO_BPERM)
         case KS_VARIANT_HALF32_BPERM: KS_P_CASES(32, HALO_BPERM)
         case KS_VARIANT_WAVE64_DPP: KS_P_CASES(64, HALO_DPP_WAVE)
         case KS_VARIANT_WAVE64_BPERM: KS_P_CASES(64, HALO_BPERM)
-        case KS_VARIANT_WAVE64_HYBRID: return lay.P == 1 ? launch_fused<1, 64, HALO_HYBRID>(lay, mode, a, st) : hipErrorInvalidValue;
-        case KS_VARIANT_WAVE64_HYBRID1: return lay.P == 1 ? launch_fused<1, 64, HALO_HYBRID1>(lay, mode, a, st) : hipErrorInvalidValue;
+        case KS_VARIANT_WAVE64_HYBRID: return lay.P == 1 ? launch_fused<1, 64, HALO_HYBRID>(lay, mode, diss, a, st) : hipErrorInvalidValue;
+        case KS_VARIANT_WAVE64_HYBRID1: return lay.P == 1 ? launch_fused<1, 64, HALO_HYBRID1>(lay, mode, diss, a, st) : hipErrorInvalidValue;
         case KS_VARIANT_LDS:
-            if (mode == KS_MODE_EXACT)
-                hipLaunchKernelGGL((ks_rk4_lds<true>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
+            if (mode == KS_MODE_EXACT && !diss)
+                hipLaunchKernelGGL((ks_rk4_lds<true, false>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
+            else if (!diss)
+                hipLaunchKernelGGL((ks_rk4_lds<false, false>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
+            else if (mode == KS_MODE_EXACT)
+                hipLaunchKernelGGL((ks_rk4_lds<true, true>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
             else
-                hipLaunchKernelGGL((ks_rk4_lds<false>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
+                hipLaunchKernelGGL((ks_rk4_lds<false, true>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
             return hipGetLastError();
         default: return hipErrorInvalidValue;
     }
@@ -802,6 +974,31 @@ hipError_t launch_rhs(const double* u, const float* phi, int n_rows, int N, doub
     hipLaunchKernelGGL(ks_rhs_kernel, dim3(grid), dim3(block), 0, st, u, phi, n_rows, N, dx, dx2, dx4, rhs,
                        ux, uxx, uxxxx);
     return hipGetLastError();
+}
+
+template <int G>
+static hipError_t launch_reward_rows_g(bool diss, const float* obs, const float* phi, int n_rows, int N, double dx,
+                                       double* out, hipStream_t st) {
+    const int block = 256, rows_per_block = block / G;
+    const unsigned grid = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
+    const double dx2 = dx * dx;   // python: self.dx**2
+    if (diss)
+        hipLaunchKernelGGL((ks_reward_rows_kernel<G, true>), dim3(grid), dim3(block), 0, st, obs, phi, n_rows, N, dx,
+                           1.0 / dx, dx2, 1.0 / dx2, out);
+    else
+        hipLaunchKernelGGL((ks_reward_rows_kernel<G, false>), dim3(grid), dim3(block), 0, st, obs, phi, n_rows, N, dx,
+                           1.0 / dx, dx2, 1.0 / dx2, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_reward_rows(int objective, const float* obs, const float* phi, int n_rows, int N, double dx,
+                              double* out, hipStream_t st) {
+    if (n_rows <= 0) return hipSuccess;
+    const bool diss = objective == KS_OBJECTIVE_DISSIPATION;
+    // enough points per lane to amortise the 9-point window, few idle lanes for small N
+    if (N <= 64) return launch_reward_rows_g<16>(diss, obs, phi, n_rows, N, dx, out, st);
+    if (N <= 512) return launch_reward_rows_g<32>(diss, obs, phi, n_rows, N, dx, out, st);
+    return launch_reward_rows_g<64>(diss, obs, phi, n_rows, N, dx, out, st);
 }
 
 hipError_t launch_selftest(unsigned* d_fail, hipStream_t st) {

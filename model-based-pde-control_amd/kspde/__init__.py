@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "..", "lib", "libkspde.so")
 
 MODE = {"fast": 0, "exact": 1}
+OBJECTIVE = {"l2control": 0, "dissipation": 1}
 VARIANT = {"auto": 0, "row16_dpp": 1, "row16_bperm": 2, "wave64_dpp": 3, "wave64_bperm": 4,
            "half32_bperm": 5, "lds": 6, "wave64_hybrid": 7, "wave64_hybrid1": 8}
 VARIANT_NAME = {v: k for k, v in VARIANT.items()}
@@ -29,6 +30,7 @@ SYMBOLS = (
     ("ks_destroy", _c.c_int, [_H]),
     ("ks_set_stream", _c.c_int, [_H, _c.c_void_p]),
     ("ks_set_mode", _c.c_int, [_H, _c.c_int]),
+    ("ks_set_objective", _c.c_int, [_H, _c.c_int]),
     ("ks_set_variant", _c.c_int, [_H, _c.c_int]),
     ("ks_set_block_size", _c.c_int, [_H, _c.c_int]),
     ("ks_get_layout", _c.c_int, [_H, _ip, _ip, _ip, _ip, _ip]),
@@ -45,6 +47,7 @@ SYMBOLS = (
     ("ks_step_device", _c.c_int, [_H, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_long, _c.c_void_p,
                                   _c.c_void_p, _c.c_void_p]),
     ("ks_sync", _c.c_int, [_H]),
+    ("ks_reward_rows_device", _c.c_int, [_H, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     ("ks_rhs", _c.c_int, [_H, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                           _c.c_void_p]),
     ("ks_selftest", _c.c_int, [_H, _c.POINTER(_c.c_uint)]),
@@ -104,6 +107,7 @@ class KSStepper:
         _check(self._lib.ks_create(self.device, self.num_envs, self.N, self.L, self.dt, ctypes.byref(self._h)))
         self.set_mode(mode)
         self.set_variant(variant)
+        self.objective = "l2control"   # the library's default (ks_set_objective is only called to change it)
         self.n_act = 0
 
     # -- lifetime ---------------------------------------------------------------------------
@@ -122,6 +126,14 @@ class KSStepper:
     def set_mode(self, mode):
         _check(self._lib.ks_set_mode(self._h, MODE[mode] if isinstance(mode, str) else int(mode)))
         self.mode = mode
+
+    def set_objective(self, objective):
+        """What the step entries' reward accumulator collects: "l2control" (sum u^2) or "dissipation"
+        (sum u_xx^2 + u_x^2 + u*phi); see ks_objective in include/kspde.h."""
+        if objective not in OBJECTIVE:
+            raise ValueError(f"objective must be one of {sorted(OBJECTIVE)}, not {objective!r}")
+        _check(self._lib.ks_set_objective(self._h, OBJECTIVE[objective]))
+        self.objective = objective
 
     def set_variant(self, variant):
         _check(self._lib.ks_set_variant(self._h, VARIANT[variant] if isinstance(variant, str) else int(variant)))
@@ -222,6 +234,16 @@ class KSStepper:
         vp = lambda x: ctypes.c_void_p(int(x)) if x else None
         _check(self._lib.ks_step_device(self._h, vp(d_phi), vp(d_actions), vp(d_env_ids), int(n_rows),
                                         int(n_substeps), vp(d_obs), vp(d_ssq), vp(d_status)))
+
+    def reward_rows_device(self, objective, d_obs, d_phi, n_rows, d_reward):
+        """Per-row reward of fp32 obs [n_rows, N] with fp32 phi [n_rows, N] (0 = NULL: phi = 0) into fp64 [n_rows],
+        raw device pointers (ints), enqueued on the handle's stream; see ks_reward_rows_device.  On the CPU twin the
+        pointers are host pointers and the call is synchronous."""
+        if objective not in OBJECTIVE:
+            raise ValueError(f"objective must be one of {sorted(OBJECTIVE)}, not {objective!r}")
+        vp = lambda x: ctypes.c_void_p(int(x)) if x else None
+        _check(self._lib.ks_reward_rows_device(self._h, OBJECTIVE[objective], vp(d_obs), vp(d_phi), int(n_rows),
+                                               vp(d_reward)))
 
     def sync(self):
         _check(self._lib.ks_sync(self._h))

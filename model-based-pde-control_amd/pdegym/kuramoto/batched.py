@@ -52,8 +52,6 @@ class KSBatchedVecEnv(gym.vector.VectorEnv):
         # a (never stepped) single env supplies spaces, forcing matrix, reward function, constants
         self.proto = KuramotoSivashinskyEnv(**config)
         p = self.proto
-        if not p.objective:
-            raise NotImplementedError("the batched env implements the l2control reward only")
         super().__init__(num_envs, p.observation_space, p.action_space)
         self.N, self.L, self.dt, self.cfg_steps = p.N, p.L, p.dt, p.cfg_steps
         self.max_episode_steps = p.max_episode_steps
@@ -90,6 +88,11 @@ class KSBatchedVecEnv(gym.vector.VectorEnv):
         if self.stepper.mode != mode:
             self.stepper.set_mode(mode)
 
+    def _set_objective(self, objective):
+        # only a dissipation env ever calls this: an l2control env keeps the stepper's default
+        if getattr(self.stepper, "objective", "l2control") != objective:
+            self.stepper.set_objective(objective)
+
     def _raise_on(self, status):
         if np.any(status):
             raise FloatingPointError(f"overflow encountered in envs {np.nonzero(status)[0].tolist()}")
@@ -100,6 +103,7 @@ class KSBatchedVecEnv(gym.vector.VectorEnv):
         u0 = self._rng.uniform_rows(ids, -0.4, 0.4, self.N)
         self.stepper.set_state_rows(ids, u0)
         self._set_mode(self.reset_mode)
+        self._set_objective("l2control")          # the burn-in's reward is discarded: the l2control kernels run
         obs, _, status = self.stepper.step_rows(ids, self.burn_in_substeps)
         self._set_mode(self.step_mode)
         self._raise_on(status)
@@ -131,6 +135,7 @@ class KSBatchedVecEnv(gym.vector.VectorEnv):
 
     def step_wait(self, **kwargs):
         assert self._actions is not None, "step_wait() without step_async()"
+        self._set_objective(self.proto.step_objective)
         obs, ssq, status = self.stepper.step_actions(self._actions, self.cfg_steps)
         self._actions = None
         return self._finish_step(obs, ssq, status)
@@ -173,6 +178,7 @@ class KSBatchedVecEnv(gym.vector.VectorEnv):
             self.stepper.set_stream(stream)
             self._stream_handle = stream
         obs, ssq, status = self._dev_out
+        self._set_objective(self.proto.step_objective)
         self.stepper.step_device(d_actions=a.data_ptr(), n_substeps=self.cfg_steps, d_obs=obs.data_ptr(),
                                  d_ssq=ssq.data_ptr(), d_status=status.data_ptr())
         rewards = ssq * (-(1.0 / self.N) / self.cfg_steps)

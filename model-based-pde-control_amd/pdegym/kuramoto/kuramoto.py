@@ -16,9 +16,12 @@ Differences from the reference that a caller can observe:
     realisation of the same attractor.  The burn-in is two thirds of all sub-steps of a run and exact arithmetic costs
     2.6x (2.13 vs 0.83 ms per 250 sub-steps at 4096 x 256), so the default follows the per-sub-step contract;
     ``reset_mode="exact"`` or ``PDEGYM_RESET_MODE=exact`` is the parity switch (every parity test passes it).
-  * ``objective=""`` (the ``dissipation`` reward) raises in ``step`` here with NotImplementedError;
-    in the reference it raises TypeError (FuncTransform hands tensors to scipy), so no working
-    behaviour is lost.  ``reward_func`` itself is provided for both objectives.
+  * ``objective=""`` (the ``dissipation`` reward, -(mean(u_xx^2) + mean(u_x^2) + mean(u*phi)) at the pre-update state
+    of every sub-step) works in ``step``, accumulated inside the fused kernel; in the reference that path raises
+    TypeError (FuncTransform hands tensors to scipy, tests/golden/ks_golden.npz: dissipation_step_raises).  As in the
+    reference only a falsy ``objective`` selects it: the default string "dissipation" selects l2control.
+    ``reward_func`` / ``batched_reward_func`` under dissipation also accept actions ``[..., n_act]`` in place of the
+    forcing field (the world model hands its reward function actions) and map them through ``forcing``.
 """
 import math
 import os
@@ -100,22 +103,66 @@ class KuramotoSivashinskyEnv(gym.Env):
         return (-1.0) * (1 / self.N) * torch.norm(obs) ** 2
 
     def batched_reward_func(self, obs, phi=None):
-        """``reward_func`` for a whole batch ``[B, ..., N]`` at once (numpy or torch, host or device): the l2control
-        value of every row, in the input's dtype -- what the reference evaluates sample by sample in a Python loop
-        (pdecontrol/mbrl/world/world.py:170).  Only the l2control objective has a batched form."""
+        """``reward_func`` for a whole batch ``[B, ..., N]`` at once (numpy or torch, host or device): the reward of
+        every row, in the input's dtype -- what the reference evaluates sample by sample in a Python loop
+        (pdecontrol/mbrl/world/world.py:170).  Dissipation: ``phi`` is ``[B, ..., N]`` or actions ``[B, ..., n_act]``;
+        CUDA input is evaluated by ``ks_reward_rows_device`` on torch's current stream."""
         if not self.objective:
-            raise NotImplementedError("batched reward exists for the l2control objective only")
+            return self._batched_dissipation(obs, phi)
         if isinstance(obs, np.ndarray):
             flat = obs.reshape(obs.shape[0], -1)
             return ((-1.0) * (1 / self.N) * np.linalg.norm(flat, axis=1) ** 2).astype(obs.dtype)
         flat = obs.reshape(obs.shape[0], -1)
         return (-1.0) * (1 / self.N) * torch.linalg.vector_norm(flat, dim=1) ** 2
 
+    def _forcing_field(self, phi):
+        """phi as a forcing field: actions ``[..., n_act]`` go through ``forcing`` (fp32 ``[..., N]``)."""
+        if phi.shape[-1] == len(self.Xi) and phi.shape[-1] != self.N:
+            return self.forcing(phi)
+        return phi
+
     def _dissipation(self, obs, phi, *args, **kwargs):
         as_np = lambda v: np.squeeze(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v))
-        u, p = as_np(obs).astype(np.float64), as_np(phi)
+        u, p = as_np(obs).astype(np.float64), self._forcing_field(as_np(phi))
         _, (u_x, u_xx, _) = self.rhs(u, p)
         return torch.as_tensor((-1) * ((u_xx * u_xx).mean() + (u_x * u_x).mean() + (u * p).mean()))
+
+    def _batched_dissipation(self, obs, phi):
+        """``_dissipation`` of every row of ``obs [B, ..., N]``: numpy rows through ``rhs`` at once, CUDA tensors by the
+        reward kernel on an env-owned handle bound to torch's current stream."""
+        if phi is None:
+            raise ValueError("the dissipation reward needs the forcing (phi or actions)")
+        b = obs.shape[0]
+        if isinstance(obs, torch.Tensor) and obs.is_cuda:
+            u = obs.reshape(b, self.N).to(torch.float32).contiguous()
+            p = self._forcing_field(torch.as_tensor(phi, device=obs.device)).reshape(b, self.N)
+            p = p.to(torch.float32).contiguous()
+            h = self._reward_handle(obs.device)
+            out = torch.empty(b, dtype=torch.float64, device=obs.device)
+            h.reward_rows_device("dissipation", u.data_ptr(), p.data_ptr(), b, out.data_ptr())
+            return out.to(obs.dtype)
+        as_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        u = as_np(obs).reshape(b, self.N).astype(np.float64)
+        p = self._forcing_field(as_np(phi)).reshape(b, self.N)
+        _, (u_x, u_xx, _) = self.rhs(u, p)
+        p64 = p.astype(np.float64)
+        rew = (-1) * ((u_xx * u_xx).mean(axis=1) + (u_x * u_x).mean(axis=1) + (u * p64).mean(axis=1))
+        if isinstance(obs, torch.Tensor):
+            return torch.as_tensor(rew).to(obs.dtype)
+        return rew.astype(obs.dtype)
+
+    def _reward_handle(self, device):
+        """One-env stepper handle on ``device`` for ks_reward_rows_device, bound to torch's current stream."""
+        import kspde
+        h = getattr(self, "_reward_stepper", None)
+        if h is None or h.device != device.index:
+            h = self._reward_stepper = kspde.KSStepper(1, self.N, self.L, self.dt, device=device.index)
+            self._reward_stream = None
+        stream = torch.cuda.current_stream(device).cuda_stream
+        if self._reward_stream != stream:
+            h.set_stream(stream)
+            self._reward_stream = stream
+        return h
 
     # -- device state ------------------------------------------------------------------------
     @property
@@ -146,10 +193,12 @@ class KuramotoSivashinskyEnv(gym.Env):
         else:
             self._stepper.set_state(value[None, :])
 
-    def _advance(self, action, n_substeps, mode):
+    def _advance(self, action, n_substeps, mode, objective="l2control"):
         s = self.stepper
         if s.mode != mode:
             s.set_mode(mode)
+        if getattr(s, "objective", "l2control") != objective:
+            s.set_objective(objective)
         if action is None:
             _, ssq, status = s.step(None, n_substeps, want_obs=False)
         else:
@@ -161,14 +210,12 @@ class KuramotoSivashinskyEnv(gym.Env):
 
     # -- gym API -----------------------------------------------------------------------------
     def step(self, action: List):
-        if not self.objective:
-            raise NotImplementedError("the 'dissipation' reward is not available inside step() "
-                                      "(the reference raises TypeError on this path)")
         action = np.array(action, dtype=np.float32)
         # phi = forcing(action) is evaluated inside the kernel as the fp32 FMA chain
         # a0*F0 (+) a1*F1 (+) a2*F2 (+) a3*F3 -- what torch's CPU matmul produced where the golden
         # vectors were captured; a host-side matmul is not bit-stable across CPU microarchitectures.
-        ssq = self._advance(action.reshape(1, -1), self.cfg_steps, self.step_mode)
+        # the kernel's reward accumulator follows the objective (the reset burn-in below keeps the l2control kernels)
+        ssq = self._advance(action.reshape(1, -1), self.cfg_steps, self.step_mode, self.step_objective)
         reward = (-1.0) * (1 / self.N) * ssq / self.cfg_steps
 
         self.timestep += 1
@@ -196,10 +243,18 @@ class KuramotoSivashinskyEnv(gym.Env):
         rhs, u_x, u_xx, u_xxxx = (o.reshape(shape) for o in outs)
         return rhs, (u_x, u_xx, u_xxxx)
 
+    @property
+    def step_objective(self) -> str:
+        """The stepper objective (kspde.OBJECTIVE) of ``step``: truthiness of ``objective``, as ``reward_func``."""
+        return "l2control" if self.objective else "dissipation"
+
     def close(self):
         if self._stepper is not None:
             self._stepper.close()
             self._stepper = None
+        if getattr(self, "_reward_stepper", None) is not None:
+            self._reward_stepper.close()
+            self._reward_stepper = None
 
     @property
     def time(self):

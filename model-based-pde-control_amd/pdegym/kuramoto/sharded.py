@@ -68,6 +68,11 @@ class KSShardedVecEnv(KSBatchedVecEnv):
             if st.mode != mode:
                 st.set_mode(mode)
 
+    def _set_objective(self, objective):
+        for _, _, st in self.shards:
+            if getattr(st, "objective", "l2control") != objective:
+                st.set_objective(objective)
+
     def _collect(self, jobs):
         """jobs: [(stepper, (obs, ssq, status) slices)] already begun; wait for all of them on the shard threads."""
         small = jobs and jobs[0][1][0] is not None and jobs[0][1][0].nbytes <= self.THREADS_FROM_BYTES
@@ -102,6 +107,7 @@ class KSShardedVecEnv(KSBatchedVecEnv):
         ssq = np.empty(n, dtype=np.float64)
         status = np.empty(n, dtype=np.int32)
         self._set_mode(self.reset_mode)
+        self._set_objective("l2control")          # the burn-in's reward is discarded: the l2control kernels run
         jobs, parts = [], []
         for lo, hi, st in self.shards:
             sel = np.nonzero((ids >= lo) & (ids < hi))[0]
@@ -125,6 +131,7 @@ class KSShardedVecEnv(KSBatchedVecEnv):
     def step_async(self, actions):
         assert not self._in_flight, "step_async() twice without step_wait()"
         a = np.ascontiguousarray(np.asarray(actions, dtype=np.float32).reshape(self.num_envs, -1))
+        self._set_objective(self.proto.step_objective)
         for lo, hi, st in self.shards:
             st.step_begin(a[lo:hi], None, self.cfg_steps, want_obs=True)
         self._in_flight = True

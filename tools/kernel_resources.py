@@ -46,6 +46,7 @@ for src, extra in SOURCES:
         name = re.sub(r"\(anonymous namespace\)::", "", name)
         name = re.sub(r"\(.*$", "", name)              # drop the argument list
         if src == "ks_kernels.hip" and "ks_rk4_fused<" in name and not re.search(
-                r"<(1, 64, [234]|4, 16, 1|16, 16, 1), (true|false)>", name):
+                r"<(1, 64, [234]|4, 16, 1|16, 16, 1), (true|false), (true|false)>", name):
             continue                                    # the layouts the chooser picks for the BASELINE configs + the hybrids
+                                                        # (template flags: EXACT, then DISS = dissipation objective)
         print("%-92s %5d %5d %5d %7d %8d %6d" % (name[:92], vgpr, agpr, sgpr, scratch, lds, waves))

@@ -11,12 +11,12 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "model-based-pde-control_amd", "csrc", "ks_kernels.hip")
-KERNELS = [("C2 default: 1 point/lane, DPP wave chain", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi2ELb0EEEvNS_8StepArgsE", 1),
-           ("C2 hybrid: +-1,+-2 DPP, +-3,+-4 ds_bpermute", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi3ELb0EEEvNS_8StepArgsE", 1),
-           ("C2 hybrid1: +-1..+-3 DPP, +-4 ds_bpermute", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi4ELb0EEEvNS_8StepArgsE", 1),
-           ("C3 default: 16 points/lane, DPP row rotations", "_ZN2ks12ks_rk4_fusedILi16ELi16ELi1ELb0EEEvNS_8StepArgsE", 16),
-           ("C3 EXACT mode (reference operation order; reset burn-in)", "_ZN2ks12ks_rk4_fusedILi16ELi16ELi1ELb1EEEvNS_8StepArgsE", 16),
-           ("C2 EXACT mode", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi2ELb1EEEvNS_8StepArgsE", 1)]
+KERNELS = [("C2 default: 1 point/lane, DPP wave chain", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi2ELb0ELb0EEEvNS_8StepArgsE", 1),
+           ("C2 hybrid: +-1,+-2 DPP, +-3,+-4 ds_bpermute", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi3ELb0ELb0EEEvNS_8StepArgsE", 1),
+           ("C2 hybrid1: +-1..+-3 DPP, +-4 ds_bpermute", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi4ELb0ELb0EEEvNS_8StepArgsE", 1),
+           ("C3 default: 16 points/lane, DPP row rotations", "_ZN2ks12ks_rk4_fusedILi16ELi16ELi1ELb0ELb0EEEvNS_8StepArgsE", 16),
+           ("C3 EXACT mode (reference operation order; reset burn-in)", "_ZN2ks12ks_rk4_fusedILi16ELi16ELi1ELb1ELb0EEEvNS_8StepArgsE", 16),
+           ("C2 EXACT mode", "_ZN2ks12ks_rk4_fusedILi1ELi64ELi2ELb1ELb0EEEvNS_8StepArgsE", 1)]
 
 with tempfile.TemporaryDirectory() as tmp:
     asm = os.path.join(tmp, "ks.s")
