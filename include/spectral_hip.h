@@ -70,11 +70,11 @@ int fno_forward(void* stream, const fno_weights* w, int width, int modes, int la
 /* Backward of fno_forward for the same pairs.  gdelta [pairs][N] = d loss / d delta; gout [nb][N] (or NULL) = d loss / d out
  * of time step gout_t (the gradient a LATER step sent to the prediction it started from).  Writes gspec
  * [4][32][spec_pairs][32] (scaled spectra of the layer gradients; window as in fno_forward), rows [pairs][fno_row_width()] (every parameter gradient except the spectral
- * weights, one row per pair) and, unless NULL, dbase [pairs][N] = d loss / d u. */
+ * weights, one row per pair) and, unless NULL, dbase [pairs][N] = d loss / d u and dact [pairs][N] = d loss / d act. */
 int fno_backward(void* stream, const fno_weights* w, int width, int modes, int layers, int n, int nb, int pairs, const float* u,
                  long u_stride_t, long u_stride_b, const float* act, long a_stride_t, long a_stride_b, float cscale,
                  const float* gdelta, const float* gout, int gout_t, const float* pre, float* gspec, int spec_pairs, int spec_pair0,
-                 float* rows, float* dbase);
+                 float* rows, float* dbase, float* dact);
 
 /* Floats per gradient row: lift_w 64 | lift_b 32 | 4 x (pw_w 1024 | pw_b 32) | p1_w 1024 | p1_b 32 | p2_w 32 | p2_b 1 | pad. */
 int fno_row_width(void);

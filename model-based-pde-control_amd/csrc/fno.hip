@@ -95,6 +95,7 @@ struct BwdArgs {
     float* gspec;           // [4][32 k][spec_pairs][32 c] scaled spectra of d_pre
     float* rows;            // [pairs][ROW] parameter-gradient rows (everything but the spectral weights)
     float* dbase;           // [pairs][N] d loss / d u (including gout passed through), or nullptr
+    float* dact;            // [pairs][N] d loss / d act, or nullptr
     const float* tabg;      // [32][N] twiddle matrix (global, per device and N)
     int n, nb, pairs;
     int spec_pairs, spec_pair0;
@@ -619,7 +620,10 @@ __global__ void __launch_bounds__(TPB) fno_backward_kernel(const BwdArgs a) {
         L.gv[n] = u[n];
         L.Z[n] = act[n];          // Z / wps are contiguous and dead: N <= 2 * 32 * KP floats
     }
-    if (threadIdx.x < C) L.misc[threadIdx.x] = a.w.lift_w[2 * threadIdx.x];
+    if (threadIdx.x < C) {
+        L.misc[threadIdx.x] = a.w.lift_w[2 * threadIdx.x];              // state column of the lift
+        L.misc[C + threadIdx.x] = a.w.lift_w[2 * threadIdx.x + 1];      // action column
+    }
     __syncthreads();
     {
         const float su = row_dot(db, L.gv, N, NP), sa = row_dot(db, L.Z, N, NP), sb = row_dot(db, nullptr, N, NP);
@@ -636,6 +640,14 @@ __global__ void __launch_bounds__(TPB) fno_backward_kernel(const BwdArgs a) {
 #pragma unroll 8
             for (int c = 0; c < C; ++c) s = fmaf(L.misc[c], db[c * NP + n], s);
             a.dbase[(size_t)p * N + n] = s;
+        }
+    }
+    if (a.dact) {
+        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+            float s = 0.0f;
+#pragma unroll 8
+            for (int c = 0; c < C; ++c) s = fmaf(L.misc[C + c], db[c * NP + n], s);
+            a.dact[(size_t)p * N + n] = s;
         }
     }
 }
@@ -843,7 +855,7 @@ int fno_forward(void* stream, const fno_weights* w, int width, int modes, int la
 int fno_backward(void* stream, const fno_weights* w, int width, int modes, int layers, int n, int nb, int pairs, const float* u,
                  long u_stride_t, long u_stride_b, const float* act, long a_stride_t, long a_stride_b, float cscale,
                  const float* gdelta, const float* gout, int gout_t, const float* pre, float* gspec, int spec_pairs, int spec_pair0,
-                 float* rows, float* dbase) {
+                 float* rows, float* dbase, float* dact) {
     if (!complete(w) || !u || !act || !gdelta || !pre || !gspec || !rows) return fail(-1, "fno_backward: bad argument");
     if (spec_pair0 < 0 || spec_pair0 + pairs > spec_pairs) return fail(-1, "fno_backward: spectra window out of range");
     if (int rc = check("fno_backward", n, nb, pairs, width, modes, layers)) return rc;
@@ -860,6 +872,7 @@ int fno_backward(void* stream, const fno_weights* w, int width, int modes, int l
     a.spec_pair0 = spec_pair0;
     a.rows = rows;
     a.dbase = dbase;
+    a.dact = dact;
     int trc = 0;
     a.tabg = twiddle_table("fno_backward", n, (hipStream_t)stream, &trc);
     if (!a.tabg) return trc;

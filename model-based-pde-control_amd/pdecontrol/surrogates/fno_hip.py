@@ -34,7 +34,7 @@ class FnoWeights(ctypes.Structure):
 _WP = ctypes.POINTER(FnoWeights)
 SYMBOLS = (
     ("fno_forward", _i, [_p, _WP, _i, _i, _i, _i, _i, _i, _p, _l, _l, _p, _l, _l, _f, _f, _p, _p, _p, _p, _i, _i]),
-    ("fno_backward", _i, [_p, _WP, _i, _i, _i, _i, _i, _i, _p, _l, _l, _p, _l, _l, _f, _p, _p, _i, _p, _p, _i, _i, _p, _p]),
+    ("fno_backward", _i, [_p, _WP, _i, _i, _i, _i, _i, _i, _p, _l, _l, _p, _l, _l, _f, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p]),
     ("fno_row_width", _i, []),
     ("fno_reduce_rows", _i, [_p, _p, _i, _p]),
     ("fno_spec_wgrad", _i, [_p, _p, _p, _i, _p * 4, _p * 4]),
@@ -137,11 +137,15 @@ def _forward_launches(lib, w, states, acts, n_given, cscale, cshift, deltas, out
                                spec_pairs, pair0 + k0 * B))
 
 
-def _backward_launches(lib, w, states, acts, outputs, pre, n_given, cscale, g_deltas, gspec, spec_pairs, pair0, rows, gouts):
+def _backward_launches(lib, w, states, acts, outputs, pre, n_given, cscale, g_deltas, gspec, spec_pairs, pair0, rows, gouts,
+                       g_outputs=None, dstates=None, dacts=None):
     """The backward launches of one rollout, last step first.  ``rows`` [K * B, width] and the spectra window receive the
     per-pair results; ``gouts``: K - n_given preallocated [B, N] buffers for the gradient a free-running step sends to the
     prediction it started from (it belongs to the step before it: free steps hand it on one by one, the teacher-forced
-    launch receives it for its LAST step only -- true states need no gradient)."""
+    launch receives it for its LAST step only).  Optional: ``g_outputs`` [K, B, N] = d loss / d outputs of the free-running
+    steps (added to what the next step hands back; the teacher-forced part is folded in by the caller), ``dstates``
+    [n_given, B, N] = d loss / d the given states through the teacher-forced steps' bases and lift (without the
+    identity term of a loss on their outputs), ``dacts`` [K, B, N] = d loss / d acts (time major)."""
     B, K, N = acts.shape[0], acts.shape[1], acts.shape[-1]
     st = _stream()
     ast, asb = acts.stride(1), acts.stride(0)
@@ -150,13 +154,16 @@ def _backward_launches(lib, w, states, acts, outputs, pre, n_given, cscale, g_de
         free = k0 >= n_given
         if free:
             u_ptr, ust, usb = outputs[k0 - 1].data_ptr(), 0, outputs.stride(1)
+            if g_outputs is not None:
+                gout = g_outputs[k0] if gout is None else gout + g_outputs[k0]
         else:
             u_ptr, ust, usb = states.data_ptr(), states.stride(1), states.stride(0)
-        new_gout = gouts[k0 - n_given] if free else None
+        new_gout = gouts[k0 - n_given] if free else dstates
         _check(lib.fno_backward(st, ctypes.byref(w), WIDTH, MODES, LAYERS, N, B, cnt * B, ctypes.c_void_p(u_ptr), ust, usb,
                                 ctypes.c_void_p(acts.data_ptr() + 4 * k0 * ast), ast, asb, cscale,
                                 _ptr(g_deltas[k0]), _ptr(gout), (0 if free else n_given - 1), _ptr(pre[k0 * B:]), _ptr(gspec),
-                                spec_pairs, pair0 + k0 * B, _ptr(rows[k0 * B:]), _ptr(new_gout)))
+                                spec_pairs, pair0 + k0 * B, _ptr(rows[k0 * B:]), _ptr(new_gout),
+                                _ptr(None if dacts is None else dacts[k0])))
         gout = new_gout
 
 
@@ -191,7 +198,8 @@ class _FNORolloutFn(torch.autograd.Function):
         B, K, N = acts.shape[0], acts.shape[1], acts.shape[-1]
         n_given = min(int(n_given), K)
         dev = states.device
-        need = any(ctx.needs_input_grad[5:])      # (grad mode is off inside forward: ask the node, not torch.is_grad_enabled)
+        # (grad mode is off inside forward: ask the node, not torch.is_grad_enabled)
+        need = any(ctx.needs_input_grad[:2]) or any(ctx.needs_input_grad[5:])
         w, keep = _weights_struct(params)
         deltas = torch.empty((K, B, N), device=dev, dtype=torch.float32)
         outputs = torch.empty((K, B, N), device=dev, dtype=torch.float32)
@@ -202,13 +210,13 @@ class _FNORolloutFn(torch.autograd.Function):
         if need:
             ctx.save_for_backward(states, acts, outputs, pre, xspec, *params)
             ctx.meta = (B, K, N, n_given, float(cscale))
-        ctx.mark_non_differentiable(outputs)
+        ctx.set_materialize_grads(False)
         del keep
         return deltas, outputs
 
     @staticmethod
-    def backward(ctx, g_deltas, _g_outputs):
-        if not ctx.need:
+    def backward(ctx, g_deltas, g_outputs):
+        if not ctx.need or (g_deltas is None and g_outputs is None):
             return (None,) * len(ctx.needs_input_grad)
         lib = load()
         B, K, N, n_given, cscale = ctx.meta
@@ -217,14 +225,32 @@ class _FNORolloutFn(torch.autograd.Function):
         params = saved[5:]
         dev = states.device
         w, keep = _weights_struct(params)
-        g_deltas = g_deltas.contiguous()
+        g_deltas = torch.zeros_like(outputs) if g_deltas is None else g_deltas.contiguous()
+        if g_outputs is not None:
+            # outputs[k] = base[k] + cscale * deltas[k] + cshift: a teacher-forced step's share goes into its delta gradient
+            # (and, identity, into d states below); the free-running steps add theirs to what the next step hands back
+            g_outputs = g_outputs.contiguous()
+            g_deltas = g_deltas.clone()
+            g_deltas[:n_given].add_(g_outputs[:n_given], alpha=cscale)
+        need_ds, need_da = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dstates = torch.empty((n_given, B, N), device=dev, dtype=torch.float32) if need_ds else None
+        dacts = torch.empty((K, B, N), device=dev, dtype=torch.float32) if need_da else None
         rows = torch.empty((K * B, lib.fno_row_width()), device=dev, dtype=torch.float32)
         gspec = torch.empty((LAYERS, 2 * MODES, K * B, WIDTH), device=dev, dtype=torch.float32)
         gouts = [torch.empty((B, N), device=dev, dtype=torch.float32) for _ in range(K - n_given)]
-        _backward_launches(lib, w, states, acts, outputs, pre, n_given, cscale, g_deltas, gspec, K * B, 0, rows, gouts)
+        _backward_launches(lib, w, states, acts, outputs, pre, n_given, cscale, g_deltas, gspec, K * B, 0, rows, gouts,
+                           g_outputs, dstates, dacts)
         out = _parameter_grads(lib, rows, xspec, gspec, K * B, ctx.needs_input_grad[5:])
+        ds = da = None
+        if need_ds:
+            if g_outputs is not None:
+                dstates.add_(g_outputs[:n_given])
+            ds = torch.zeros_like(states)                                   # [B, S, 1, N]; given states past K: no path
+            ds[:, :n_given] = dstates.transpose(0, 1).unsqueeze(2)
+        if need_da:
+            da = dacts.transpose(0, 1).unsqueeze(2)                          # [B, K, 1, N]
         del keep
-        return (None, None, None, None, None, *out)
+        return (ds, da, None, None, None, *out)
 
 
 class _FNOTBPTTFn(torch.autograd.Function):
@@ -311,6 +337,8 @@ def tbptt(surrogate, states, actions, tau, tbtt, grid):
     from pdecontrol.surrogates.surrogate import action_and_target_indices, take_steps
     model = surrogate.model
     if states.dtype != torch.float32 or states.dim() != 4 or states.shape[2] != 1 or actions.shape != states.shape:
+        return None
+    if states.requires_grad or actions.requires_grad:   # the node hands out no input gradients: the chunk loop (on rollout)
         return None
     n, T = states.shape[-1], actions.shape[1]
     if not supported(model, n):

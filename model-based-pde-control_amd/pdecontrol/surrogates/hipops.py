@@ -181,6 +181,9 @@ class _Pack:
         views = self._gviews
         return views is not None and all(p.grad is v for p, v in zip(self.params, views))
 
+    def all_trainable(self):
+        return all(p.requires_grad for p in self.params)
+
     def own_flat_grads(self):
         """Point the kernel's gradient addresses at the pack-owned flat buffer (created on first use); param.grad untouched."""
         if self.gflat is None:
@@ -193,17 +196,26 @@ class _Pack:
             self.c.g[i] = view.data_ptr()
 
     def resolve_grads(self):
-        """Gradient addresses, taken when the reduction is about to be launched.  Sets ``self.overwrite``."""
-        grads = [p.grad for p in self.params]
+        """Gradient addresses, taken when the reduction is about to be launched.  Sets ``self.overwrite``.  A frozen
+        parameter (``requires_grad=False``) keeps ``.grad`` undefined: its slot is pointed at its (never handed out) view
+        of the pack-owned flat buffer, which the reduction overwrites or adds to and nothing reads."""
+        frozen = [not p.requires_grad for p in self.params]
+        grads = [None if f else p.grad for p, f in zip(self.params, frozen)]
         if all(g is None for g in grads):
             if self.gflat is None:
                 self.own_flat_grads()
-            for i, (p, view) in enumerate(zip(self.params, self._gviews)):
-                p.grad = view
+            for i, (p, view, f) in enumerate(zip(self.params, self._gviews, frozen)):
+                if not f:
+                    p.grad = view
                 self.c.g[i] = view.data_ptr()
             self.overwrite = True
             return
+        if any(frozen) and self.gflat is None:
+            self.own_flat_grads()
         for i, (p, g) in enumerate(zip(self.params, grads)):
+            if frozen[i]:
+                self.c.g[i] = self._gviews[i].data_ptr()
+                continue
             if g is None:
                 g = p.grad = torch.zeros_like(p)
             if not (g.is_cuda and g.is_contiguous() and g.dtype == torch.float32):
@@ -498,6 +510,10 @@ class PackAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         packs = self._packs()
+        if not all(pack.all_trainable() for pack in packs.packs):
+            raise SurrogateHipError("PackAdam updates whole parameter packs and a pack holds a parameter with "
+                                    "requires_grad=False: use torch.optim.Adam over the trainable parameters "
+                                    "(PDETrainingModule.configure_optimizers does)")
         group = self.param_groups[0]
         pending = self.__dict__.pop("_pending_state", None)
         if pending is not None:
@@ -636,7 +652,8 @@ class _EncoderFn(torch.autograd.Function):
         saved = _encoder_saved_buffer(pack, m, x.device) if any(ctx.needs_input_grad) else None
         _check(load().sur_encoder_forward(_stream(), ctypes.byref(pack.c), _p(x), m, _p(z), _p(saved)))
         ctx.save_for_backward(x)
-        ctx.pack, ctx.owner, ctx.need_dx, ctx.fwd_saved = pack, owner, x.requires_grad, saved
+        # (needs_input_grad, not x.requires_grad: grad mode is off in here, so a contiguous COPY never requires grad)
+        ctx.pack, ctx.owner, ctx.need_dx, ctx.fwd_saved = pack, owner, ctx.needs_input_grad[0], saved
         return z
 
     @staticmethod
@@ -699,7 +716,10 @@ class _ChunkFn(torch.autograd.Function):
         ctx.save_for_backward(xlat_t, lstates_t, h0, c0, h_all, c_all)
         ctx.fwd_saved = saved
         ctx.pack, ctx.owner = pack, owner
-        ctx.needs = (xlat_t.requires_grad, lstates_t.requires_grad, h0.requires_grad, c0.requires_grad)
+        # (the inputs as given: grad mode is off in here, so a contiguous COPY -- of H0 / C0 expanded over the batch --
+        # never requires grad)
+        nig = ctx.needs_input_grad
+        ctx.needs = (nig[0], nig[1], nig[3], nig[4])
         ctx.set_materialize_grads(False)
         return h_all, c_all, d_all, out_all
 
@@ -724,7 +744,21 @@ class _ChunkFn(torch.autograd.Function):
                                          _p(ctx.fwd_saved), _p(work)))
         ctx.pack.dirty = True
         ctx.owner.schedule_flush()
-        return dxlat, dlst, None, dh0, dc0, None, None, None
+        dstates = _dstates(dout_all, lstates_t.shape[0]) if ctx.needs_input_grad[2] else None
+        return dxlat, dlst, dstates, dh0, dc0, None, None, None
+
+
+def _dstates(dout_all, s):
+    """d loss / d states_t [S,B,1,N] through the integration bases (the state-encoder path comes back as d lstates_t).  A
+    teacher-forced step k integrates from states[k]; the free-running steps integrate from the previous output, and their
+    transition ignores the (re-encoded) input state, so every output from step S-1 on is states[S-1] plus deltas: d out_j /
+    d states[S-1] = I for all j >= S-1."""
+    if dout_all is None:
+        return None
+    d = dout_all[:s].clone()
+    if dout_all.shape[0] > s:
+        d[s - 1] += dout_all[s:].sum(dim=0)
+    return d
 
 
 class _DeltaLossFn(torch.autograd.Function):
@@ -1138,7 +1172,10 @@ def _tbptt_backward(owner, bounds, dims, saved_state, unified, dd_all):
 def fused_tbptt(surrogate, states, actions, tau, tbtt):
     """TBPTT forward of PDETrainingModule (training.py:71-98) on the fused kernels.  Returns
     (outputs [B,T,1,N], outdeltas [B,T,1,N], (H, C), time-major outdeltas [T,B,1,N]) with one action per step
-    (the training layout)."""
+    (the training layout).  None when ``states`` or ``actions`` require grad: the node hands out no input gradients, the
+    caller runs its chunk loop on ``fused_rollout`` instead."""
+    if states.requires_grad or actions.requires_grad:
+        return None
     b, _, _, n = states.shape
     owner = packs_for(surrogate, n, b)
     d_all, out_all, h, c = _TBPTTFn.apply(states, actions, owner.anchor, owner, surrogate, tau, tbtt)

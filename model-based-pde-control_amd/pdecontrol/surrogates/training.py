@@ -82,15 +82,18 @@ class PDETrainingModule(pl.LightningModule):
         start from the previous chunk's last prediction with gradients cut (state and hidden)."""
         from pdecontrol.surrogates import ops
         if isinstance(self.surrogate, AutoRegPDESurrogate) and ops.use_fused_for(self.surrogate, states):
-            # every chunk in a handful of launches, independent work on parallel streams (hipops._TBPTTFn)
+            # every chunk in a handful of launches, independent work on parallel streams (hipops._TBPTTFn); None: inputs
+            # that require grad -> the generic chunk loop below (on the fused rollout)
             from pdecontrol.surrogates import hipops
-            outputs, deltas, hidden, d_all = hipops.fused_tbptt(self.surrogate, states, actions, self.tau, self.tbtt)
-            out = ModelRollout(outputs=outputs, deltas=deltas, hidden=tuple(h.detach() for h in hidden))
-            out.time_major_deltas = d_all
-            return [out]
+            fused = hipops.fused_tbptt(self.surrogate, states, actions, self.tau, self.tbtt)
+            if fused is not None:
+                outputs, deltas, hidden, d_all = fused
+                out = ModelRollout(outputs=outputs, deltas=deltas, hidden=tuple(h.detach() for h in hidden))
+                out.time_major_deltas = d_all
+                return [out]
         if states.is_cuda and ops.fused_enabled() and type(self.surrogate).__name__ == "FNOAutoRegSurrogate":
             # the FNO surrogate's whole TBPTT pass as one autograd node on the whole-network kernels (csrc/fno.hip); None:
-            # a geometry they are not built for -> the generic chunk loop below (per-operator path)
+            # a geometry they are not built for or inputs that require grad -> the generic chunk loop below
             from pdecontrol.surrogates import fno_hip
             fused = fno_hip.tbptt(self.surrogate, states, actions, self.tau, self.tbtt, self._grid)
             if fused is not None:
@@ -173,6 +176,11 @@ class PDETrainingModule(pl.LightningModule):
                 return out
         return self._eager_training_step(batch, bidx)
 
+    def _frozen_parameters(self):
+        """Names of the surrogate's parameters with requires_grad=False, apart from the initial hidden state (H0 / C0 are
+        non-trainable by construction, transition.py)."""
+        return [n for n, p in self.surrogate.named_parameters() if not p.requires_grad and not n.endswith((".H0", ".C0"))]
+
     def _split_graph_training_step(self, batch):
         """training_step under Lightning's automatic optimization as two replayed hipGraphs behind one autograd node
         (``graph_step.GraphedAutogradStep``): forward + loss now, backward + gradient reduction when the caller runs
@@ -189,11 +197,13 @@ class PDETrainingModule(pl.LightningModule):
         if torch.cuda.is_current_stream_capturing():
             return None
         from pdecontrol.surrogates.graph_step import GraphedAutogradStep
+        if states.requires_grad or actions.requires_grad:
+            return None         # the captured step copies the batch into static buffers: no gradient reaches the inputs
         key = (tuple(states.shape), tuple(actions.shape))
         cache = self.__dict__.setdefault("_split_steps", {})
         step = cache.get(key)
         if step is None or not step.valid():
-            if not all(p.requires_grad for n, p in self.surrogate.named_parameters() if not n.endswith((".H0", ".C0"))):
+            if self._frozen_parameters():
                 return None     # a frozen sub-module: the captured backward would still write its gradients
             step = cache[key] = GraphedAutogradStep(self, key[0], key[1])
         elif not step.all_trainable():
@@ -248,7 +258,18 @@ class PDETrainingModule(pl.LightningModule):
         states, actions, *_ = batch
         key = (tuple(states.shape), tuple(actions.shape))
         cache = self.__dict__.setdefault("_graphed_steps", {})
-        if key not in cache or not cache[key].valid():
+        trained = self.__dict__.get("_graphed_trained")
+        stale = key not in cache or not cache[key].valid()
+        if stale or trained is None or not all(p.requires_grad for p in trained):
+            # the captured step reduces and applies Adam over whole parameter sets: it would train frozen weights
+            frozen = self._frozen_parameters()
+            if frozen:
+                raise RuntimeError(f"fused_step trains every parameter, but {len(frozen)} have requires_grad=False "
+                                   f"({', '.join(frozen[:3])}{', ...' if len(frozen) > 3 else ''}): use training_step + "
+                                   f"backward + the optimizer of configure_optimizers for a partly frozen surrogate")
+            self.__dict__["_graphed_trained"] = [p for n, p in self.surrogate.named_parameters()
+                                                 if not n.endswith((".H0", ".C0"))]
+        if stale:
             # one process per GPU with an initialised process group: the captured step must exchange gradients
             # (forward/backward graph -> one flat-bucket all-reduce -> Adam graph), never train the ranks apart silently
             dist = torch.distributed
@@ -366,11 +387,12 @@ class PDETrainingModule(pl.LightningModule):
         on_gpu = bool(params) and params[0].is_cuda
         if self.graphed and on_gpu:
             optimizer = _GraphOwnedAdam(params, lr=self.lr)
-        elif on_gpu and self._fused_eager():
+        elif on_gpu and self._fused_eager() and not self._frozen_parameters():
             # the whole Adam update as ONE launch over the fused packs' flat state (same rule as torch.optim.Adam)
             from pdecontrol.surrogates import hipops
             optimizer = hipops.PackAdam(self.surrogate, lr=self.lr)
         else:
+            # (a partly frozen surrogate lands here: PackAdam's single launch would move the frozen weights of a pack)
             extra = {"fused": True} if on_gpu else {}
             optimizer = torch.optim.Adam(params, lr=self.lr, **extra)
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=self.step_size, gamma=self.lr_gamma)
