@@ -14,8 +14,18 @@
  * the batch of two tiny tensors the launches save ([B, C, 2, modes] each) and is left to the caller (one einsum).
  *
  * All pointers are DEVICE pointers of contiguous fp32 tensors; launches are asynchronous on the given hipStream_t.
- * Return 0 on success, negative on error (spec_last_error()).  Constraints: Cin, Cout multiples of 16; modes a
- * multiple of 8 with modes <= N/2 - 1... (modes < N/2); N a power of two, 32 <= N <= 2048.
+ * Return 0 on success, negative on error (spec_last_error()).  A geometry launches only if all of these hold:
+ *   - Cin and Cout are multiples of 16;
+ *   - N is a power of two, 32 <= N <= 2048;
+ *   - modes is a multiple of 8 with modes < N/2;
+ *   - Cin * modes <= 1024 and Cout * modes <= 1024 (mode mixing: 4 outputs per thread of a 256-thread workgroup);
+ *   - the launch's LDS fits 160 KiB.  With c_in / c_out the channels of the launch's input / output tensor
+ *     (forward: Cin / Cout; backward: Cout / Cin) and kp = 2 modes + 4, it needs
+ *         base  = 4 * (c_in * (N + 4) + (c_in + c_out) * kp) bytes, plus
+ *         dense = base + 4 * N * kp  (twiddle matrix in LDS), taken if <= 160 KiB and N <= (c_in + c_out) * kp,
+ *         table = base + 4 * N       (cosine table) otherwise; refused (-4) if that is above 160 KiB.
+ *     So forward and backward can differ: either path, and a geometry the forward accepts the backward may refuse.
+ * spec_conv_supported() answers for both directions at once, without a launch.
  */
 #ifndef SPECTRAL_HIP_H
 #define SPECTRAL_HIP_H
@@ -33,6 +43,10 @@ int spec_conv_forward(void* stream, const float* x, const float* wr, const float
  * Weight gradients: gWr[i,o,m] = sum_b gyr*xr + gyi*xi,  gWi[i,o,m] = sum_b -gyr*xi + gyi*xr. */
 int spec_conv_backward(void* stream, const float* dy, const float* wr, const float* wi, int b, int cin, int cout, int n, int modes,
                        float* dx, float* gyft);
+
+/* 0 if both spec_conv_forward and spec_conv_backward accept this geometry (for any batch size); otherwise the negative code
+ * and spec_last_error() text of the call that would refuse it.  Host only: touches no device. */
+int spec_conv_supported(int cin, int cout, int n, int modes);
 
 const char* spec_last_error(void);
 

@@ -299,19 +299,40 @@ __global__ void __launch_bounds__(TPB) spec_conv_kernel(const Args a) {
     }
 }
 
+constexpr size_t LDS_MAX = 160 * 1024;
+
+// LDS plan of one launch direction (c_in / c_out = channels of THIS launch's input / output tensors): the dense twiddle
+// matrix when it fits and its N-entry cosine scratch fits in S / Z, else the cosine table.  The one place the rule lives:
+// the launches and spec_conv_supported both go through check_lds.
+struct LdsPlan {
+    bool dense;
+    size_t bytes;
+};
+
+LdsPlan lds_plan(int c_in, int c_out, int n, int m) {
+    const size_t kp = 2 * (size_t)m + 4;
+    const size_t base = sizeof(float) * ((size_t)c_in * (n + 4) + (size_t)(c_in + c_out) * kp);
+    const size_t lds_dense = base + sizeof(float) * (size_t)n * kp, lds_table = base + sizeof(float) * (size_t)n;
+    const bool dense = lds_dense <= LDS_MAX && (size_t)n <= (size_t)(c_in + c_out) * kp;
+    return {dense, dense ? lds_dense : lds_table};
+}
+
+int check_lds(const char* who, int c_in, int c_out, int n, int m, LdsPlan* plan) {
+    *plan = lds_plan(c_in, c_out, n, m);
+    if (plan->bytes > LDS_MAX) return fail(-4, "%s: needs %zu B of LDS (> 160 KiB): channels x N too large", who, plan->bytes);
+    return 0;
+}
+
 int launch(void* stream, const Args& a, int b, const char* who) {
     const int c_in = a.backward ? a.cout : a.cin, c_out = a.backward ? a.cin : a.cout;
-    const size_t kp = 2 * a.m + 4;
-    const size_t base = sizeof(float) * ((size_t)c_in * (a.n + 4) + (size_t)(c_in + c_out) * kp);
-    const size_t lds_dense = base + sizeof(float) * (size_t)a.n * kp, lds_table = base + sizeof(float) * (size_t)a.n;
-    const bool dense = lds_dense <= 160 * 1024 && (size_t)a.n <= (size_t)(c_in + c_out) * kp;
-    const size_t lds = dense ? lds_dense : lds_table;
-    if (lds > 160 * 1024) return fail(-4, "%s: needs %zu B of LDS (> 160 KiB): channels x N too large", who, lds);
+    LdsPlan plan;
+    if (int rc = check_lds(who, c_in, c_out, a.n, a.m, &plan)) return rc;
+    const size_t lds = plan.bytes;
     auto go = [&](auto kernel) {
         if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kernel, dim3(b), dim3(TPB), lds, (hipStream_t)stream, a);
     };
-    if (dense) go(spec_conv_kernel<true>);
+    if (plan.dense) go(spec_conv_kernel<true>);
     else go(spec_conv_kernel<false>);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(-2, "%s launch failed: %s", who, hipGetErrorString(e));
@@ -333,6 +354,15 @@ int check_geometry(const char* who, int b, int cin, int cout, int n, int modes) 
 extern "C" {
 
 const char* spec_last_error(void) { return g_err; }
+
+int spec_conv_supported(int cin, int cout, int n, int modes) {
+    // the checks of the two launches in their order, under their names: a refusal here is the refusing call's, code and text
+    if (int rc = check_geometry("spec_conv_forward", 1, cin, cout, n, modes)) return rc;
+    LdsPlan plan;
+    if (int rc = check_lds("spec_conv_forward", cin, cout, n, modes, &plan)) return rc;
+    if (int rc = check_lds("spec_conv_backward", cout, cin, n, modes, &plan)) return rc;
+    return 0;
+}
 
 int spec_conv_forward(void* stream, const float* x, const float* wr, const float* wi, int b, int cin, int cout, int n, int modes,
                       float* y, float* xft) {

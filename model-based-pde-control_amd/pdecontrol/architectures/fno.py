@@ -12,7 +12,9 @@ own conventions so that they plug into its training module and world env unchang
 
 On CUDA tensors a rollout of the default geometry (width 32, 16 modes, 4 layers, N <= 512) runs on the whole-network HIP
 kernels (pdecontrol/surrogates/fno_hip.py, csrc/fno.hip): one launch per model evaluation and direction instead of ~170
-small kernels; any other geometry keeps the per-operator path below (fused spectral convolution + torch / rocBLAS).
+small kernels; any other geometry keeps the per-operator path below (spectral convolution + torch / rocBLAS).  There the
+spectral convolution runs on its fused HIP kernel for every fp32 geometry that kernel accepts in both directions
+(``spectral.unsupported``); any other geometry or dtype runs the torch.fft spelling, with one logged notice per geometry.
 """
 import torch
 from torch import nn

@@ -6,11 +6,16 @@ published one (Li et al. 2021):  ``y = irfft(W . rfft(x)[..., :modes], n=N)`` wi
 * CPU tensors (and CUDA tensors after ``ops.enable_fused(False)``): ``torch.fft`` -- this is also the fp32 reference the
   kernel is tested against.
 * CUDA tensors: ``libspectral_hip.so`` (include/spectral_hip.h): truncated-DFT GEMM -> complex mode mixing -> inverse-DFT
-  GEMM fused in one launch per direction, one workgroup per sample, MFMA fp32.  No fallback: a missing library raises.
-  **Parity unpinned** against the reference (nothing there to compare with); pinned against ``torch.fft`` in
-  tests/test_fno.py.
+  GEMM fused in one launch per direction, one workgroup per sample, MFMA fp32.  A missing library raises.  The kernel
+  takes every fp32 geometry that ``spec_conv_supported`` accepts for BOTH directions (channels multiples of 16, N a power
+  of two in [32, 2048], modes a multiple of 8 below N/2, channels x modes <= 1024, LDS <= 160 KiB); any other dtype or
+  geometry runs the torch.fft spelling on the GPU, announced once per geometry through the ``pdecontrol.surrogates``
+  logger -- so a module that trains on the CPU also trains on the GPU, and a geometry whose backward launch would not fit
+  never fails mid-step.  **Parity unpinned** against the reference (nothing there to compare with); pinned against the
+  dense DFT definition in tests/test_fno.py and tests/test_spectral_geometry.py.
 """
 import ctypes
+import logging
 import os
 
 import torch
@@ -22,8 +27,12 @@ _p, _i = ctypes.c_void_p, ctypes.c_int
 SYMBOLS = (
     ("spec_conv_forward", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     ("spec_conv_backward", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    ("spec_conv_supported", [_i, _i, _i, _i]),
 )
 _lib = None
+_LOG = logging.getLogger("pdecontrol.surrogates")
+_GEOMETRY = {}      # (cin, cout, n, modes) -> None (the kernel runs both directions) or the library's refusal
+_NOTIFIED = set()
 
 
 class SpectralHipError(RuntimeError):
@@ -50,6 +59,16 @@ def _check(rc):
         raise SpectralHipError(f"libspectral_hip error {rc}: {load().spec_last_error().decode(errors='replace')}")
 
 
+def unsupported(cin, cout, n, modes):
+    """None when both kernel launches accept this geometry, else the refusing call's message (asked once per geometry)."""
+    key = (int(cin), int(cout), int(n), int(modes))
+    if key not in _GEOMETRY:
+        lib = load()
+        rc = lib.spec_conv_supported(*key)
+        _GEOMETRY[key] = None if rc == 0 else f"error {rc}: {lib.spec_last_error().decode(errors='replace')}"
+    return _GEOMETRY[key]
+
+
 def _stream():
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
 
@@ -74,6 +93,9 @@ class _SpectralConvFn(torch.autograd.Function):
         x, wr, wi = x.contiguous(), wr.contiguous(), wi.contiguous()
         b, cin, n = x.shape
         cout, modes = wr.shape[1], wr.shape[2]
+        if wr.shape != (cin, cout, modes) or wi.shape != wr.shape or wr.device != x.device or wi.device != x.device:
+            raise SpectralHipError(f"weights {tuple(wr.shape)} / {tuple(wi.shape)} on {wr.device} / {wi.device} do not fit "
+                                   f"x {tuple(x.shape)} on {x.device}")
         y = torch.empty((b, cout, n), device=x.device, dtype=torch.float32)
         need = any(ctx.needs_input_grad)
         xft = torch.empty((b, cin, 2, modes), device=x.device, dtype=torch.float32) if need else None
@@ -99,12 +121,24 @@ class _SpectralConvFn(torch.autograd.Function):
         return (dx if ctx.needs_input_grad[0] else None), gwr, gwi
 
 
+def _refusal(x, wr, wi):
+    """Why the kernel cannot take this call (None: it can)."""
+    if x.dtype != torch.float32 or wr.dtype != torch.float32 or wi.dtype != torch.float32:
+        return f"dtype {x.dtype} / {wr.dtype}: the kernel is fp32"
+    return unsupported(wr.shape[0], wr.shape[1], x.shape[-1], wr.shape[-1])
+
+
 def spectral_conv1d(x, wr, wi):
     from pdecontrol.surrogates import ops
     if ops.use_fused(x):
-        if x.dtype != torch.float32:
-            raise SpectralHipError("the fused spectral convolution is fp32")
-        return _SpectralConvFn.apply(x, wr, wi)
+        reason = _refusal(x, wr, wi)
+        if reason is None:
+            return _SpectralConvFn.apply(x, wr, wi)
+        key = (x.dtype, wr.dtype, tuple(wr.shape), x.shape[-1])
+        if key not in _NOTIFIED:
+            _NOTIFIED.add(key)
+            _LOG.warning("spectral convolution Cin=%d, Cout=%d, N=%d, modes=%d (%s): the HIP kernel refuses it (%s); it runs "
+                         "on torch.fft", wr.shape[0], wr.shape[1], x.shape[-1], wr.shape[-1], x.dtype, reason)
     return spectral_conv1d_reference(x, wr, wi)
 
 

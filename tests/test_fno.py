@@ -182,7 +182,8 @@ def _fno_pair(dev, n, scaled):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,scaled,B,T", [(512, False, 4, 20), (128, True, 3, 13), (64, False, 2, 7)])
+@pytest.mark.parametrize("n,scaled,B,T", [(512, False, 4, 20), (128, True, 3, 13), (64, False, 2, 7),
+                                         (512, True, 64, 20)])     # the shape bench.py times: 1 280 (step, sample) pairs
 def test_whole_network_kernels_training_step_vs_cpu(n, scaled, B, T):
     """training_step + backward through the whole-network kernels (teacher-forced launch + free-running chain, two TBPTT
     chunks at T = 20) against the same module on the CPU: loss <= 1e-5 relative (north_star's TBPTT tolerance), every
