@@ -169,6 +169,30 @@ int sur_chunks_backward(void* stream, const sur_chunk_params* p, int nspans, con
                         const float* h_all, const float* c_all, const float* dd_all, int k_total, int b, float* dxlat_t,
                         int row_base, int row_count, const float* saved, float* workspace);
 int sur_flush_chunk_grads(void* stream, const sur_chunk_params* p, const sur_adam* adam /* may be NULL */, int overwrite);
+
+/* Latent-space rollout (LatentAutoRegPDESurrogate, the KSLatentConvolutionalLSTM ablation): the same cell and decoder
+ * parameters, but the cell output h_k is integrated in LATENT space and the running latent is decoded:
+ *   z_{-1} = lstates_t[0],   z_k = z_{k-1} + delta * h_k,   out_k = decoder(z_k)     (p->mul / p->add are not used)
+ * Forward: the cell chain as in sur_chunk_forward, an element-wise scan for z, then the decoders of all (step, sample)
+ * pairs in parallel on z.  Outputs: h_all, c_all, z_all [K,B,cs,hq]; out_all [K,B,1,N].  With `saved` (same size as for
+ * sur_chunk_forward) z_k is stored in the h_k slot of each saved block: the decoder backward takes its input from that
+ * slot, the cell backward reads only [gates | c_k] and the cell weight gradients read h_all.
+ * Backward: the decoder backward of all pairs on dout_all (may be NULL = 0), a reverse scan that turns the decoder's and
+ * the upstream dz_all gradients (dz_all may be NULL) into d loss / d h_k = delta * sum_{j >= k} d loss / d z_j, the cell
+ * chain's BPTT and the cell weight gradients.  d loss / d z_{-1} is ADDED to dlstates_t[0] after the cell backward has
+ * written the teacher-forcing gradient there.  Other arguments as sur_chunk_backward; the workspace holds
+ * sur_latent_workspace_floats(p, k, b) floats: sur_chunk_workspace_floats plus B*cs*hq for d loss / d z_{-1}, which must
+ * outlive the cell backward. */
+int sur_latent_chunk_forward(void* stream, const sur_chunk_params* p, const float* xlat_t, const float* lstates_t,
+                             const float* h0, const float* c0, int hc_bstride, int k, int s, int b, float* h_all, float* c_all,
+                             float* z_all, float* out_all, float* saved /* NULL: forward only, no backward later */);
+int sur_latent_workspace_floats(const sur_chunk_params* p, int k, int b);
+int sur_latent_chunk_backward(void* stream, const sur_chunk_params* p, const float* xlat_t, const float* lstates_t,
+                              const float* h0, const float* c0, int hc_bstride, const float* h_all, const float* c_all,
+                              const float* dout_all, const float* dz_all, const float* dh_all, const float* dc_all, int k, int s, int b,
+                              float* dxlat_t, float* dlstates_t, float* dh0, float* dc0, int row_base, int row_count,
+                              const float* saved /* what sur_latent_chunk_forward wrote */,
+                              float* workspace /* sur_latent_workspace_floats */);
 /* The reductions of a surrogate's three parameter packs (two encoders, chunk) in ONE launch; bit j of overwrite_mask
  * is the `overwrite` flag of pack j. */
 int sur_flush_all_grads(void* stream, const sur_encoder_params* e0, const sur_adam* a0, const sur_encoder_params* e1,

@@ -2435,6 +2435,46 @@ dgrad_scan_kernel(const float* __restrict__ dd_all, const float* __restrict__ do
     }
 }
 
+// Latent-space rollout (LatentAutoRegPDESurrogate): z_k = z_{k-1} + delta * h_k from z_{-1} = lstates_t[0] (the encoded
+// first given state); the decoder reads z_k.  With `saved`, z_k also replaces h_k in the h slot of the pair's saved block,
+// where dec_bwd_kernel takes the decoder's input from: cell_bwd_kernel reads only [gates | c], cell_wgrad_kernel reads h_all.
+__global__ void __launch_bounds__(TPB)
+latent_scan_kernel(const float* __restrict__ h_all, const float* __restrict__ z0, int K, int B, int sl, float delta,
+                   float* __restrict__ z_all, float* __restrict__ saved, int save_stride) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= B * sl) return;
+    const int b = e / sl, i = e - b * sl;
+    float z = z0[e];
+    for (int k = 0; k < K; ++k) {
+        const size_t idx = (size_t)k * B * sl + e;
+        z = fmaf(delta, h_all[idx], z);
+        z_all[idx] = z;
+        if (saved) saved[((size_t)k * B + b) * save_stride + 5 * sl + i] = z;
+    }
+}
+
+// Backward of latent_scan_kernel: G_k = dz_dec_k + dz_all_k + G_{k+1} (d loss / d z_k); the cell chain receives
+// d loss / d h_k = delta * G_k, written over dz_dec in place.  G_0 = d loss / d z_{-1} goes to dz0 (may be NULL).
+__global__ void __launch_bounds__(TPB)
+latent_dscan_kernel(float* __restrict__ dh_dec, const float* __restrict__ dz_all, int K, int B, int sl, float delta,
+                    float* __restrict__ dz0) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= B * sl) return;
+    float carry = 0.0f;
+    for (int k = K - 1; k >= 0; --k) {
+        const size_t idx = (size_t)k * B * sl + e;
+        carry += dh_dec[idx] + (dz_all ? dz_all[idx] : 0.0f);
+        dh_dec[idx] = delta * carry;
+    }
+    if (dz0) dz0[e] = carry;
+}
+
+// dst += src over n floats (d z_{-1} onto the teacher-forcing gradient cell_bwd_kernel wrote into dlstates_t[0])
+__global__ void __launch_bounds__(TPB) add_into_kernel(float* __restrict__ dst, const float* __restrict__ src, int n) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) dst[e] += src[e];
+}
+
 // decoder backward of every (step, sample) pair: dh_dec[m] = d loss / d h_m through the decoder; decoder parameter
 // gradients into this workgroup's partial row.  Built for DEC_BWD_OCC workgroups per CU: at N = 256 the LDS layout below
 // is 52 KB (round 2: 75 KB, two per CU), so three workgroups share a CU and the 640 pairs of a 10-step chunk are ONE round
@@ -3364,18 +3404,16 @@ int sur_chunk_saved_floats(const sur_chunk_params* p) {
     return step_saved_floats(*p);
 }
 
-int sur_chunk_forward(void* stream, const sur_chunk_params* p, const float* xlat_t, const float* lstates_t,
-                      const float* states_t, const float* h0, const float* c0, int hc_bstride, int k, int s, int b,
-                      float* h_all, float* c_all, float* d_all, float* out_all, float* saved) {
-    if (!p || !xlat_t || !h0 || !c0 || !h_all || !c_all || !d_all || k <= 0 || b <= 0 || s < 1 ||
-        !lstates_t || !states_t || hc_bstride < 0)
-        return fail(-1, "sur_chunk_forward: bad argument (need K > 0, B > 0, S >= 1)");
-    if (int rc = chunk_geometry(p, "sur_chunk_forward")) return rc;
-    if (p->hq & 15) return fail(-4, "sur_chunk_forward: latent width N/4 = %d must be a multiple of 16", p->hq);
+// The launches of a chunk forward up to the decoder: the cell chain (one workgroup per sample), then the decoders of ALL
+// (step, sample) pairs in parallel into d_all.  z_all == NULL: the decoder reads h_all (AutoRegPDESurrogate); otherwise the
+// latent scan runs in between and the decoder reads z_all (LatentAutoRegPDESurrogate).
+static int chunk_forward_launches(void* stream, const sur_chunk_params* p, const float* xlat_t, const float* lstates_t,
+                                  const float* h0, const float* c0, int hc_bstride, int k, int s, int b, float* h_all, float* c_all,
+                                  float* z_all, float* d_all, float* saved, const char* who) {
+    if (int rc = chunk_geometry(p, who)) return rc;
+    if (p->hq & 15) return fail(-4, "%s: latent width N/4 = %d must be a multiple of 16", who, p->hq);
     if (saved && sur_chunk_saved_floats(p) == 0)
-        return fail(-4, "sur_chunk_forward: hq = %d, ca = %d, cs = %d: no `saved` buffer for this geometry", p->hq, p->ca, p->cs);
-    // split path: the cell chain (one workgroup per sample), then the decoders of all (step, sample) pairs in
-    // parallel, then the integration of the predicted deltas
+        return fail(-4, "%s: hq = %d, ca = %d, cs = %d: no `saved` buffer for this geometry", who, p->hq, p->ca, p->cs);
     int psize_lstm = 0, psize_dec = 0;
     for (int i = 0; i < ST_NLSTM; ++i) psize_lstm += p->size[i];
     for (int i = ST_NLSTM; i < SUR_ST_NPARAM; ++i) psize_dec += p->size[i];
@@ -3395,12 +3433,44 @@ int sur_chunk_forward(void* stream, const sur_chunk_params* p, const float* xlat
                                       : (chain_threads == 2 * TPB ? launch_cell_fwd(cell_fwd_kernel<2 * TPB>)
                                                                   : launch_cell_fwd(cell_fwd_kernel<4 * TPB>)))
         return rc;
-    if (int rc = launch_checked([&] {
-            hipLaunchKernelGGL(dec_fwd_kernel, dim3(m < 1024 ? m : 1024), dim3(TPB), lds_dec, (hipStream_t)stream, *p, h_all, m,
-                               d_all, saved);
-        }, "dec_fwd")) return rc;
+    const float* dec_in = h_all;
+    if (z_all) {
+        const int sl = p->cs * p->hq;
+        if (int rc = launch_checked([&] {
+                hipLaunchKernelGGL(latent_scan_kernel, dim3((b * sl + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, h_all,
+                                   lstates_t, k, b, sl, p->delta, z_all, saved, step_saved_floats(*p));
+            }, "latent_scan")) return rc;
+        dec_in = z_all;
+    }
+    return launch_checked([&] {
+        hipLaunchKernelGGL(dec_fwd_kernel, dim3(m < 1024 ? m : 1024), dim3(TPB), lds_dec, (hipStream_t)stream, *p, dec_in, m,
+                           d_all, saved);
+    }, "dec_fwd");
+}
+
+int sur_chunk_forward(void* stream, const sur_chunk_params* p, const float* xlat_t, const float* lstates_t,
+                      const float* states_t, const float* h0, const float* c0, int hc_bstride, int k, int s, int b,
+                      float* h_all, float* c_all, float* d_all, float* out_all, float* saved) {
+    if (!p || !xlat_t || !h0 || !c0 || !h_all || !c_all || !d_all || k <= 0 || b <= 0 || s < 1 ||
+        !lstates_t || !states_t || hc_bstride < 0)
+        return fail(-1, "sur_chunk_forward: bad argument (need K > 0, B > 0, S >= 1)");
+    // split path: the cell chain (one workgroup per sample), then the decoders of all (step, sample) pairs in
+    // parallel, then the integration of the predicted deltas
+    if (int rc = chunk_forward_launches(stream, p, xlat_t, lstates_t, h0, c0, hc_bstride, k, s, b, h_all, c_all, nullptr, d_all,
+                                        saved, "sur_chunk_forward"))
+        return rc;
     if (!out_all) return 0;   // the caller integrates later / elsewhere (sur_chunk_integrate)
     return sur_chunk_integrate(stream, p, states_t, d_all, k, s, b, out_all);
+}
+
+int sur_latent_chunk_forward(void* stream, const sur_chunk_params* p, const float* xlat_t, const float* lstates_t,
+                             const float* h0, const float* c0, int hc_bstride, int k, int s, int b, float* h_all, float* c_all,
+                             float* z_all, float* out_all, float* saved) {
+    if (!p || !xlat_t || !lstates_t || !h0 || !c0 || !h_all || !c_all || !z_all || !out_all || k <= 0 || b <= 0 || s < 1 ||
+        hc_bstride < 0)
+        return fail(-1, "sur_latent_chunk_forward: bad argument (need K > 0, B > 0, S >= 1)");
+    return chunk_forward_launches(stream, p, xlat_t, lstates_t, h0, c0, hc_bstride, k, s, b, h_all, c_all, z_all, out_all, saved,
+                                  "sur_latent_chunk_forward");
 }
 
 int sur_chunk_integrate(void* stream, const sur_chunk_params* p, const float* states_t, const float* d_all, int k, int s, int b,
@@ -3418,10 +3488,23 @@ int sur_chunk_workspace_floats(const sur_chunk_params* p, int k, int b) {
     return k * b * (5 * p->cs * p->hq + 4 * p->hq);   // dh_dec [K,B,cs,hq] + dg_all [K,B,4,cs,hq] + ga_all [K,B,1,N]
 }
 
+int sur_latent_workspace_floats(const sur_chunk_params* p, int k, int b) {
+    const int base = sur_chunk_workspace_floats(p, k, b);
+    return base > 0 ? base + b * p->cs * p->hq : 0;   // + d loss / d z_{-1} [B,cs,hq], which must outlive the cell backward
+}
+
+// What the latent rollout's backward adds to chunks_backward_impl: the upstream gradient wrt z_all (may be NULL) and
+// where d loss / d z_{-1} lands on top of the teacher-forcing gradient (dlstates0 = dlstates_t[0], may be NULL).
+struct LatentBwd {
+    const float* dz_all;
+    float* dlstates0;
+};
+
 static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const ChunkSpans& spans, const float* xlat_t,
                                 const float* h_all, const float* c_all, const float* dd_all, const float* dout_all,
                                 const float* dh_all, const float* dc_all, int k_total, int b, float* dxlat_t, float* dh0,
-                                float* dc0, int row_base, int row_count, const float* saved, float* workspace, const char* who) {
+                                float* dc0, int row_base, int row_count, const float* saved, float* workspace, const char* who,
+                                const LatentBwd* latent = nullptr) {
     if (int rc = chunk_geometry(p, who)) return rc;
     if (!saved || !workspace) return fail(-1, "%s: needs the `saved` buffer the forward filled and a workspace", who);
     if (sur_chunk_saved_floats(p) == 0) return fail(-4, "%s: hq = %d, ca = %d, cs = %d: geometry not supported", who, p->hq, p->ca, p->cs);
@@ -3438,7 +3521,15 @@ static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const C
     float* dg_all = workspace + (size_t)m * sl;
     float* ga_all = workspace + (size_t)m * 5 * sl;
     const float* ga = dd_all;
-    if (dout_all || !dd_all) {
+    if (latent) {
+        // the decoder read z_k: its output gradient goes to the decoder backward as it is (no integration in state space)
+        ga = dout_all;
+        if (!ga) {
+            if (hipMemsetAsync(ga_all, 0, sizeof(float) * (size_t)m * n, (hipStream_t)stream) != hipSuccess)
+                return fail(-2, "%s: clearing the output gradient failed", who);
+            ga = ga_all;
+        }
+    } else if (dout_all || !dd_all) {
         if (spans.n != 1) return fail(-1, "%s: gradients wrt the outputs are supported for one chunk at a time", who);
         if (int rc = launch_checked([&] {
                 hipLaunchKernelGGL(dgrad_scan_kernel, dim3((b * n + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, dd_all,
@@ -3463,6 +3554,12 @@ static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const C
             if (dec_gl) hipLaunchKernelGGL(dec_bwd_kernel<true>, dim3(grid), dim3(TPB), lds_dec, (hipStream_t)stream, *p, saved, ga, m, dh_dec, row_base);
             else hipLaunchKernelGGL(dec_bwd_kernel<false>, dim3(grid), dim3(TPB), lds_dec, (hipStream_t)stream, *p, saved, ga, m, dh_dec, row_base);
         }, "dec_bwd")) return rc;
+    float* dz0 = latent && latent->dlstates0 ? workspace + (size_t)m * (5 * sl + n) : nullptr;
+    if (latent)
+        if (int rc = launch_checked([&] {
+                hipLaunchKernelGGL(latent_dscan_kernel, dim3((b * sl + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, dh_dec,
+                                   latent->dz_all, k_total, b, sl, p->delta, dz0);
+            }, "latent_dscan")) return rc;
     const int chain_threads = cell_chain_threads(*p);
     auto launch_cell_bwd = [&](auto kernel) -> int {
         if (int rc = set_lds(kernel, lds_cell, "cell backward")) return rc;
@@ -3475,6 +3572,11 @@ static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const C
                                       : (chain_threads == 2 * TPB ? launch_cell_bwd(cell_bwd_kernel<2 * TPB>)
                                                                   : launch_cell_bwd(cell_bwd_kernel<4 * TPB>)))
         return rc;
+    if (dz0)   // cell_bwd has WRITTEN dlstates_t[0] (the hidden input of the first, teacher-forced step): add z_{-1}'s share
+        if (int rc = launch_checked([&] {
+                hipLaunchKernelGGL(add_into_kernel, dim3((b * sl + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream,
+                                   latent->dlstates0, dz0, b * sl);
+            }, "latent_dz0")) return rc;
     return launch_checked([&] {
         if (wg_gl) hipLaunchKernelGGL(cell_wgrad_kernel<true>, dim3(grid), dim3(TPB), lds_wg, (hipStream_t)stream, *p, spans, xlat_t, h_all, dg_all, k_total, b, dxlat_t, row_base);
         else hipLaunchKernelGGL(cell_wgrad_kernel<false>, dim3(grid), dim3(TPB), lds_wg, (hipStream_t)stream, *p, spans, xlat_t, h_all, dg_all, k_total, b, dxlat_t, row_base);
@@ -3493,6 +3595,21 @@ int sur_chunk_backward(void* stream, const sur_chunk_params* p, const float* xla
     spans.sp[0] = sur_chunk_span{0, k, s < k ? s : k, lstates_t, h0, c0, hc_bstride, dlstates_t};
     return chunks_backward_impl(stream, p, spans, xlat_t, h_all, c_all, dd_all, dout_all, dh_all, dc_all, k, b, dxlat_t, dh0, dc0,
                                 row_base, row_count, saved, workspace, "sur_chunk_backward");
+}
+
+int sur_latent_chunk_backward(void* stream, const sur_chunk_params* p, const float* xlat_t, const float* lstates_t,
+                              const float* h0, const float* c0, int hc_bstride, const float* h_all, const float* c_all,
+                              const float* dout_all, const float* dz_all, const float* dh_all, const float* dc_all, int k, int s, int b,
+                              float* dxlat_t, float* dlstates_t, float* dh0, float* dc0, int row_base, int row_count,
+                              const float* saved, float* workspace) {
+    if (!p || !xlat_t || !lstates_t || !h0 || !c0 || !h_all || !c_all || k <= 0 || b <= 0 || s < 1 || hc_bstride < 0)
+        return fail(-1, "sur_latent_chunk_backward: bad argument (need K > 0, B > 0, S >= 1)");
+    ChunkSpans spans{};
+    spans.n = 1;
+    spans.sp[0] = sur_chunk_span{0, k, s < k ? s : k, lstates_t, h0, c0, hc_bstride, dlstates_t};
+    const LatentBwd latent{dz_all, dlstates_t};
+    return chunks_backward_impl(stream, p, spans, xlat_t, h_all, c_all, nullptr, dout_all, dh_all, dc_all, k, b, dxlat_t, dh0, dc0,
+                                row_base, row_count, saved, workspace, "sur_latent_chunk_backward", &latent);
 }
 
 int sur_chunks_backward(void* stream, const sur_chunk_params* p, int nspans, const sur_chunk_span* spans_in, const float* xlat_t,

@@ -3,3 +3,4 @@
 from pdecontrol.architectures.autoreg import (KSAutoRegConvolutionalLSTM, KSAutoRegConvolutionalLSTMN,
                                               KSAutoRegFullyConnectedLSTM)
 from pdecontrol.architectures.fno import BurgersFNO
+from pdecontrol.architectures.latent import KSLatentConvolutionalLSTM, KSLatentConvolutionalLSTMN, KSLatentLSTM

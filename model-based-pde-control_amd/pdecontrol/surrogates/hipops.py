@@ -83,6 +83,10 @@ SYMBOLS = (
     ("sur_fold_rows", [_fp, _EP, _EP, _CP, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     ("sur_tbptt_delta_loss_range", [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i]),
+    ("sur_latent_chunk_forward", [_fp, _CP, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
+    ("sur_latent_workspace_floats", [_CP, _i, _i]),
+    ("sur_latent_chunk_backward", [_fp, _CP, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp,
+                                   _i, _i, _fp, _fp]),
 )
 _lib = None
 
@@ -299,6 +303,15 @@ def _dscale_constants(dscaling):
     raise SurrogateHipError("fused rollout supports dscaling = identity or Normalize(scalar stats).Inverse only")
 
 
+def _chunk_scale(surrogate):
+    """(mul, add) of the chunk kernels' integration.  The latent rollout integrates in latent space and applies ``dscaling``
+    in torch (to the differences of the decoded outputs), so its kernels take any ``dscaling`` and never read these."""
+    from pdecontrol.surrogates.surrogate import LatentAutoRegPDESurrogate
+    if isinstance(surrogate, LatentAutoRegPDESurrogate):
+        return 1.0, 0.0
+    return _dscale_constants(surrogate.dscaling)
+
+
 def scaling_signature(surrogate, undscaling=None):
     """What the scaling constants baked into captured launches depend on.  The controller re-fits the delta statistics
     between training rounds (``update_delta_transform``, pdecontrol/mbrl/mbrl.py:597-602: ``Normalize.reset()`` +
@@ -374,7 +387,7 @@ def _chunk_pack(surrogate, rows):
     c.ca, c.cs, c.hq = cell.in_channels, cell.out_channels, tm.ssize
     c.c_mid = d1.deconvolution.out_channels
     c.delta = float(surrogate.delta)
-    c.mul, c.add = _dscale_constants(surrogate.dscaling)
+    c.mul, c.add = _chunk_scale(surrogate)
     return _Pack(params, c, load().sur_flush_chunk_grads, rows)
 
 
@@ -406,7 +419,7 @@ class FusedPacks:
         self.chunk.ensure_rows(batch)
         for pack in self.packs:
             pack.refresh()
-        self.chunk.c.mul, self.chunk.c.add = _dscale_constants(surrogate.dscaling)
+        self.chunk.c.mul, self.chunk.c.add = _chunk_scale(surrogate)
 
     def refresh_partials(self):
         for pack in self.packs:
@@ -588,11 +601,23 @@ class PackAdam(torch.optim.Optimizer):
 
 def fused_supported(surrogate):
     """True when ``surrogate`` has the KSAutoRegConvolutionalLSTM layout the fused kernels implement."""
+    from pdecontrol.surrogates.surrogate import AutoRegPDESurrogate
+    return isinstance(surrogate, AutoRegPDESurrogate) and _conv_lstm_layout(surrogate)
+
+
+def fused_latent_supported(surrogate):
+    """True when ``surrogate`` is a LatentAutoRegPDESurrogate with the KSLatentConvolutionalLSTM layout (the same modules as
+    KSAutoRegConvolutionalLSTM): ``fused_latent_rollout`` runs it.  ``fused_supported`` stays False for it, so no
+    autoreg-only path (fused TBPTT, captured steps, PackAdam, the world env's device path) ever sees one."""
+    from pdecontrol.surrogates.surrogate import LatentAutoRegPDESurrogate
+    return isinstance(surrogate, LatentAutoRegPDESurrogate) and _conv_lstm_layout(surrogate)
+
+
+def _conv_lstm_layout(surrogate):
     try:
         from pdecontrol.surrogates.models.cnn import ResidualBlock
-        from pdecontrol.surrogates.surrogate import AutoRegPDESurrogate
         from pdecontrol.surrogates.transition import CNNLSTMTransitionModel
-        if not isinstance(surrogate, AutoRegPDESurrogate) or not isinstance(surrogate.transition_model, CNNLSTMTransitionModel):
+        if not isinstance(surrogate.transition_model, CNNLSTMTransitionModel):
             return False
         for enc in (surrogate.state_encoder.model, surrogate.action_encoder.model):
             blocks = [getattr(enc, name) for name in getattr(enc, "layers", ())]
@@ -884,6 +909,86 @@ def fused_rollout(surrogate, states, actions, times, targets, hidden):
     by_batch = lambda t: take_steps(t.transpose(0, 1), pick)
     return ModelRollout(inlatents=None, outlatents=by_batch(h_all), deltas=by_batch(d_all), outputs=by_batch(out_all),
                         hidden=(h_all[-1], c_all[-1]))
+
+
+class _LatentChunkFn(torch.autograd.Function):
+    """K latent-rollout steps (sur_latent_chunk_forward): the cell chain, z_k = z_{k-1} + delta * h_k from z_{-1} =
+    lstates_t[0], the decoder on every z_k.  Time-major inputs / outputs as _ChunkFn.  ``train``: grad mode of the caller
+    (inside forward it is always off); without it no saved buffer is written -- no-grad inference runs forward only."""
+
+    @staticmethod
+    def forward(ctx, xlat_t, lstates_t, h0, c0, anchor, pack, owner, train):
+        xlat_t, lstates_t, h0, c0 = xlat_t.contiguous(), lstates_t.contiguous(), h0.contiguous(), c0.contiguous()
+        k, b = xlat_t.shape[:2]
+        s = lstates_t.shape[0]
+        h_all = torch.empty((k, b, pack.c.cs, pack.c.hq), device=xlat_t.device, dtype=torch.float32)
+        c_all, z_all = torch.empty_like(h_all), torch.empty_like(h_all)
+        out_all = torch.empty((k, b, 1, 4 * pack.c.hq), device=xlat_t.device, dtype=torch.float32)
+        saved = _saved_buffer(pack, k, b, xlat_t.device) if train and any(ctx.needs_input_grad) else None
+        _check(load().sur_latent_chunk_forward(_stream(), ctypes.byref(pack.c), _p(xlat_t), _p(lstates_t), _p(h0), _p(c0),
+                                               pack.c.cs * pack.c.hq, k, s, b, _p(h_all), _p(c_all), _p(z_all), _p(out_all),
+                                               _p(saved)))
+        ctx.save_for_backward(xlat_t, lstates_t, h0, c0, h_all, c_all)
+        ctx.fwd_saved = saved
+        ctx.pack, ctx.owner = pack, owner
+        ctx.needs = ctx.needs_input_grad[:4]   # (as given: a contiguous copy made in here never requires grad)
+        ctx.set_materialize_grads(False)
+        return h_all, c_all, z_all, out_all
+
+    @staticmethod
+    def backward(ctx, dh_all, dc_all, dz_all, dout_all):
+        xlat_t, lstates_t, h0, c0, h_all, c_all = ctx.saved_tensors
+        nx, nl, nh, nc = ctx.needs
+        cont = lambda t: None if t is None else t.contiguous()
+        dh_all, dc_all, dz_all, dout_all = cont(dh_all), cont(dc_all), cont(dz_all), cont(dout_all)
+        dxlat = torch.empty_like(xlat_t) if nx else None
+        dlst = torch.zeros_like(lstates_t) if nl else None
+        dh0 = torch.empty_like(h0) if nh else None
+        dc0 = torch.empty_like(c0) if nc else None
+        k, b = xlat_t.shape[:2]
+        rows = max(b, CHUNK_ROWS)
+        ctx.pack.ensure_rows(rows)
+        ctx.owner.refresh_partials()
+        work = torch.empty(load().sur_latent_workspace_floats(ctypes.byref(ctx.pack.c), k, b), device=xlat_t.device,
+                           dtype=torch.float32)
+        _check(load().sur_latent_chunk_backward(_stream(), ctypes.byref(ctx.pack.c), _p(xlat_t), _p(lstates_t), _p(h0), _p(c0),
+                                                ctx.pack.c.cs * ctx.pack.c.hq, _p(h_all), _p(c_all), _p(dout_all), _p(dz_all),
+                                                _p(dh_all), _p(dc_all), k, lstates_t.shape[0], b, _p(dxlat), _p(dlst), _p(dh0),
+                                                _p(dc0), 0, rows, _p(ctx.fwd_saved), _p(work)))
+        ctx.pack.dirty = True
+        ctx.owner.schedule_flush()
+        return dxlat, dlst, dh0, dc0, None, None, None, None
+
+
+def fused_latent_rollout(surrogate, states, actions, times, targets, hidden):
+    """GPU rollout of LatentAutoRegPDESurrogate (same outputs as surrogate.py, and as the reference's surrogate.py:159-206):
+    two encoder launches + one latent chunk.  ``deltas`` cover ALL internal steps (not picked by the targets) and
+    ``inlatents`` are the encoded given states while teacher forcing, z_{k-1} afterwards; both are computed in torch from
+    the chunk's outputs.  states [B,S,1,N], actions [B,A,1,N]."""
+    from pdecontrol.mbrl.types import ModelRollout
+    from pdecontrol.surrogates.surrogate import action_and_target_indices, take_steps
+    b, s_given, _, n = states.shape
+    owner = packs_for(surrogate, n, b)
+    cs, hq, ca = owner.chunk.c.cs, owner.chunk.c.hq, owner.chunk.c.ca
+    aidx, tidx = action_and_target_indices(times, targets, surrogate.delta)
+    actions_t = take_steps(actions, aidx.tolist()).transpose(0, 1).contiguous()         # [K, B, 1, N]
+    n_steps = actions_t.shape[0]
+    s_used = min(s_given, n_steps)
+    states_t = states[:, :s_used].transpose(0, 1).contiguous()                          # [S, B, 1, N]
+    lstates_t = encode(states_t.reshape(s_used * b, 1, n), owner.state_enc, owner).reshape(s_used, b, cs, hq)
+    lactions_t = encode(actions_t.reshape(n_steps * b, 1, n), owner.action_enc, owner).reshape(n_steps, b, ca, hq)
+    if hidden is None:
+        tm = surrogate.transition_model
+        hidden = (tm.H0.unsqueeze(0).expand(b, -1, -1), tm.C0.unsqueeze(0).expand(b, -1, -1))
+    h_all, c_all, z_all, out_all = _LatentChunkFn.apply(lactions_t, lstates_t, hidden[0], hidden[1], owner.anchor, owner.chunk,
+                                                        owner, torch.is_grad_enabled())
+    outputs = out_all.transpose(0, 1)                                                   # [B, K, 1, N]
+    deltas = surrogate.dscaling.Inverse(torch.diff(torch.cat((states[:, :1], outputs), dim=1), dim=1) / surrogate.delta)
+    inlatents_t = torch.cat((lstates_t, z_all[s_used - 1:n_steps - 1]), dim=0)          # [K, B, cs, hq]
+    pick = tidx.tolist()
+    by_batch = lambda t: take_steps(t.transpose(0, 1), pick)
+    return ModelRollout(inlatents=by_batch(inlatents_t), outlatents=by_batch(h_all), deltas=deltas,
+                        outputs=take_steps(outputs, pick), hidden=(h_all[-1], c_all[-1]))
 
 
 # ---------------------------------------------------------------------------------------------

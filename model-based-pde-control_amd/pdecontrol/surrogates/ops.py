@@ -69,10 +69,23 @@ def use_fused(tensor):
 def use_fused_for(surrogate, tensor):
     """``use_fused(tensor)`` for a surrogate the fused kernels implement; for any other architecture False, with one
     logged notice per class (it then runs on PyTorch-ROCm kernels, as in the reference)."""
+    from pdecontrol.surrogates import hipops
+    return _use_fused_layout(surrogate, tensor, hipops.fused_supported, "KSAutoRegConvolutionalLSTM")
+
+
+def use_fused_latent_for(surrogate, tensor):
+    """``use_fused_for`` of the latent-space rollout (LatentAutoRegPDESurrogate): True for the KSLatentConvolutionalLSTM
+    layout at a supported grid width; any other latent architecture (KSLatentLSTM) runs on PyTorch-ROCm kernels, announced
+    once per class."""
+    from pdecontrol.surrogates import hipops
+    return _use_fused_layout(surrogate, tensor, hipops.fused_latent_supported, "KSLatentConvolutionalLSTM")
+
+
+def _use_fused_layout(surrogate, tensor, supported, layout):
     if not (_FUSED["enabled"] and tensor.is_cuda):
         return False
     from pdecontrol.surrogates import hipops
-    if hipops.fused_supported(surrogate):
+    if supported(surrogate):
         if not use_fused(tensor):
             return False
         reason = hipops.geometry_unsupported(surrogate, tensor.shape[-1])
@@ -85,17 +98,9 @@ def use_fused_for(surrogate, tensor):
     name = type(surrogate).__name__ + "/" + type(getattr(surrogate, "transition_model", None)).__name__
     if name not in _NOTIFIED:
         _NOTIFIED.add(name)
-        _LOG.warning("%s is not the architecture the fused HIP kernels implement (KSAutoRegConvolutionalLSTM layout): "
-                     "it runs on plain PyTorch-ROCm kernels", name)
+        _LOG.warning("%s is not the architecture the fused HIP kernels implement (%s layout): "
+                     "it runs on plain PyTorch-ROCm kernels", name, layout)
     return False
-
-
-def require_plain_path(tensor, what):
-    """Surrogates the fused kernels do not implement must not run on MIOpen by accident."""
-    if tensor.is_cuda and _FUSED["enabled"]:
-        from pdecontrol.surrogates.hipops import SurrogateHipError
-        raise SurrogateHipError(f"{what} has no fused HIP implementation; to run it on plain PyTorch-ROCm kernels opt out "
-                                f"explicitly with pdecontrol.surrogates.ops.enable_fused(False) or PDECONTROL_FUSED=0")
 
 
 def conv_act_norm(x, conv, activation, layernorm):

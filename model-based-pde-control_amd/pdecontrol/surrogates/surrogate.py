@@ -152,7 +152,10 @@ class LatentAutoRegPDESurrogate(_EncDecSurrogate):
 
     def rollout(self, states: torch.Tensor, actions: torch.Tensor, times: torch.Tensor, targets: torch.Tensor,
                 hidden=None, **kwargs) -> ModelRollout:
-        ops.require_plain_path(states, "LatentAutoRegPDESurrogate (ablation)")
+        if ops.use_fused_latent_for(self, states):
+            # the KSLatentConvolutionalLSTM layout: two encoder launches and one latent chunk (hipops._LatentChunkFn)
+            from pdecontrol.surrogates import hipops
+            return hipops.fused_latent_rollout(self, states, actions, times, targets, hidden)
         n_given = states.size(1)
         lstates = self.state_encoder(states)
         aidx, tidx = action_and_target_indices(times, targets, self.delta)
