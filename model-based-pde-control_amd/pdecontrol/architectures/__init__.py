@@ -4,3 +4,4 @@ from pdecontrol.architectures.autoreg import (KSAutoRegConvolutionalLSTM, KSAuto
                                               KSAutoRegFullyConnectedLSTM)
 from pdecontrol.architectures.fno import BurgersFNO
 from pdecontrol.architectures.latent import KSLatentConvolutionalLSTM, KSLatentConvolutionalLSTMN, KSLatentLSTM
+from pdecontrol.architectures.delay import KSDelayCNNSurrogateFactory

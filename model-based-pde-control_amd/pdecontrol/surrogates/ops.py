@@ -69,8 +69,27 @@ def use_fused(tensor):
 def use_fused_for(surrogate, tensor):
     """``use_fused(tensor)`` for a surrogate the fused kernels implement; for any other architecture False, with one
     logged notice per class (it then runs on PyTorch-ROCm kernels, as in the reference)."""
+    if is_delay(surrogate):
+        return False   # its own kernels and its own notice: use_fused_delay_for
     from pdecontrol.surrogates import hipops
     return _use_fused_layout(surrogate, tensor, hipops.fused_supported, "KSAutoRegConvolutionalLSTM")
+
+
+def is_delay(surrogate):
+    """True for a surrogate with a DelayTransitionModel (the KSDelayCNNSurrogateFactory ablation)."""
+    from pdecontrol.surrogates.transition import DelayTransitionModel
+    return isinstance(getattr(surrogate, "transition_model", None), DelayTransitionModel)
+
+
+def use_fused_delay_for(surrogate, tensor):
+    """``use_fused_for`` of a delay-embedding surrogate: True for the KSDelayCNNSurrogateFactory layout on fp32 CUDA
+    tensors of width 64 (``delay_hip.fused_delay_rollout``); any other delay model, fp64 input or an unsupported dscaling
+    form runs on PyTorch-ROCm kernels, announced once.  False without a notice for any other transition model."""
+    if not is_delay(surrogate):
+        return False
+    from pdecontrol.surrogates import delay_hip
+    return _use_fused_layout(surrogate, tensor, delay_hip.fused_delay_supported, "KSDelayCNNSurrogateFactory",
+                             geometry=lambda sur, t: delay_hip.geometry_unsupported(sur, t), lib=delay_hip.load)
 
 
 def use_fused_latent_for(surrogate, tensor):
@@ -81,14 +100,17 @@ def use_fused_latent_for(surrogate, tensor):
     return _use_fused_layout(surrogate, tensor, hipops.fused_latent_supported, "KSLatentConvolutionalLSTM")
 
 
-def _use_fused_layout(surrogate, tensor, supported, layout):
+def _use_fused_layout(surrogate, tensor, supported, layout, geometry=None, lib=None):
     if not (_FUSED["enabled"] and tensor.is_cuda):
         return False
     from pdecontrol.surrogates import hipops
     if supported(surrogate):
-        if not use_fused(tensor):
+        if lib is not None:
+            lib()           # raises when the library has not been built: no silent fallback
+        elif not use_fused(tensor):
             return False
-        reason = hipops.geometry_unsupported(surrogate, tensor.shape[-1])
+        reason = (hipops.geometry_unsupported(surrogate, tensor.shape[-1]) if geometry is None
+                  else geometry(surrogate, tensor))
         if reason is None:
             return True
         if reason not in _NOTIFIED:

@@ -97,16 +97,21 @@ class _EncDecSurrogate(PDESurrogate):
 class AutoRegPDESurrogate(_EncDecSurrogate):
     """State-space autoregression: next = prev + delta * dscaling(decoder(transition(...))).
 
-    ``reencode_predictions``: the reference re-encodes every prediction (``inlast``) but its
+    ``reencode_predictions``: the reference re-encodes every prediction (``inlast``) but the ConvLSTM's and the LSTM's
     free-running transition ignores that input (transition.py:285-296), so the encoder pass only
     ever populates ``ModelRollout.inlatents``, which nothing reads.  True (default) keeps that
     field identical to the reference; the training module switches it off (inlatents = None) and
-    saves roughly a third of the forward work.  Outputs / deltas / hidden are unaffected."""
+    saves roughly a third of the forward work.  Outputs / deltas / hidden are unaffected.  A transition model whose
+    free-running step reads the prediction (``reads_free_running_state``: the delay model) keeps it on."""
 
     reencode_predictions = True
 
     def rollout(self, states: torch.Tensor, actions: torch.Tensor, times: torch.Tensor, targets: torch.Tensor,
                 hidden=None, **kwargs) -> ModelRollout:
+        if ops.use_fused_delay_for(self, states):
+            # the KSDelayCNNSurrogateFactory layout: the whole rollout in one launch (delay_hip._DelayRolloutFn)
+            from pdecontrol.surrogates import delay_hip
+            return delay_hip.fused_delay_rollout(self, states, actions, times, targets, hidden)
         if ops.use_fused_for(self, states):
             # one launch per module instead of ~60 per time step (no inlatents in this mode)
             from pdecontrol.surrogates import hipops

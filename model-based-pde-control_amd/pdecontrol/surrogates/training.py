@@ -103,9 +103,11 @@ class PDETrainingModule(pl.LightningModule):
                 return [out]
         rollouts = []
         seed_states, hidden = None, None
-        autoreg = isinstance(self.surrogate, AutoRegPDESurrogate)
+        # inlatents are never read by the loss: skip the re-encoding unless the free-running transition reads it
+        autoreg = (isinstance(self.surrogate, AutoRegPDESurrogate)
+                   and not getattr(self.surrogate.transition_model, "reads_free_running_state", False))
         if autoreg:
-            self.surrogate.reencode_predictions = False  # inlatents are never read by the loss
+            self.surrogate.reencode_predictions = False
         try:
             for c, achunk in enumerate(torch.split(actions, self.tbtt, dim=1)):
                 if c == 0:

@@ -2,7 +2,8 @@
 
 API / state_dict mirror of the reference's ``pdecontrol/surrogates/transition.py``:
 ``TransitionModel`` :7-31, ``CNNLSTMCell`` :112-226, ``CNNLSTMTransitionModel`` :229-296 (the hot
-one), ``LSTMTransitionModel`` :34-109 (fully connected ablation).  Parameter names (``Wxi`` ...
+one), ``LSTMTransitionModel`` :34-109 (fully connected ablation), ``DelayTransitionModel`` :299-382 (delay-embedding
+ablation; its GPU kernels are ``pdecontrol.surrogates.delay_hip``).  Parameter names (``Wxi`` ...
 ``Who``, ``H0``, ``C0``, ``cnnlstmcell``, ``lstm``) and construction order are the reference's.
 The cell arithmetic itself lives in ``pdecontrol.surrogates.ops.lstm_cell`` (torch on CPU, one
 fused HIP kernel for all 8 circular convolutions + gates on the GPU).
@@ -14,6 +15,11 @@ from pdecontrol.surrogates import ops
 
 
 class TransitionModel(nn.Module):
+    # whether the free-running ``transition`` reads its ``states`` input (the re-encoded prediction).  The recurrent
+    # models carry their own hidden state and ignore it, so the training loop may skip the re-encoding; a model that
+    # reads it sets this True.
+    reads_free_running_state = False
+
     def __init__(self, schannels: int, ssize: int, achannels: int, asize: int, dtype=torch.FloatTensor, **kwargs):
         super().__init__()
         self.dtype = dtype
@@ -119,3 +125,57 @@ class LSTMTransitionModel(TransitionModel):
         hidden = self._initial(bsize) if hidden is None else hidden
         outputs, hidden = self.lstm(actions.reshape(bsize, steps, -1), hidden)
         return outputs.reshape(bsize, steps, self.schannels, self.ssize), hidden
+
+
+class DelayTransitionModel(TransitionModel):
+    """MLP on a sliding window of the last ``delay`` encoded states and actions.
+
+    ``hidden = (scontext [B, delay, schannels, ssize], acontext [B, delay, achannels, asize])``, oldest slot first.  A step
+    drops the oldest slot and appends the given state / action; ``fwd_model`` maps the flattened window to the next
+    latent.  The free-running step appends its (detached) ``states`` input -- the re-encoded prediction -- so it sets
+    ``reads_free_running_state``.  Values are the reference's; unlike the reference, a hidden passed in by the caller is
+    never written to, and the zero context is made on the input's device and dtype."""
+
+    reads_free_running_state = True
+
+    def __init__(self, schannels: int, ssize: int, achannels: int, asize: int, fwd_model: nn.Module, delay: int,
+                 dtype=torch.FloatTensor):
+        super().__init__(schannels=schannels, ssize=ssize, achannels=achannels, asize=asize, dtype=dtype)
+        self.delay = delay
+        self.fwd_model = fwd_model
+
+    def forward(self, scontext, acontext):
+        bsize, ssteps, schannels, ssize = scontext.shape
+        _, asteps, achannels, asize = acontext.shape
+        assert ssteps == self.delay and asteps == self.delay and ssize == asize
+        augmented = torch.cat((scontext, acontext), dim=2).reshape(bsize, self.delay * (schannels + achannels), ssize)
+        return self.fwd_model(augmented).reshape(bsize, 1, self.schannels, self.ssize)
+
+    def _context(self, like, hidden):
+        if hidden is not None:
+            return hidden
+        b = like.size(0)
+        return (like.new_zeros(b, self.delay, self.schannels, self.ssize),
+                like.new_zeros(b, self.delay, self.achannels, self.asize))
+
+    @staticmethod
+    def _shift(context, newest):
+        """The window one step on: slots 1.. of ``context`` then ``newest`` [B, C, S] (a new tensor)."""
+        return torch.cat((context[:, 1:], newest.unsqueeze(1)), dim=1)
+
+    def teacherforcing(self, states, actions, hidden=None, **kwargs):
+        assert states.size(1) == actions.size(1)
+        scontext, acontext = self._context(states, hidden)
+        outputs = []
+        for idx in range(states.size(1)):
+            scontext = self._shift(scontext, states[:, idx])
+            acontext = self._shift(acontext, actions[:, idx])
+            outputs.append(self(scontext, acontext))
+        return torch.cat(outputs, dim=1), (scontext, acontext)
+
+    def transition(self, states, actions, hidden=None, **kwargs):
+        assert states.size(1) == 1 and actions.size(1) == 1
+        scontext, acontext = self._context(states, hidden)
+        scontext = self._shift(scontext, states[:, 0].detach())
+        acontext = self._shift(acontext, actions[:, 0])
+        return self(scontext, acontext), (scontext, acontext)
