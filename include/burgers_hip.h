@@ -34,6 +34,22 @@ int bg_step(void* stream, float* u, const float* actions, const float* F, int n_
 /* test hook: out [n_rows,N] = nu * laplace(u) - u * grad(u) + phi (phi may be NULL) */
 int bg_residual(void* stream, const float* u, const float* phi, int n_rows, int N, float dx, float nu, float* out);
 
+/* Physics-informed loss of the reference's BurgersPhyPDELoss (phyloss.py:17-25, 62-86) on augmented [B,T,N] fp32:
+ *   target[:,0] = augmented[:,T-1] (the LAST slice, as the reference has it), target[:,t] = Phi(augmented[:,t-1]) with
+ *   Phi = `substeps` explicit-midpoint steps of the residual above (no forcing), loss = (augmented - target)^2.
+ * One launch each, one (b,t) row per wavefront as in the stepper; no atomics, results bit-identical run to run.
+ *
+ * forward:  loss [B,T,N] out.  diff [B,T,N] out (augmented - target) or NULL when no gradient will be asked for.  With diff
+ *           and substeps > 1, states must hold B*(T-1)*(substeps-1)*N floats (states_len = its capacity in floats): the
+ *           state before sub-steps 1 .. substeps-1 of every row t <= T-2, read back by the adjoint.  NULL otherwise.
+ * backward: g_loss [B,T,N] = d L / d loss; diff and states as the forward wrote them; grad [B,T,N] out = d L / d augmented
+ *           = e_t - [t <= T-2] DPhi(a_t)^T e_(t+1) - [t = T-1] e_0 with e = 2 diff g_loss; the midpoint sub-steps are
+ *           walked in reverse with J(v)^T p = nu laplace(p) - grad(v) p + grad(v p). */
+int bg_phyloss_forward(void* stream, const float* augmented, int B, int T, int N, float dx, float dt, float nu, int substeps,
+                       float* loss, float* diff, float* states, long states_len);
+int bg_phyloss_backward(void* stream, const float* augmented, const float* diff, const float* g_loss, const float* states,
+                        long states_len, int B, int T, int N, float dx, float dt, float nu, int substeps, float* grad);
+
 const char* bg_last_error(void);
 
 #ifdef __cplusplus

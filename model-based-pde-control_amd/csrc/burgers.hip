@@ -42,6 +42,14 @@ struct Args {
     float dt, hdt;
 };
 
+// the stencil coefficients every kernel of this file reads, pre-divided once on the host
+void set_coefficients(Args& a, float dx, float dt, float nu) {
+    a.half_inv_dx = 0.5f / dx;
+    const float s = nu / (dx * dx);
+    a.l0 = s * (-5.0f / 2.0f); a.l1 = s * (4.0f / 3.0f); a.l2 = s * (-1.0f / 12.0f);
+    a.dt = dt; a.hdt = 0.5f * dt;
+}
+
 // DPP control words (GFX9): wave_ror:1 = 0x13C (lane i receives lane i-1), wave_rol:1 = 0x134 (lane i receives lane i+1)
 __device__ __forceinline__ float from_lower(float x) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x13C, 0xf, 0xf, false));
@@ -242,6 +250,182 @@ hipError_t launch(const Args& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Physics-informed loss (the reference's BurgersPhyPDELoss.__call__, phyloss.py:17-25): for augmented [B, T, N]
+//   target[:, 0] = a[:, T-1],  target[:, t] = Phi(a[:, t-1]) (Phi = ``substeps`` midpoint steps),  loss = (a - target)^2.
+// Same layout as bg_step_kernel: one row (b, t) = one wavefront, P points per lane, the halo by ``window``.  Row (b, t)
+// produces slot t + 1 (row T - 1: slot 0), so no row waits for another.  Stored for the adjoint: diff [B, T, N] and, for
+// substeps > 1, the state before sub-steps 1 .. substeps-1 of every row t <= T-2 ([B, T-1, substeps-1, N]; the state
+// before sub-step 0 is a_t itself).
+struct PhyArgs {
+    Args c;                    // coefficients only
+    const float* a;            // [B, T, N]
+    const float* diff_in;      // backward: [B, T, N]
+    const float* g;            // backward: d L / d loss [B, T, N]
+    float* loss;               // forward out [B, T, N]
+    float* diff;               // forward out [B, T, N] or null
+    float* states;             // forward out / backward in, or null
+    float* grad;               // backward out [B, T, N]
+    int B, T, N, S;
+};
+
+template <int P>
+__device__ __forceinline__ void midpoint_step(float (&u)[P], const Args& c) {
+    float w[P + 4], r[P], ut[P], zero[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) zero[j] = 0.0f;
+    window<P>(u, w);
+    residual<P>(w, zero, c, r);
+#pragma unroll
+    for (int j = 0; j < P; ++j) ut[j] = fmaf(c.hdt, r[j], u[j]);
+    window<P>(ut, w);
+    residual<P>(w, zero, c, r);
+#pragma unroll
+    for (int j = 0; j < P; ++j) u[j] = fmaf(c.dt, r[j], u[j]);
+}
+
+// out = J(v)^T p = nu Lap(p) - Grad(v) o p + Grad(v o p), from the windows of v and p (Lap is symmetric, the central Grad
+// antisymmetric under the periodic boundary; the window of v o p is the product of the windows: no further rotation)
+template <int P>
+__device__ __forceinline__ void residual_adjoint(const float (&wv)[P + 4], const float (&wp)[P + 4], const Args& c, float (&out)[P]) {
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const float gradv = (wv[j + 3] - wv[j + 1]) * c.half_inv_dx;
+        const float gradq = fmaf(wv[j + 3], wp[j + 3], -(wv[j + 1] * wp[j + 1])) * c.half_inv_dx;
+        float acc = fmaf(c.l0, wp[j + 2], gradq);
+        acc = fmaf(c.l1, wp[j + 1] + wp[j + 3], acc);
+        acc = fmaf(c.l2, wp[j] + wp[j + 4], acc);
+        out[j] = fmaf(-gradv, wp[j + 2], acc);
+    }
+}
+
+// lam (d L / d u') -> d L / d u of one midpoint sub-step started at u:  w = dt J(u~)^T lam',  lam = lam' + w + dt/2 J(u)^T w
+template <int P>
+__device__ __forceinline__ void midpoint_step_adjoint(const float (&u)[P], float (&lam)[P], const Args& c) {
+    float wu[P + 4], wt[P + 4], wl[P + 4], r[P], ut[P], w[P], zero[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) zero[j] = 0.0f;
+    window<P>(u, wu);
+    residual<P>(wu, zero, c, r);
+#pragma unroll
+    for (int j = 0; j < P; ++j) ut[j] = fmaf(c.hdt, r[j], u[j]);
+    window<P>(ut, wt);
+    window<P>(lam, wl);
+    residual_adjoint<P>(wt, wl, c, w);
+#pragma unroll
+    for (int j = 0; j < P; ++j) w[j] *= c.dt;
+    window<P>(w, wl);
+    residual_adjoint<P>(wu, wl, c, r);
+#pragma unroll
+    for (int j = 0; j < P; ++j) lam[j] = fmaf(c.hdt, r[j], lam[j] + w[j]);
+}
+
+template <int P>
+__global__ void __launch_bounds__(256) bg_phyloss_fwd_kernel(const PhyArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int slot = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int rows = a.B * a.T;
+    const bool active = slot < rows;
+    const int row = active ? slot : rows - 1;       // tail waves redo the last row (their lanes must still rotate)
+    const int b = row / a.T, t = row - b * a.T;
+    const size_t col = (size_t)lane * P;
+    const float* src = a.a + (size_t)row * a.N + col;
+
+    float u[P], d[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) u[j] = src[j];
+    size_t out;                                      // the slot this row produces
+    if (t + 1 < a.T) {
+        float* st = a.states ? a.states + ((size_t)(b * (a.T - 1) + t) * (a.S - 1)) * a.N + col : nullptr;
+        for (int s = 0; s < a.S; ++s) {
+            if (st && s > 0 && active) {
+#pragma unroll
+                for (int j = 0; j < P; ++j) st[(size_t)(s - 1) * a.N + j] = u[j];
+            }
+            midpoint_step<P>(u, a.c);
+        }
+        out = (size_t)(row + 1) * a.N + col;
+#pragma unroll
+        for (int j = 0; j < P; ++j) d[j] = a.a[out + j] - u[j];
+    } else {                                         // slot 0 is compared with the LAST slice (the reference's choice)
+        out = (size_t)(b * a.T) * a.N + col;
+#pragma unroll
+        for (int j = 0; j < P; ++j) d[j] = a.a[out + j] - u[j];
+    }
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) a.loss[out + j] = d[j] * d[j];
+        if (a.diff) {
+#pragma unroll
+            for (int j = 0; j < P; ++j) a.diff[out + j] = d[j];
+        }
+    }
+}
+
+// d L / d a_t = e_t - [t <= T-2] DPhi(a_t)^T e_{t+1} - [t = T-1] e_0,  e = 2 diff g.  One row per wavefront, no atomics.
+template <int P>
+__global__ void __launch_bounds__(256) bg_phyloss_bwd_kernel(const PhyArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int slot = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int rows = a.B * a.T;
+    const bool active = slot < rows;
+    const int row = active ? slot : rows - 1;
+    const int b = row / a.T, t = row - b * a.T;
+    const size_t col = (size_t)lane * P;
+    const size_t own = (size_t)row * a.N + col;
+    const size_t other = (t + 1 < a.T ? (size_t)(row + 1) : (size_t)(b * a.T)) * a.N + col;
+
+    float lam[P], u[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) lam[j] = 2.0f * a.diff_in[other + j] * a.g[other + j];
+    if (t + 1 < a.T) {
+        const float* st = a.S > 1 ? a.states + ((size_t)(b * (a.T - 1) + t) * (a.S - 1)) * a.N + col : nullptr;
+        for (int s = a.S - 1; s >= 0; --s) {
+            const float* src = s > 0 ? st + (size_t)(s - 1) * a.N : a.a + own;
+#pragma unroll
+            for (int j = 0; j < P; ++j) u[j] = src[j];
+            midpoint_step_adjoint<P>(u, lam, a.c);
+        }
+    }
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) a.grad[own + j] = fmaf(2.0f * a.diff_in[own + j], a.g[own + j], -lam[j]);
+    }
+}
+
+template <int P>
+hipError_t launch_phyloss(const PhyArgs& a, bool backward, hipStream_t st) {
+    const int waves_per_block = 4;
+    const int grid = (a.B * a.T + waves_per_block - 1) / waves_per_block;
+    if (backward) hipLaunchKernelGGL(bg_phyloss_bwd_kernel<P>, dim3(grid), dim3(64 * waves_per_block), 0, st, a);
+    else hipLaunchKernelGGL(bg_phyloss_fwd_kernel<P>, dim3(grid), dim3(64 * waves_per_block), 0, st, a);
+    return hipGetLastError();
+}
+
+// shared host-side validation and dispatch of the two loss entry points
+int phyloss_launch(const char* who, PhyArgs& a, bool backward, void* stream, long states_len, float dx, float dt, float nu) {
+    if (a.B <= 0 || a.T <= 0 || a.N <= 0 || a.S < 1) return fail(-1, "%s: bad argument", who);
+    if (!(dx > 0.0f) || !(dt > 0.0f) || !(nu >= 0.0f)) return fail(-1, "%s: dx, dt must be positive, nu non-negative", who);
+    if (a.N % 64) return fail(-4, "%s: N = %d is not a multiple of 64", who, a.N);
+    if ((long)a.B * a.T > (1L << 30)) return fail(-1, "%s: B * T = %ld rows is too many", who, (long)a.B * a.T);
+    const long need = (long)a.B * (a.T - 1) * (a.S - 1) * a.N;
+    if (a.states ? states_len < need : (backward && need > 0))
+        return fail(-3, "%s: the sub-step state store holds %ld floats, B (T-1) (substeps-1) N = %ld are needed", who,
+                    a.states ? states_len : 0L, need);
+    set_coefficients(a.c, dx, dt, nu);
+    hipError_t e;
+    switch (a.N / 64) {
+        case 1: e = launch_phyloss<1>(a, backward, (hipStream_t)stream); break;
+        case 2: e = launch_phyloss<2>(a, backward, (hipStream_t)stream); break;
+        case 4: e = launch_phyloss<4>(a, backward, (hipStream_t)stream); break;
+        case 8: e = launch_phyloss<8>(a, backward, (hipStream_t)stream); break;
+        case 16: e = launch_phyloss<16>(a, backward, (hipStream_t)stream); break;
+        default: return fail(-4, "%s: N = %d: supported sizes are 64, 128, 256, 512, 1024", who, a.N);
+    }
+    if (e != hipSuccess) return fail(-2, "%s launch failed: %s", who, hipGetErrorString(e));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -257,10 +441,7 @@ int bg_step(void* stream, float* u, const float* actions, const float* F, int n_
     Args a{};
     a.u = u; a.actions = actions; a.F = F; a.obs = obs; a.ssq_sum = ssq_sum; a.status = status;
     a.n_act = n_act; a.n_envs = n_envs; a.N = N; a.n_substeps = n_substeps;
-    a.half_inv_dx = 0.5f / dx;
-    const float s = nu / (dx * dx);
-    a.l0 = s * (-5.0f / 2.0f); a.l1 = s * (4.0f / 3.0f); a.l2 = s * (-1.0f / 12.0f);
-    a.dt = dt; a.hdt = 0.5f * dt;
+    set_coefficients(a, dx, dt, nu);
     hipError_t e;
     switch (N / 64) {
         case 1: e = launch<1>(a, (hipStream_t)stream); break;
@@ -283,6 +464,26 @@ int bg_residual(void* stream, const float* u, const float* phi, int n_rows, int 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(-2, "bg_residual launch failed: %s", hipGetErrorString(e));
     return 0;
+}
+
+int bg_phyloss_forward(void* stream, const float* augmented, int B, int T, int N, float dx, float dt, float nu, int substeps,
+                       float* loss, float* diff, float* states, long states_len) {
+    if (!augmented || !loss) return fail(-1, "bg_phyloss_forward: bad argument");
+    if (states && !diff) return fail(-1, "bg_phyloss_forward: a state store without diff");
+    PhyArgs a{};
+    a.a = augmented; a.loss = loss; a.diff = diff; a.states = substeps > 1 ? states : nullptr;
+    a.B = B; a.T = T; a.N = N; a.S = substeps;
+    if (diff && substeps > 1 && T > 1 && !states) return fail(-3, "bg_phyloss_forward: substeps > 1 with diff needs the state store");
+    return phyloss_launch("bg_phyloss_forward", a, false, stream, states_len, dx, dt, nu);
+}
+
+int bg_phyloss_backward(void* stream, const float* augmented, const float* diff, const float* g_loss, const float* states,
+                        long states_len, int B, int T, int N, float dx, float dt, float nu, int substeps, float* grad) {
+    if (!augmented || !diff || !g_loss || !grad) return fail(-1, "bg_phyloss_backward: bad argument");
+    PhyArgs a{};
+    a.a = augmented; a.diff_in = diff; a.g = g_loss; a.states = const_cast<float*>(states); a.grad = grad;
+    a.B = B; a.T = T; a.N = N; a.S = substeps;
+    return phyloss_launch("bg_phyloss_backward", a, true, stream, states_len, dx, dt, nu);
 }
 
 }  // extern "C"

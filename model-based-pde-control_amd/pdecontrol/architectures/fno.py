@@ -7,7 +7,8 @@ own conventions so that they plug into its training module and world env unchang
   -> project (pointwise conv width -> width -> 1); the published architecture (Li et al. 2021) in 1-D.
 * ``FNOAutoRegSurrogate``: the same contract as ``AutoRegPDESurrogate.rollout`` (pdecontrol/surrogates/surrogate.py:79-133):
   ``next = prev + delta * dscaling(model(prev, action))``, teacher forced on the given states, free running afterwards,
-  same integer path for action / target indices; stateless (``hidden`` is an empty tuple).  ``training_mode = "delta"``.
+  same integer path for action / target indices; stateless (``hidden`` is an empty tuple).  ``training_mode`` is "delta"
+  (default) or "decoded" (constructor keyword): which of the two tensors ``PDETrainingModule`` hands to its loss.
 * ``BurgersFNO``: the factory (``--factory BurgersFNO``), ``model(N=..., width=..., modes=..., layers=...)``.
 
 On CUDA tensors a rollout of the default geometry (width 32, 16 modes, 4 layers, N <= 512) runs on the whole-network HIP
@@ -89,8 +90,13 @@ class FNO1d(nn.Module):
 class FNOAutoRegSurrogate(PDESurrogate):
     training_mode = "delta"
 
-    def __init__(self, model: nn.Module, delta: float, dscaling: BatchTransform = None, **kwargs):
+    def __init__(self, model: nn.Module, delta: float, dscaling: BatchTransform = None, training_mode: str = "delta", **kwargs):
         super().__init__()
+        if training_mode not in ("delta", "decoded"):
+            raise ValueError(f"training_mode must be 'delta' or 'decoded', got {training_mode!r}")
+        # what PDETrainingModule's loss reads: the predicted deltas (MSELoss against the true ones) or the decoded states
+        # (a loss on the trajectory itself, e.g. phyloss.BurgersPhyPDELoss)
+        self.training_mode = training_mode
         self.model, self.delta = model, delta
         self.dscaling = BatchTransform(Identity()) if dscaling is None else dscaling
 

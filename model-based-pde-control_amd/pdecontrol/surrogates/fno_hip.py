@@ -11,8 +11,8 @@ free running afterwards, ``next = prev + delta * dscaling(model(prev, action))``
             saved spectra into the spectral weight gradients.
 
 ``_FNORolloutFn`` is a single autograd node per rollout, ``_FNOTBPTTFn`` one node for the training module's whole TBPTT pass
-(all chunks; their backward chains run concurrently): parameters go in as inputs, their gradients come out of ``backward`` --
-ordinary autograd, so optimizers, DDP hooks and hipGraph capture see nothing unusual.  There is no
+(all chunks; their backward chains run concurrently; a loss may read the deltas, the decoded outputs or both): parameters
+go in as inputs, their gradients come out of ``backward`` -- ordinary autograd, so optimizers, DDP hooks and hipGraph capture see nothing unusual.  There is no
 reference-side pin for any of this (the reference has no FNO): the kernels are pinned against the torch spelling
 (tests/test_fno.py).
 """
@@ -155,7 +155,8 @@ def _backward_launches(lib, w, states, acts, outputs, pre, n_given, cscale, g_de
         if free:
             u_ptr, ust, usb = outputs[k0 - 1].data_ptr(), 0, outputs.stride(1)
             if g_outputs is not None:
-                gout = g_outputs[k0] if gout is None else gout + g_outputs[k0]
+                # (in place: gout is one of the private ``gouts`` buffers, so a side stream allocates nothing here)
+                gout = g_outputs[k0] if gout is None else gout.add_(g_outputs[k0])
         else:
             u_ptr, ust, usb = states.data_ptr(), states.stride(1), states.stride(0)
         new_gout = gouts[k0 - n_given] if free else dstates
@@ -287,13 +288,13 @@ class _FNOTBPTTFn(torch.autograd.Function):
         if need:
             ctx.save_for_backward(states, actions, outputs, pre, xspec, *params)
             ctx.meta = (B, T, N, float(cscale), [(k0, K, ng) for k0, K, ng, _ in chunks], int(tau))
-        ctx.mark_non_differentiable(outputs)
+        ctx.set_materialize_grads(False)
         del keep
         return deltas, outputs
 
     @staticmethod
-    def backward(ctx, g_deltas, _g_outputs):
-        if not ctx.need:
+    def backward(ctx, g_deltas, g_outputs):
+        if not ctx.need or (g_deltas is None and g_outputs is None):
             return (None,) * len(ctx.needs_input_grad)
         from pdecontrol.surrogates import hipops
         lib = load()
@@ -303,7 +304,15 @@ class _FNOTBPTTFn(torch.autograd.Function):
         params = saved[5:]
         dev = states.device
         w, keep = _weights_struct(params)
-        g_deltas = g_deltas.contiguous()
+        g_deltas = torch.zeros_like(outputs) if g_deltas is None else g_deltas.contiguous()
+        if g_outputs is not None:
+            # a loss on the decoded states: outputs[k] = base[k] + cscale * deltas[k] + cshift, so a teacher-forced step's
+            # share goes into its delta gradient, chunk by chunk; the free-running steps add theirs to what the next step
+            # hands back (_backward_launches).  The seed of a later chunk is cut from the graph, as in the forward.
+            g_outputs = g_outputs.contiguous()
+            g_deltas = g_deltas.clone()
+            for k0, _, ng in chunks:
+                g_deltas[k0:k0 + ng].add_(g_outputs[k0:k0 + ng], alpha=cscale)
         # every buffer is allocated here, on the current stream, before the branches fork
         rows = torch.empty((T * B, lib.fno_row_width()), device=dev, dtype=torch.float32)
         gspec = torch.empty((LAYERS, 2 * MODES, T * B, WIDTH), device=dev, dtype=torch.float32)
@@ -313,7 +322,7 @@ class _FNOTBPTTFn(torch.autograd.Function):
         for c, (k0, K, ng) in enumerate(chunks):
             seed = states[:, :ng] if k0 == 0 else outputs[k0 - 1].view(B, 1, 1, N)
             args = (lib, w, seed, actions[:, k0:k0 + K], outputs[k0:], pre[k0 * B:], ng, cscale, g_deltas[k0:], gspec, T * B,
-                    k0 * B, rows[k0 * B:], gouts[c])
+                    k0 * B, rows[k0 * B:], gouts[c], None if g_outputs is None else g_outputs[k0:])
             if c + 1 < len(chunks):       # every chunk but the last on a side stream; the last one on the current stream
                 fork = hipops._Fork(streams[c])
                 with fork:

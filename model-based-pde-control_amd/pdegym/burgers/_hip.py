@@ -9,6 +9,8 @@ _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 SYMBOLS = (
     ("bg_step", [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, ctypes.c_long, _p, _p, _p]),
     ("bg_residual", [_p, _p, _p, _i, _i, _f, _f, _p]),
+    ("bg_phyloss_forward", [_p, _p, _i, _i, _i, _f, _f, _f, _i, _p, _p, _p, ctypes.c_long]),
+    ("bg_phyloss_backward", [_p, _p, _p, _p, _p, ctypes.c_long, _i, _i, _i, _f, _f, _f, _i, _p]),
 )
 _lib = None
 
