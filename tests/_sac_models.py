@@ -1,0 +1,213 @@
+"""Shared pieces of the SAC tests and of tools/gen_sac_golden.py: spaces, configurations, seeded batches and the scenario
+the fixture tests/golden/sac_golden.npz records (run there on the reference's class, in tests/test_sac_host.py on ours)."""
+from argparse import Namespace
+
+import numpy as np
+import torch
+
+# tag -> (hidden, B, updates, automatic entropy tuning, target_update_interval, seed)
+CASES = {"h32": (32, 16, 3, False, 1, 101), "h32_auto": (32, 16, 3, True, 2, 102), "h256": (256, 256, 2, False, 1, 103)}
+OBS, ACT, N_ACT_OBS = 64, 4, 10
+LOG_KEYS = ("Pol. Rew. Mean", "SAC/Qloss", "SAC/PolicyLoss", "SAC/entropy_loss", "SAC/alpha_loss")
+NETS = ("critic", "critic_target", "policy")
+
+
+class Box:
+    """The three attributes of gym.spaces.Box the agent reads."""
+
+    def __init__(self, low, high, shape):
+        self.low = np.full(shape, low, dtype=np.float32)
+        self.high = np.full(shape, high, dtype=np.float32)
+        self.shape = shape
+
+
+def spaces(obs_dim=OBS, act_dim=ACT, low=-1.0, high=1.0):
+    return Box(-np.inf, np.inf, (1, obs_dim)), Box(low, high, (1, act_dim))
+
+
+def config(hidden=256, auto=False, interval=1, cuda=False, **over):
+    cfg = dict(gamma=0.99, tau=0.005, alpha=0.2, policy="Gaussian", target_update_interval=interval,
+               automatic_entropy_tuning=auto, cuda=cuda, hidden_size=hidden, lr=3e-4)
+    cfg.update(over)
+    return Namespace(**cfg)
+
+
+def smooth_fields(B, N, seed):
+    """[B, 1, 1, N] fp32: per sample a sum of four sines, amplitudes uniform(-1, 1), phases uniform(0, 6)."""
+    rs = np.random.RandomState(seed)
+    x = np.linspace(0, 2 * np.pi, N, endpoint=False)
+    rows = [sum(rs.uniform(-1, 1) * np.sin((k + 1) * x + rs.uniform(0, 6)) for k in range(4)) for _ in range(B)]
+    return np.stack(rows).astype(np.float32).reshape(B, 1, 1, N)
+
+
+def make_batch(B, seed, obs_dim=OBS, act_dim=ACT, dtype=torch.float32):
+    """The 7-tuple of ``SAC.update``: obs, actions, nxtobs [B, 1, 1, n]; rewards in (-1, 0), flags and steps [B, 1]."""
+    rs = np.random.RandomState(seed + 1000)
+    obs = torch.from_numpy(smooth_fields(B, obs_dim, seed)).to(dtype)
+    nxt = torch.from_numpy(smooth_fields(B, obs_dim, seed + 1)).to(dtype)
+    act = torch.from_numpy(rs.uniform(-1, 1, (B, 1, 1, act_dim)).astype(np.float32)).to(dtype)
+    rew = torch.from_numpy(-rs.uniform(0.01, 0.99, (B, 1)).astype(np.float32)).to(dtype)
+    flags = torch.zeros((B, 1), dtype=torch.bool)
+    steps = torch.from_numpy(rs.randint(0, 100, (B, 1)))
+    return obs, act, nxt, rew, flags, flags.clone(), steps
+
+
+def noise_pair(B, seed, act_dim=ACT, dtype=torch.float32):
+    """Two stored standard-normal tensors [B, 1, act_dim] (next-state draw, current-state draw)."""
+    rs = np.random.RandomState(seed + 2000)
+    return tuple(torch.from_numpy(rs.standard_normal((B, 1, act_dim)).astype(np.float32)).to(dtype) for _ in range(2))
+
+
+def snapshot(out, tag, k, agent, whole):
+    for net in NETS:
+        for name, p in getattr(agent, net).state_dict().items():
+            v = p.detach().cpu().numpy()
+            if whole:
+                out[f"{tag}_u{k}_{net}.{name}"] = v.copy()
+            else:
+                out[f"{tag}_u{k}_{net}.{name}_sum"] = np.asarray(v.astype(np.float64).sum())
+                out[f"{tag}_u{k}_{net}.{name}_head"] = v.reshape(-1)[:8].copy()
+    if getattr(agent, "automatic_entropy_tuning", False):
+        out[f"{tag}_u{k}_log_alpha"] = agent.log_alpha.detach().cpu().numpy().copy()
+
+
+def scenario(tag, make_agent, logs):
+    """Seed, build the agent, act, update ``updates`` times on the case's batch, act again.  ``make_agent(obs_space,
+    act_space, cfg)`` builds it; ``logs`` is the list the agent's logger appends (dict, commit) to.  Returns {key: array}."""
+    hidden, B, updates, auto, interval, seed = CASES[tag]
+    whole = hidden <= 32
+    out = {}
+    batch = make_batch(B, seed)
+    act_obs = smooth_fields(N_ACT_OBS, OBS, seed + 7)[:, 0]
+    torch.manual_seed(seed)
+    agent = make_agent(*spaces(), config(hidden, auto, interval))
+    for name, t in zip(("obs", "actions", "nxtobs", "rewards", "terminated", "truncated", "steps"), batch):
+        out[f"{tag}_batch_{name}"] = t.numpy().copy()
+    out[f"{tag}_act_obs"] = act_obs.copy()
+    snapshot(out, tag, 0, agent, whole)
+    out[f"{tag}_action_before"] = np.asarray(agent.select_action(act_obs)).copy()
+    for k in range(1, updates + 1):
+        del logs[:]
+        agent.update(batch)
+        merged = {}
+        for entry, _commit in logs:
+            merged.update(entry)
+        out[f"{tag}_u{k}_logged"] = np.asarray([float(merged[key]) for key in LOG_KEYS], dtype=np.float64)
+        snapshot(out, tag, k, agent, whole)
+    out[f"{tag}_action_after"] = np.asarray(agent.select_action(act_obs)).copy()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# helpers of the GPU tests
+# ---------------------------------------------------------------------------------------------------------------------
+class stored_noise:
+    """``with stored_noise([n1, n2, ...]):`` -- every standard-normal draw of the agent (torch spelling and fused path
+    alike) takes the next stored tensor instead, cast to the dtype and device asked for."""
+
+    def __init__(self, tensors):
+        self.queue = list(tensors)
+
+    def _draw(self, like):
+        t = self.queue.pop(0)
+        assert t.shape == like.shape, (t.shape, like.shape)
+        return t.to(device=like.device, dtype=like.dtype)
+
+    def __enter__(self):
+        from pdecontrol.sac import policies, sac
+        self.saved = (policies.draw_noise, sac.draw_noise)
+        policies.draw_noise = sac.draw_noise = self._draw
+        return self
+
+    def __exit__(self, *exc):
+        from pdecontrol.sac import policies, sac
+        policies.draw_noise, sac.draw_noise = self.saved
+
+
+def build(hidden=256, auto=False, interval=1, obs_dim=OBS, act_dim=ACT, seed=0, device="cpu", logs=None, low=-1.0, high=1.0, **over):
+    """A freshly seeded agent of this repository's class."""
+    from pdecontrol.sac.sac import SAC
+    torch.manual_seed(seed)
+    logger = None if logs is None else (lambda entry, commit=True: logs.append((dict(entry), commit)))
+    cfg = config(hidden, auto, interval, device=device, **over)
+    return SAC(*spaces(obs_dim, act_dim, low, high), cfg, logger=logger)
+
+
+def twin(agent, dtype, logs=None):
+    """A CPU agent in ``dtype`` with the parameters, target and entropy coefficient of ``agent`` (optimizers fresh)."""
+    from pdecontrol.sac.sac import SAC
+    pol = agent.policy
+    hidden = pol.linear1.out_features
+    auto = bool(agent.automatic_entropy_tuning)
+    cfg = config(hidden, auto, agent.target_update_interval, gamma=agent.gamma, tau=agent.tau,
+                 alpha=float(agent.alpha) if not isinstance(agent.alpha, torch.Tensor) else float(agent.alpha.item()),
+                 lr=agent.critic_optim.param_groups[0]["lr"])
+    logger = None if logs is None else (lambda entry, commit=True: logs.append((dict(entry), commit)))
+    out = SAC(*spaces(pol.linear1.in_features, pol.mean_linear.out_features), cfg, logger=logger)
+    for net in NETS:
+        getattr(out, net).load_state_dict({k: v.detach().cpu() for k, v in getattr(agent, net).state_dict().items()})
+        getattr(out, net).to(dtype)
+    out.policy.action_scale = pol.action_scale.detach().cpu().to(dtype)
+    out.policy.action_bias = pol.action_bias.detach().cpu().to(dtype)
+    if auto:
+        with torch.no_grad():
+            out.log_alpha.copy_(agent.log_alpha.detach().cpu())
+        out.log_alpha.data = out.log_alpha.data.to(dtype)
+    out.updates = agent.updates
+    return out
+
+
+def cast_batch(batch, dtype=None, device=None):
+    return tuple(t.to(device=device, dtype=dtype if t.is_floating_point() else None) for t in batch)
+
+
+def terms(agent, batch, noises):
+    """Losses and gradients of one update of ``agent`` at its current state, in its own dtype on its own device, with the
+    policy gradient taken against the not-yet-updated critic (what ``sac_grads`` computes)."""
+    obs, actions, nxtobs, rewards, terminated, _ = agent._prepare(batch)
+    n_next, n_cur = (n.to(device=obs.device, dtype=obs.dtype) for n in noises)
+    with torch.no_grad():
+        a2, lp2, _ = agent.policy.sample(nxtobs, noise=n_next)
+        q1t, q2t = agent.critic_target(nxtobs, a2)
+        y = rewards + (1.0 - terminated.to(obs.dtype)) * agent.gamma * (torch.min(q1t, q2t) - agent.alpha * lp2)
+    q1, q2 = agent.critic(obs, actions)
+    qloss = torch.nn.functional.mse_loss(q1, y) + torch.nn.functional.mse_loss(q2, y)
+    names_c = [n for n, _ in agent.critic.named_parameters()]
+    gc = dict(zip(names_c, torch.autograd.grad(qloss, list(agent.critic.parameters()))))
+    pi, lp, mean = agent.policy.sample(obs, noise=n_cur)
+    q1p, q2p = agent.critic(obs, pi)
+    ploss = (agent.alpha * lp - torch.min(q1p, q2p)).mean()
+    names_p = [n for n, _ in agent.policy.named_parameters()]
+    gp = dict(zip(names_p, torch.autograd.grad(ploss, list(agent.policy.parameters()))))
+    gla = -(lp + agent.target_entropy).mean().detach() if agent.automatic_entropy_tuning else None
+    gap = (q1p - q2p).detach().abs().min() / torch.cat([q1p, q2p]).detach().abs().max()
+    return dict(critic=gc, policy=gp, log_alpha=gla, qloss=qloss.detach(), ploss=ploss.detach(), q_gap=float(gap),
+                action=pi.detach(), logp=lp.detach(), mean=mean.detach())
+
+
+def tensor_dev(got, ref):
+    """max over tensors of max|got - ref| / max|ref|"""
+    worst = 0.0
+    for k, r in ref.items():
+        r = r.detach().cpu().double()
+        worst = max(worst, float((got[k].detach().cpu().double() - r).abs().max() / r.abs().max()))
+    return worst
+
+
+def full_state(agent):
+    """Every parameter, Adam moment, step count and the entropy state, as CPU tensors."""
+    out = {}
+    for net in NETS:
+        for k, v in getattr(agent, net).state_dict().items():
+            out[f"{net}.{k}"] = v.detach().cpu().clone()
+    opts = [("critic_optim", agent.critic_optim), ("policy_optim", agent.policy_optim)]
+    if agent.automatic_entropy_tuning:
+        opts.append(("alpha_optim", agent.alpha_optim))
+        out["log_alpha"] = agent.log_alpha.detach().cpu().clone()
+    for name, opt in opts:
+        for i, p in enumerate(opt.param_groups[0]["params"]):
+            for k, v in opt.state.get(p, {}).items():
+                out[f"{name}.{i}.{k}"] = torch.as_tensor(v).detach().cpu().clone()
+    out["alpha"] = torch.as_tensor(agent.alpha).detach().cpu().clone().reshape(-1).float()
+    out["updates"] = torch.tensor(agent.updates)
+    return out

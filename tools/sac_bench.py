@@ -1,0 +1,189 @@
+#!/usr/bin/env python3
+"""Timings of the SAC agent (pdecontrol.sac.sac.SAC; hidden 256, (1, 64) observations, (1, 4) actions) on an MI355X.
+Record only.
+
+  update   one ``update`` at B = 256 on three paths of the same process, alternated over ``--rounds`` rounds: the torch
+           spelling (``ops.fused(False)``: the reference's operations on PyTorch-ROCm kernels), the fused kernels launched
+           eagerly (``update``: five launches of csrc/sac.hip plus the two noise draws), and ``update_many`` over 50 batches
+           (one captured hipGraph replayed per batch).  No logger is attached, so no path fetches statistics.
+  act      ``act`` at B = 10 and 100: one launch against the torch spelling.
+
+Every path is warmed up; a window is at least ``--min-seconds`` (0.3) of work between two device synchronisations; ms per
+call = window / calls.
+
+Other modes:
+  --profile-run        twenty fused updates and twenty ``act`` calls and nothing else: the program to put behind
+                       ``rocprofv3 --kernel-trace --stats`` (in a run of its own)
+  --parity FILE.jsonl  collect the records tests/test_sac_gpu.py appends (observed deviations) into ``--out``
+
+Usage (repo root, on an MI355X):  python tools/sac_bench.py --out profiles/sac_bench.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from argparse import Namespace
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "model-based-pde-control_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+B, N, A, MANY = 256, 64, 4, 50
+
+
+def box(low, high, n):
+    return SimpleNamespace(low=np.full((1, n), low, np.float32), high=np.full((1, n), high, np.float32), shape=(1, n))
+
+
+def agent_on(dev, auto=True):
+    from pdecontrol.sac.sac import SAC
+    cfg = Namespace(gamma=0.99, tau=0.005, alpha=0.2, policy="Gaussian", target_update_interval=1,
+                    automatic_entropy_tuning=auto, cuda=False, device=dev, hidden_size=256, lr=3e-4)
+    torch.manual_seed(0)
+    return SAC(box(-np.inf, np.inf, N), box(-1.0, 1.0, A), cfg, logger=None)
+
+
+def batch_on(dev, b, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.linspace(0, 2 * np.pi, N)
+    field = lambda: sum(torch.rand(b, 1, 1, 1, generator=g) * torch.sin((k + 1) * x + 6 * torch.rand(b, 1, 1, 1, generator=g))
+                        for k in range(4))
+    flags = torch.zeros(b, 1, dtype=torch.bool)
+    batch = (field(), 2 * torch.rand(b, 1, 1, A, generator=g) - 1, field(), -torch.rand(b, 1, generator=g), flags, flags,
+             flags.long())
+    return tuple(t.to(dev) for t in batch)
+
+
+def window_ms(call, min_seconds, per_call=1):
+    """ms per unit of work over one window of at least ``min_seconds`` between two device synchronisations."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    call()
+    torch.cuda.synchronize()
+    n = max(2, int(1.3 * min_seconds / max(time.perf_counter() - t0, 1e-6)))
+    while True:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            call()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if dt >= min_seconds:
+            return 1e3 * dt / (n * per_call), n * per_call
+        n *= 2
+
+
+def bench(paths, rounds, min_seconds):
+    """paths: {name: (call, units of work per call)}; alternated, medians reported."""
+    ms = {k: [] for k in paths}
+    for call, _ in paths.values():
+        for _ in range(3):
+            call()
+    for _ in range(rounds):
+        for name, (call, per) in paths.items():
+            t, _n = window_ms(call, min_seconds, per)
+            ms[name].append(round(t, 4))
+    return {k: {"ms": v, "ms_median": round(float(np.median(v)), 4)} for k, v in ms.items()}
+
+
+def collect_parity(path, out):
+    rows = [json.loads(line) for line in open(path) if line.strip()]
+    worst = {}
+
+    def flat(prefix, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                yield from flat(f"{prefix}.{k}" if prefix else k, x)
+        elif isinstance(v, list):
+            for x in v:
+                yield from flat(prefix, x)
+        elif isinstance(v, (int, float)):
+            yield prefix, float(v)
+    for r in rows:
+        for key, val in flat("", {k: v for k, v in r.items() if k not in ("case", "tol", "cap", "atol_scale", "q_gap", "first", "last")}):
+            group = r["case"].split("-")[0] + ":" + key
+            if val >= worst.get(group, {"max": -1.0})["max"]:
+                worst[group] = {"max": val, "case": r["case"]}
+    rec = {"what": "deviations tests/test_sac_gpu.py observed on an MI355X: forward outputs and gradients against the CPU "
+                   "module in fp64 relative to each tensor's maximum (next to the fp32 torch spelling on the CPU against the "
+                   "same fp64), shares of elements whose first Adam step differs from the fp64 step by more than 0.1 lr, "
+                   "relative loss differences", "worst": worst, "cases": rows}
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(worst))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--min-seconds", type=float, default=0.3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--profile-run", action="store_true")
+    ap.add_argument("--parity", default=None)
+    args = ap.parse_args()
+    if args.parity:
+        return collect_parity(args.parity, args.out or os.path.join(ROOT, "profiles", "sac_parity_observed.json"))
+    assert torch.cuda.is_available(), "needs a GPU"
+    dev = torch.device("cuda", 0)
+    from pdecontrol.surrogates import ops
+    batch = batch_on(dev, B, 1)
+    if args.profile_run:
+        agent = agent_on(dev)
+        obs = batch[0][:100].squeeze(1)
+        for _ in range(20):
+            agent.update(batch)
+            agent.act(obs)
+        torch.cuda.synchronize()
+        return
+    rec = {"what": "SAC agent, hidden 256, 64 observations, 4 actions, automatic entropy tuning on: ms per update at B = 256 "
+                   "(torch spelling on PyTorch-ROCm kernels / fused kernels launched eagerly / update_many = one captured "
+                   "hipGraph replayed per batch) and ms per act call; paths alternated, medians over the rounds",
+           "B": B, "rounds": args.rounds, "min_seconds_per_window": args.min_seconds, "device": torch.cuda.get_device_name(dev)}
+    agents = {name: agent_on(dev) for name in ("torch", "fused", "graph")}
+    many = [batch] * MANY
+
+    def torch_update():
+        with ops.fused(False):
+            agents["torch"].update(batch)
+    upd = bench({"torch": (torch_update, 1), "fused_eager": (lambda: agents["fused"].update(batch), 1),
+                 "fused_update_many": (lambda: agents["graph"].update_many(many), MANY)}, args.rounds, args.min_seconds)
+    upd["speedup_eager_vs_torch"] = round(upd["torch"]["ms_median"] / upd["fused_eager"]["ms_median"], 2)
+    upd["speedup_update_many_vs_torch"] = round(upd["torch"]["ms_median"] / upd["fused_update_many"]["ms_median"], 2)
+    rec["update"] = upd
+    rec["act"] = {}
+    for b in (10, 100):
+        obs = batch[0][:b].squeeze(1)
+
+        def torch_act():
+            with ops.fused(False):
+                agents["torch"].act(obs)
+        r = bench({"torch": (torch_act, 1), "fused": (lambda: agents["fused"].act(obs), 1)}, args.rounds, args.min_seconds)
+        r["speedup"] = round(r["torch"]["ms_median"] / r["fused"]["ms_median"], 2)
+        rec["act"][f"B{b}"] = r
+    # device time of the captured update alone (events around replays, no input copies, no noise draws)
+    g = agents["graph"]._fused.graph_for((B, (1, A)))
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    agents["graph"]._fused.sync_in()
+    start.record()
+    for _ in range(200):
+        g.graph.replay()
+    end.record()
+    torch.cuda.synchronize()
+    rec["update"]["graph_replay_device_ms"] = round(start.elapsed_time(end) / 200, 4)
+    line = json.dumps(rec)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
