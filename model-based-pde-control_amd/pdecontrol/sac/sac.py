@@ -228,19 +228,35 @@ class SAC(object):
             return
         B = first[0].shape[0]
         graph = fused.graph_for((B, tuple(first[1].shape[1:])))
-        history = torch.zeros((len(batches), 8), dtype=torch.float32, device=self.device) if self.logger is not None else None
+        history = self._stats_history(len(batches))
         for i, batch in enumerate(batches):
             obs, actions, nxtobs, rewards, terminated, _ = first if i == 0 else self._prepare(batch)
             assert obs.shape[0] == B and tuple(actions.shape[1:]) == tuple(graph.noise_cur.shape[1:]), "batches must share a shape"
-            fused.sync_in()
-            for dst, src in zip(graph.inputs[:5], (obs, actions, nxtobs, rewards, terminated)):
-                dst.copy_(src.reshape(dst.shape), non_blocking=True)
-            graph.noise_next.normal_()
-            graph.noise_cur.normal_()
-            graph.graph.replay()
-            fused.sync_out()
-            if history is not None:
-                history[i].copy_(fused.stats)
+            srcs = (obs, actions, nxtobs, rewards, terminated)
+            fill = lambda: [dst.copy_(src.reshape(dst.shape), non_blocking=True) for dst, src in zip(graph.inputs[:5], srcs)]
+            self._replay_update(fused, graph, fill, None if history is None else history[i])
+        self._log_history(history)
+
+    def _stats_history(self, n):
+        """Device rows for the statistics of ``n`` captured updates, or None without a logger (nothing is fetched then)."""
+        return torch.zeros((n, 8), dtype=torch.float32, device=self.device) if self.logger is not None else None
+
+    @staticmethod
+    def _replay_update(fused, graph, fill, stats_row=None):
+        """One update on the captured graph.  ``fill()`` enqueues whatever writes the graph's five static batch buffers
+        (``update_many``: five copies; the policy-update phase: one ``rp_gather`` launch); the noise is drawn outside the
+        graph with the calls of ``update``, and the statistics are kept in ``stats_row`` on the device."""
+        fused.sync_in()
+        fill()
+        graph.noise_next.normal_()
+        graph.noise_cur.normal_()
+        graph.graph.replay()
+        fused.sync_out()
+        if stats_row is not None:
+            stats_row.copy_(fused.stats)
+
+    def _log_history(self, history):
+        """The one fetch at the end of a run of captured updates: the terminated check, then the reference's log calls."""
         if history is not None:
             rows = history.tolist()
             self._check_terminated(sum(r[5] for r in rows))
