@@ -11,22 +11,12 @@
 // barrier, no index arithmetic.  HBM is touched once on entry and once on exit; the kernel is VALU-issue bound.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../include/burgers_hip.h"
+#include "capi_error.h"
 
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 struct Args {
     float* u;
@@ -243,11 +233,11 @@ __global__ void bg_residual_kernel(const float* __restrict__ u, const float* __r
 }
 
 template <int P>
-hipError_t launch(const Args& a, hipStream_t st) {
+int launch(const Args& a, hipStream_t st) {
     const int waves_per_block = 4;
     const int grid = (a.n_envs + waves_per_block - 1) / waves_per_block;
     hipLaunchKernelGGL(bg_step_kernel<P>, dim3(grid), dim3(64 * waves_per_block), 0, st, a);
-    return hipGetLastError();
+    return launch_status(-2, "bg_step");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -394,12 +384,12 @@ __global__ void __launch_bounds__(256) bg_phyloss_bwd_kernel(const PhyArgs a) {
 }
 
 template <int P>
-hipError_t launch_phyloss(const PhyArgs& a, bool backward, hipStream_t st) {
+int launch_phyloss(const char* who, const PhyArgs& a, bool backward, hipStream_t st) {
     const int waves_per_block = 4;
     const int grid = (a.B * a.T + waves_per_block - 1) / waves_per_block;
     if (backward) hipLaunchKernelGGL(bg_phyloss_bwd_kernel<P>, dim3(grid), dim3(64 * waves_per_block), 0, st, a);
     else hipLaunchKernelGGL(bg_phyloss_fwd_kernel<P>, dim3(grid), dim3(64 * waves_per_block), 0, st, a);
-    return hipGetLastError();
+    return launch_status(-2, who);
 }
 
 // shared host-side validation and dispatch of the two loss entry points
@@ -413,17 +403,14 @@ int phyloss_launch(const char* who, PhyArgs& a, bool backward, void* stream, lon
         return fail(-3, "%s: the sub-step state store holds %ld floats, B (T-1) (substeps-1) N = %ld are needed", who,
                     a.states ? states_len : 0L, need);
     set_coefficients(a.c, dx, dt, nu);
-    hipError_t e;
     switch (a.N / 64) {
-        case 1: e = launch_phyloss<1>(a, backward, (hipStream_t)stream); break;
-        case 2: e = launch_phyloss<2>(a, backward, (hipStream_t)stream); break;
-        case 4: e = launch_phyloss<4>(a, backward, (hipStream_t)stream); break;
-        case 8: e = launch_phyloss<8>(a, backward, (hipStream_t)stream); break;
-        case 16: e = launch_phyloss<16>(a, backward, (hipStream_t)stream); break;
+        case 1: return launch_phyloss<1>(who, a, backward, (hipStream_t)stream);
+        case 2: return launch_phyloss<2>(who, a, backward, (hipStream_t)stream);
+        case 4: return launch_phyloss<4>(who, a, backward, (hipStream_t)stream);
+        case 8: return launch_phyloss<8>(who, a, backward, (hipStream_t)stream);
+        case 16: return launch_phyloss<16>(who, a, backward, (hipStream_t)stream);
         default: return fail(-4, "%s: N = %d: supported sizes are 64, 128, 256, 512, 1024", who, a.N);
     }
-    if (e != hipSuccess) return fail(-2, "%s launch failed: %s", who, hipGetErrorString(e));
-    return 0;
 }
 
 }  // namespace
@@ -442,17 +429,14 @@ int bg_step(void* stream, float* u, const float* actions, const float* F, int n_
     a.u = u; a.actions = actions; a.F = F; a.obs = obs; a.ssq_sum = ssq_sum; a.status = status;
     a.n_act = n_act; a.n_envs = n_envs; a.N = N; a.n_substeps = n_substeps;
     set_coefficients(a, dx, dt, nu);
-    hipError_t e;
     switch (N / 64) {
-        case 1: e = launch<1>(a, (hipStream_t)stream); break;
-        case 2: e = launch<2>(a, (hipStream_t)stream); break;
-        case 4: e = launch<4>(a, (hipStream_t)stream); break;
-        case 8: e = launch<8>(a, (hipStream_t)stream); break;
-        case 16: e = launch<16>(a, (hipStream_t)stream); break;
+        case 1: return launch<1>(a, (hipStream_t)stream);
+        case 2: return launch<2>(a, (hipStream_t)stream);
+        case 4: return launch<4>(a, (hipStream_t)stream);
+        case 8: return launch<8>(a, (hipStream_t)stream);
+        case 16: return launch<16>(a, (hipStream_t)stream);
         default: return fail(-4, "bg_step: N = %d: supported sizes are 64, 128, 256, 512, 1024", N);
     }
-    if (e != hipSuccess) return fail(-2, "bg_step launch failed: %s", hipGetErrorString(e));
-    return 0;
 }
 
 int bg_residual(void* stream, const float* u, const float* phi, int n_rows, int N, float dx, float nu, float* out) {
@@ -461,9 +445,7 @@ int bg_residual(void* stream, const float* u, const float* phi, int n_rows, int 
     const size_t total = (size_t)n_rows * N;
     hipLaunchKernelGGL(bg_residual_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u, phi, n_rows, N,
                        0.5f / dx, s * (-5.0f / 2.0f), s * (4.0f / 3.0f), s * (-1.0f / 12.0f), out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, "bg_residual launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status(-2, "bg_residual");
 }
 
 int bg_phyloss_forward(void* stream, const float* augmented, int B, int T, int N, float dx, float dt, float nu, int substeps,

@@ -23,10 +23,10 @@
 // fp32 throughout with explicit fmaf.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../include/delay_hip.h"
+#include "capi_error.h"
 
 namespace {
 
@@ -42,15 +42,6 @@ constexpr int MIN = DELAY * SLOT;           // 288
 constexpr int H1 = 96, H2 = 64, H3 = 64;
 constexpr int ACT_NONE = 0, ACT_ELU = 1, ACT_TANH = 2;
 constexpr float LN_EPS = 1e-5f;
-
-thread_local char g_err[256] = "";
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 // ---- the flat parameter vector (named_parameters() order of the factory's module tree) ------------------------------
 struct Blk {                                 // one encoder ResidualBlock: offsets; ln < 0 when it has no LayerNorm
@@ -586,12 +577,6 @@ __global__ void __launch_bounds__(TPB) dly_reduce_kernel(const float* __restrict
     out[p] = s;
 }
 
-int launched(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, "%s launch failed: %s", what, hipGetErrorString(e));
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -620,7 +605,7 @@ int dly_forward(void* stream, const float* params, int B, int S, int K, const fl
     const int su = S < K ? S : K;
     hipLaunchKernelGGL(dly_fwd_kernel, dim3(B), dim3(TPB), 0, (hipStream_t)stream, params, S, K, su, states, actions,
                        ctx_s_in, ctx_a_in, delta, mul, add, outputs, deltas, inlatents, outlatents, ctx_s_out, ctx_a_out);
-    return launched("dly_forward");
+    return launch_status(-2, "dly_forward");
 }
 
 int dly_backward(void* stream, const float* params, int B, int S, int K, const float* states, const float* actions,
@@ -637,11 +622,11 @@ int dly_backward(void* stream, const float* params, int B, int S, int K, const f
     hipLaunchKernelGGL(dly_bwd_kernel, dim3(B), dim3(TPB), 0, (hipStream_t)stream, params, S, K, su, states, actions,
                        ctx_s_in, ctx_a_in, inlatents, outlatents, delta, mul, d_outputs, d_deltas, d_inlatents,
                        d_outlatents, d_ctx_s_out, d_ctx_a_out, d_states, d_actions, d_ctx_s_in, d_ctx_a_in, work);
-    int rc = launched("dly_backward");
+    int rc = launch_status(-2, "dly_backward");
     if (rc) return rc;
     hipLaunchKernelGGL(dly_reduce_kernel, dim3((NPARAM + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, work, B,
                        d_params);
-    return launched("dly_backward (reduce)");
+    return launch_status(-2, "dly_backward (reduce)");
 }
 
 const char* dly_last_error(void) { return g_err; }

@@ -23,13 +23,13 @@
 // fp32 throughout, v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <map>
 #include <mutex>
 #include <utility>
 
 #include "../../include/spectral_hip.h"
+#include "capi_error.h"
 
 namespace {
 
@@ -42,15 +42,6 @@ constexpr int KP = K2 + 4;   // padded row of a spectrum / of a 32 x 32 weight m
 constexpr int KS = 2;        // K-split of the K = N contractions (8 waves: 4 output tiles x 2 halves of K)
 constexpr int TPB = 512;
 constexpr int LAYERS = 4;
-
-thread_local char g_err[256] = "";
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 struct Weights {            // device pointers, fp32
     const float* lift_w;    // [32][2]
@@ -754,9 +745,7 @@ int launch(K kernel, const char* who, void* stream, int pairs, int n, const A& a
     if (lds > 160 * 1024) return fail(-4, "%s: needs %zu B of LDS", who, lds);
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kernel, dim3(pairs), dim3(TPB), lds, (hipStream_t)stream, args);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, "%s launch failed: %s", who, hipGetErrorString(e));
-    return 0;
+    return launch_status(-2, who);
 }
 
 // twiddle matrix of (current device, N): created on first use (one tiny kernel + one synchronisation), then shared by every
@@ -886,9 +875,7 @@ int fno_backward(void* stream, const fno_weights* w, int width, int modes, int l
 int fno_reduce_rows(void* stream, const float* rows, int pairs, float* out) {
     if (!rows || !out || pairs <= 0) return fail(-1, "fno_reduce_rows: bad argument");
     hipLaunchKernelGGL(fno_reduce_rows_kernel, dim3((ROW + 63) / 64), dim3(512), 0, (hipStream_t)stream, rows, pairs, ROW, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, "fno_reduce_rows launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status(-2, "fno_reduce_rows");
 }
 
 int fno_spec_wgrad(void* stream, const float* xspec, const float* gspec, int pairs, float* const* dwr, float* const* dwi) {
@@ -900,9 +887,7 @@ int fno_spec_wgrad(void* stream, const float* xspec, const float* gspec, int pai
         dst.dwi[l] = dwi[l];
     }
     hipLaunchKernelGGL(fno_spec_wgrad_kernel, dim3(LAYERS * M), dim3(256 * WG_KS), 0, (hipStream_t)stream, xspec, gspec, pairs, dst);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, "fno_spec_wgrad launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status(-2, "fno_spec_wgrad");
 }
 
 const char* fno_last_error(void) { return g_err; }

@@ -6,27 +6,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 
 #include "../../include/kspde.h"
+#include "capi_error.h"
 #include "ks_cpu.h"
 #include "ks_internal.h"
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 #define KS_HIP(call)                                                                        \
     do {                                                                                    \

@@ -13,24 +13,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
 #include "../../include/replay_hip.h"
+#include "capi_error.h"
 
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -203,8 +192,7 @@ int rp_gather(void* stream, int nsrc, const rp_source* srcs, int B, const long* 
     }
     g.total = first;
     hipLaunchKernelGGL(rp_gather_kernel, dim3((B + WAVES - 1) / WAVES), dim3(NT), 0, static_cast<hipStream_t>(stream), g);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(-20, "rp_gather launch failed: %s", hipGetErrorString(e));
+    return launch_status(-20, "rp_gather");
 }
 
 const char* rp_last_error(void) { return g_err; }

@@ -16,24 +16,13 @@
 // No float atomics anywhere; no kernel stores through the scalar unit.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
 #include "../../include/sac_hip.h"
+#include "capi_error.h"
 
 namespace {
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -652,8 +641,7 @@ int launch(K kernel, const char* name, int grid, size_t lds, hipStream_t stream,
 {
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), lds, stream, args);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(-20, "%s launch failed: %s", name, hipGetErrorString(e));
+    return launch_status(-20, name);
 }
 
 bool any_null(float* const* p, int n)

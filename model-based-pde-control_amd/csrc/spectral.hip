@@ -13,24 +13,15 @@
 // arithmetic; larger geometries gather from the N-entry cosine table instead (DENSE = false).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../include/spectral_hip.h"
+#include "capi_error.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TPB = 256;
-
-thread_local char g_err[256] = "";
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 struct Args {
     const float* in;    // [B, Cin_, N]   (x, or dy)
@@ -334,9 +325,7 @@ int launch(void* stream, const Args& a, int b, const char* who) {
     };
     if (plan.dense) go(spec_conv_kernel<true>);
     else go(spec_conv_kernel<false>);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, "%s launch failed: %s", who, hipGetErrorString(e));
-    return 0;
+    return launch_status(-2, who);
 }
 
 int check_geometry(const char* who, int b, int cin, int cout, int n, int modes) {

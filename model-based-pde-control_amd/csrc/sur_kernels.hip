@@ -25,11 +25,11 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 
 #include "../../include/surrogate_hip.h"
+#include "capi_error.h"
 
 // Diagnostic build only (-DSUR_STAMP): shader-clock stamps per phase for workgroup 0 of each launch,
 // accumulated in a __device__ buffer nothing else reads (guide section 7, In-kernel stamps).
@@ -53,16 +53,6 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr float LN_EPS = 1e-5f;
-
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_rot(float v) {
@@ -3099,9 +3089,7 @@ adam_all_kernel(const sur_encoder_params e0, const sur_adam a0, int n0, const su
 template <typename F>
 int launch_checked(F&& f, const char* what) {
     f();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, "%s launch failed: %s", what, hipGetErrorString(e));
-    return 0;
+    return launch_status(-2, what);
 }
 
 constexpr size_t LDS_LIMIT = 160 * 1024;

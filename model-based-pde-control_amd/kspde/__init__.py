@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+import hipbind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "..", "lib", "libkspde.so")
 
@@ -66,28 +68,12 @@ def load():
     """dlopen libkspde.so and type every exported symbol.  Raises if it is missing."""
     global _lib
     if _lib is None:
-        # torch ships its own HIP runtime (torch/lib/libamdhip64.so, SONAME libamdhip64.so.7).  Import it
-        # FIRST so that libkspde's NEEDED libamdhip64.so.7 binds to that already-loaded copy: two HIP
-        # runtimes in one process cannot both own the GPU ("No HIP GPUs are available").
-        import torch  # noqa: F401
-        path = os.path.abspath(os.environ.get("KSPDE_LIB") or LIB_PATH)
-        if not os.path.exists(path):
-            raise KSError(
-                f"{path} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; "
-                f"g.build()' or make -C model-based-pde-control_amd/csrc). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, res, args in SYMBOLS:
-            fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _lib = lib
+        _lib = hipbind.open_library(os.path.abspath(os.environ.get("KSPDE_LIB") or LIB_PATH), SYMBOLS, KSError,
+                                    "There is no CPU fallback.")
     return _lib
 
 
-def _check(rc):
-    if rc != 0:
-        msg = load().ks_last_error().decode(errors="replace")
-        raise KSError(f"libkspde error {rc}: {msg}")
+_check = hipbind.checker(KSError, "libkspde", "ks_last_error", lambda: load())
 
 
 def _ptr(a):

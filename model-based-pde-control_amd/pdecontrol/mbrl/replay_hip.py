@@ -5,6 +5,8 @@ A missing library raises: the kernel tier of pdecontrol/mbrl/policy_phase.py has
 import ctypes
 import os
 
+import hipbind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "lib", "libreplay_hip.so"))
 
@@ -35,15 +37,7 @@ class ReplayHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ReplayHipError(f"{LIB_PATH} not found: build it (python -c 'import __graft_entry__ as g; g.build()').  "
-                                 f"The fused batch gather has no fallback.")
-        import torch  # noqa: F401  (its bundled HIP runtime must be the one the library binds to)
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS:
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = lib
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, ReplayHipError, "The fused batch gather has no fallback.")
     return _lib
 
 

@@ -17,6 +17,7 @@ import os
 
 import torch
 
+import hipbind
 from pdecontrol.surrogates import ops
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,14 +63,7 @@ class SacHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise SacHipError(f"{LIB_PATH} not found: build it (python -c 'import __graft_entry__ as g; g.build()').  "
-                              f"The fused SAC path has no fallback.")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS:
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = lib
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, SacHipError, "The fused SAC path has no fallback.")
     return _lib
 
 
@@ -77,17 +71,8 @@ def last_error():
     return load().sac_last_error().decode(errors="replace")
 
 
-def _check(rc):
-    if rc != 0:
-        raise SacHipError(f"libsac_hip error {rc}: {last_error()}")
-
-
-def _stream():
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+_check = hipbind.checker(SacHipError, "libsac_hip", "sac_last_error", lambda: load())
+_stream, _ptr = hipbind.stream, hipbind.ptr
 
 
 def _adam_reason(opt, what):

@@ -19,6 +19,8 @@ import os
 
 import torch
 
+import hipbind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "lib", "libdelay_hip.so"))
 
@@ -43,28 +45,12 @@ class DelayHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise DelayHipError(f"{LIB_PATH} not found: build it (python -c 'import __graft_entry__ as g; g.build()').  "
-                                f"The fused delay surrogate path has no fallback.")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS:
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = lib
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, DelayHipError, "The fused delay surrogate path has no fallback.")
     return _lib
 
 
-def _check(rc):
-    if rc != 0:
-        raise DelayHipError(f"libdelay_hip error {rc}: {load().dly_last_error().decode(errors='replace')}")
-
-
-def _stream():
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+_check = hipbind.checker(DelayHipError, "libdelay_hip", "dly_last_error", lambda: load())
+_stream, _ptr = hipbind.stream, hipbind.ptr
 
 
 # ---------------------------------------------------------------------------------------------------------------------

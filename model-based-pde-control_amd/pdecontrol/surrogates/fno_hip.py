@@ -20,6 +20,7 @@ import ctypes
 
 import torch
 
+import hipbind
 from pdecontrol.surrogates import spectral
 
 _p, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
@@ -50,25 +51,12 @@ class FnoHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        lib = spectral.load()           # same shared library; raises when it has not been built
-        for name, res, args in SYMBOLS:
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = lib
+        _lib = hipbind.type_symbols(spectral.load(), SYMBOLS)   # same shared library; raises when it has not been built
     return _lib
 
 
-def _check(rc):
-    if rc != 0:
-        raise FnoHipError(f"libspectral_hip (fno) error {rc}: {load().fno_last_error().decode(errors='replace')}")
-
-
-def _stream():
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+_check = hipbind.checker(FnoHipError, "libspectral_hip (fno)", "fno_last_error", lambda: load())
+_stream, _ptr = hipbind.stream, hipbind.ptr
 
 
 def parameters_of(model):

@@ -19,6 +19,8 @@ import types
 import torch
 from torch import nn
 
+import hipbind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "lib", "libsurrogate_hip.so"))
 
@@ -54,39 +56,40 @@ MAX_SPANS = 4
 _EP, _CP, _i = ctypes.POINTER(EncoderParams), ctypes.POINTER(ChunkParams), ctypes.c_int
 _AP = ctypes.POINTER(AdamParams)
 SYMBOLS = (
-    ("sur_geometry_supported", [_EP, _EP, _CP]),
-    ("sur_encoder_saved_floats", [_EP]),
-    ("sur_encoder_forward", [_fp, _EP, _fp, _i, _fp, _fp]),
-    ("sur_encoder_backward", [_fp, _EP, _fp, _fp, _i, _fp, _i, _i, _fp]),
-    ("sur_encoder_workspace_floats", [_EP, _i]),
-    ("sur_encoder_forward_multi", [_fp, _i, ctypes.POINTER(_EP), ctypes.POINTER(_fp), ctypes.POINTER(_i), ctypes.POINTER(_fp),
-                                   ctypes.POINTER(_fp), _i]),
-    ("sur_encoder_backward_multi", [_fp, _i, ctypes.POINTER(_EP), ctypes.POINTER(_fp), ctypes.POINTER(_fp),
-                                    ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_fp),
-                                    ctypes.POINTER(_fp)]),
-    ("sur_flush_encoder_grads", [_fp, _EP, _AP, _i]),
-    ("sur_chunk_saved_floats", [_CP]),
-    ("sur_chunk_forward", [_fp, _CP, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
-    ("sur_chunk_workspace_floats", [_CP, _i, _i]),
-    ("sur_chunk_backward", [_fp, _CP, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp,
-                            _i, _i, _fp, _fp]),
-    ("sur_chunks_backward", [_fp, _CP, _i, ctypes.POINTER(ChunkSpan), _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _fp, _fp]),
-    ("sur_flush_chunk_grads", [_fp, _CP, _AP, _i]),
-    ("sur_flush_all_grads", [_fp, _EP, _AP, _EP, _AP, _CP, _AP, _i]),
-    ("sur_adam_apply", [_fp, _EP, _AP, _EP, _AP, _CP, _AP]),
-    ("sur_tbptt_delta_loss", [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp, _fp,
-                              _fp, _fp, _fp]),
-    ("sur_chunk_integrate", [_fp, _CP, _fp, _fp, _i, _i, _i, _fp]),
-    ("sur_tbptt_delta_loss_rows", [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
-                                   ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i]),
-    ("sur_tbptt_delta_loss_finalize", [_fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
-    ("sur_fold_rows", [_fp, _EP, _EP, _CP, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
-    ("sur_tbptt_delta_loss_range", [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
-                                    ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i]),
-    ("sur_latent_chunk_forward", [_fp, _CP, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
-    ("sur_latent_workspace_floats", [_CP, _i, _i]),
-    ("sur_latent_chunk_backward", [_fp, _CP, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp,
-                                   _i, _i, _fp, _fp]),
+    ("sur_geometry_supported", _i, [_EP, _EP, _CP]),
+    ("sur_encoder_saved_floats", _i, [_EP]),
+    ("sur_encoder_forward", _i, [_fp, _EP, _fp, _i, _fp, _fp]),
+    ("sur_encoder_backward", _i, [_fp, _EP, _fp, _fp, _i, _fp, _i, _i, _fp]),
+    ("sur_encoder_workspace_floats", _i, [_EP, _i]),
+    ("sur_encoder_forward_multi", _i, [_fp, _i, ctypes.POINTER(_EP), ctypes.POINTER(_fp), ctypes.POINTER(_i), ctypes.POINTER(_fp),
+                                       ctypes.POINTER(_fp), _i]),
+    ("sur_encoder_backward_multi", _i, [_fp, _i, ctypes.POINTER(_EP), ctypes.POINTER(_fp), ctypes.POINTER(_fp),
+                                        ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_fp),
+                                        ctypes.POINTER(_fp)]),
+    ("sur_flush_encoder_grads", _i, [_fp, _EP, _AP, _i]),
+    ("sur_chunk_saved_floats", _i, [_CP]),
+    ("sur_chunk_forward", _i, [_fp, _CP, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
+    ("sur_chunk_workspace_floats", _i, [_CP, _i, _i]),
+    ("sur_chunk_backward", _i, [_fp, _CP, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp,
+                                _i, _i, _fp, _fp]),
+    ("sur_chunks_backward", _i, [_fp, _CP, _i, ctypes.POINTER(ChunkSpan), _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _fp, _fp]),
+    ("sur_flush_chunk_grads", _i, [_fp, _CP, _AP, _i]),
+    ("sur_flush_all_grads", _i, [_fp, _EP, _AP, _EP, _AP, _CP, _AP, _i]),
+    ("sur_adam_apply", _i, [_fp, _EP, _AP, _EP, _AP, _CP, _AP]),
+    ("sur_tbptt_delta_loss", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                  ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    ("sur_chunk_integrate", _i, [_fp, _CP, _fp, _fp, _i, _i, _i, _fp]),
+    ("sur_tbptt_delta_loss_rows", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i]),
+    ("sur_tbptt_delta_loss_finalize", _i, [_fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
+    ("sur_fold_rows", _i, [_fp, _EP, _EP, _CP, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    ("sur_tbptt_delta_loss_range", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i]),
+    ("sur_latent_chunk_forward", _i, [_fp, _CP, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
+    ("sur_latent_workspace_floats", _i, [_CP, _i, _i]),
+    ("sur_latent_chunk_backward", _i, [_fp, _CP, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp,
+                                       _i, _i, _fp, _fp]),
+    ("sur_last_error", ctypes.c_char_p, []),
 )
 _lib = None
 
@@ -98,31 +101,12 @@ class SurrogateHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise SurrogateHipError(f"{LIB_PATH} not found: build it (python -c 'import __graft_entry__ as g; "
-                                    f"g.build()').  The fused surrogate path has no fallback.")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, args in SYMBOLS:
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = ctypes.c_int, args
-        lib.sur_last_error.restype = ctypes.c_char_p
-        _lib = lib
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, SurrogateHipError, "The fused surrogate path has no fallback.")
     return _lib
 
 
-def _check(rc):
-    if rc != 0:
-        raise SurrogateHipError(f"libsurrogate_hip error {rc}: {load().sur_last_error().decode(errors='replace')}")
-
-
-def _stream():
-    # raw handle of torch's current stream; torch.cuda.current_stream() costs ~8 us of Python per call and the eager
-    # step makes a dozen
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+_check = hipbind.checker(SurrogateHipError, "libsurrogate_hip", "sur_last_error", lambda: load())
+_stream, _ptr = hipbind.stream, hipbind.ptr
 
 
 # ---------------------------------------------------------------------------------------------
@@ -675,7 +659,7 @@ class _EncoderFn(torch.autograd.Function):
             h //= s
         z = torch.empty((m, pack.c.c[3], h), device=x.device, dtype=torch.float32)
         saved = _encoder_saved_buffer(pack, m, x.device) if any(ctx.needs_input_grad) else None
-        _check(load().sur_encoder_forward(_stream(), ctypes.byref(pack.c), _p(x), m, _p(z), _p(saved)))
+        _check(load().sur_encoder_forward(_stream(), ctypes.byref(pack.c), _ptr(x), m, _ptr(z), _ptr(saved)))
         ctx.save_for_backward(x)
         # (needs_input_grad, not x.requires_grad: grad mode is off in here, so a contiguous COPY never requires grad)
         ctx.pack, ctx.owner, ctx.need_dx, ctx.fwd_saved = pack, owner, ctx.needs_input_grad[0], saved
@@ -689,8 +673,8 @@ class _EncoderFn(torch.autograd.Function):
             _encoder_backward_multi(load(), [(ctx.pack, x, dz.contiguous(), x.shape[0], 0,
                                               min(ENCODER_ROWS, ctx.pack.c.rows), ctx.fwd_saved)])
         else:
-            _check(load().sur_encoder_backward(_stream(), ctypes.byref(ctx.pack.c), _p(x), _p(dz.contiguous()), x.shape[0],
-                                               _p(dx), 0, min(ENCODER_ROWS, ctx.pack.c.rows), _p(ctx.fwd_saved)))
+            _check(load().sur_encoder_backward(_stream(), ctypes.byref(ctx.pack.c), _ptr(x), _ptr(dz.contiguous()), x.shape[0],
+                                               _ptr(dx), 0, min(ENCODER_ROWS, ctx.pack.c.rows), _ptr(ctx.fwd_saved)))
         ctx.pack.dirty = True
         ctx.owner.schedule_flush()
         return dx, None, None, None
@@ -735,9 +719,9 @@ class _ChunkFn(torch.autograd.Function):
         d_all = torch.empty((k, b, 1, n), device=xlat_t.device, dtype=torch.float32)
         out_all = torch.empty_like(d_all)
         saved = _saved_buffer(pack, k, b, xlat_t.device) if any(ctx.needs_input_grad) else None
-        _check(load().sur_chunk_forward(_stream(), ctypes.byref(pack.c), _p(xlat_t), _p(lstates_t), _p(states_t), _p(h0),
-                                        _p(c0), pack.c.cs * pack.c.hq, k, s, b, _p(h_all), _p(c_all), _p(d_all), _p(out_all),
-                                        _p(saved)))
+        _check(load().sur_chunk_forward(_stream(), ctypes.byref(pack.c), _ptr(xlat_t), _ptr(lstates_t), _ptr(states_t), _ptr(h0),
+                                        _ptr(c0), pack.c.cs * pack.c.hq, k, s, b, _ptr(h_all), _ptr(c_all), _ptr(d_all), _ptr(out_all),
+                                        _ptr(saved)))
         ctx.save_for_backward(xlat_t, lstates_t, h0, c0, h_all, c_all)
         ctx.fwd_saved = saved
         ctx.pack, ctx.owner = pack, owner
@@ -763,10 +747,10 @@ class _ChunkFn(torch.autograd.Function):
         ctx.pack.ensure_rows(rows)
         ctx.owner.refresh_partials()
         work = _chunk_workspace(ctx.pack, k, b, xlat_t.device) if ctx.fwd_saved is not None else None
-        _check(load().sur_chunk_backward(_stream(), ctypes.byref(ctx.pack.c), _p(xlat_t), _p(lstates_t), _p(h0), _p(c0),
-                                         ctx.pack.c.cs * ctx.pack.c.hq, _p(h_all), _p(c_all), _p(dd_all), _p(dout_all), _p(dh_all), _p(dc_all), k,
-                                         lstates_t.shape[0], b, _p(dxlat), _p(dlst), _p(dh0), _p(dc0), 0, rows,
-                                         _p(ctx.fwd_saved), _p(work)))
+        _check(load().sur_chunk_backward(_stream(), ctypes.byref(ctx.pack.c), _ptr(xlat_t), _ptr(lstates_t), _ptr(h0), _ptr(c0),
+                                         ctx.pack.c.cs * ctx.pack.c.hq, _ptr(h_all), _ptr(c_all), _ptr(dd_all), _ptr(dout_all),
+                                         _ptr(dh_all), _ptr(dc_all), k, lstates_t.shape[0], b, _ptr(dxlat), _ptr(dlst), _ptr(dh0), _ptr(dc0), 0, rows,
+                                         _ptr(ctx.fwd_saved), _ptr(work)))
         ctx.pack.dirty = True
         ctx.owner.schedule_flush()
         dstates = _dstates(dout_all, lstates_t.shape[0]) if ctx.needs_input_grad[2] else None
@@ -802,9 +786,9 @@ class _DeltaLossFn(torch.autograd.Function):
         dd = torch.empty_like(d_all) if ctx.needs_input_grad[0] else None
         ctx.set_materialize_grads(False)
         partial, ticket = scratch
-        _check(load().sur_tbptt_delta_loss(_stream(), _p(states), states.stride(0), states.stride(1), _p(d_all), b, t, n, delta,
-                                           mean, stdv, _p(deltas), _p(dd),
-                                           _p(hstep), _p(loss), _p(stats), _p(partial), _p(ticket)))
+        _check(load().sur_tbptt_delta_loss(_stream(), _ptr(states), states.stride(0), states.stride(1), _ptr(d_all), b, t, n, delta,
+                                           mean, stdv, _ptr(deltas), _ptr(dd),
+                                           _ptr(hstep), _ptr(loss), _ptr(stats), _ptr(partial), _ptr(ticket)))
         ctx.dd = dd
         ctx.mark_non_differentiable(deltas, hstep, stats)
         return loss, hstep, stats, deltas
@@ -925,9 +909,9 @@ class _LatentChunkFn(torch.autograd.Function):
         c_all, z_all = torch.empty_like(h_all), torch.empty_like(h_all)
         out_all = torch.empty((k, b, 1, 4 * pack.c.hq), device=xlat_t.device, dtype=torch.float32)
         saved = _saved_buffer(pack, k, b, xlat_t.device) if train and any(ctx.needs_input_grad) else None
-        _check(load().sur_latent_chunk_forward(_stream(), ctypes.byref(pack.c), _p(xlat_t), _p(lstates_t), _p(h0), _p(c0),
-                                               pack.c.cs * pack.c.hq, k, s, b, _p(h_all), _p(c_all), _p(z_all), _p(out_all),
-                                               _p(saved)))
+        _check(load().sur_latent_chunk_forward(_stream(), ctypes.byref(pack.c), _ptr(xlat_t), _ptr(lstates_t), _ptr(h0), _ptr(c0),
+                                               pack.c.cs * pack.c.hq, k, s, b, _ptr(h_all), _ptr(c_all), _ptr(z_all), _ptr(out_all),
+                                               _ptr(saved)))
         ctx.save_for_backward(xlat_t, lstates_t, h0, c0, h_all, c_all)
         ctx.fwd_saved = saved
         ctx.pack, ctx.owner = pack, owner
@@ -951,10 +935,10 @@ class _LatentChunkFn(torch.autograd.Function):
         ctx.owner.refresh_partials()
         work = torch.empty(load().sur_latent_workspace_floats(ctypes.byref(ctx.pack.c), k, b), device=xlat_t.device,
                            dtype=torch.float32)
-        _check(load().sur_latent_chunk_backward(_stream(), ctypes.byref(ctx.pack.c), _p(xlat_t), _p(lstates_t), _p(h0), _p(c0),
-                                                ctx.pack.c.cs * ctx.pack.c.hq, _p(h_all), _p(c_all), _p(dout_all), _p(dz_all),
-                                                _p(dh_all), _p(dc_all), k, lstates_t.shape[0], b, _p(dxlat), _p(dlst), _p(dh0),
-                                                _p(dc0), 0, rows, _p(ctx.fwd_saved), _p(work)))
+        _check(load().sur_latent_chunk_backward(_stream(), ctypes.byref(ctx.pack.c), _ptr(xlat_t), _ptr(lstates_t), _ptr(h0), _ptr(c0),
+                                                ctx.pack.c.cs * ctx.pack.c.hq, _ptr(h_all), _ptr(c_all), _ptr(dout_all), _ptr(dz_all),
+                                                _ptr(dh_all), _ptr(dc_all), k, lstates_t.shape[0], b, _ptr(dxlat), _ptr(dlst), _ptr(dh0),
+                                                _ptr(dc0), 0, rows, _ptr(ctx.fwd_saved), _ptr(work)))
         ctx.pack.dirty = True
         ctx.owner.schedule_flush()
         return dxlat, dlst, dh0, dc0, None, None, None, None
@@ -1139,8 +1123,8 @@ def _tbptt_forward(states, actions, owner, surrogate, tau, tbtt, after_chunk=Non
     if fork_point is None:
         encode_later_actions()     # chunk 0's own action latents are among them (or nothing forks): before the chunk loop
     if not split:
-        _check(lib.sur_encoder_forward(_stream(), ctypes.byref(owner.state_enc.c), _p(states_t0), tau * b, _p(lstates[0]),
-                                       _p(ssaved[0])))
+        _check(lib.sur_encoder_forward(_stream(), ctypes.byref(owner.state_enc.c), _ptr(states_t0), tau * b, _ptr(lstates[0]),
+                                       _ptr(ssaved[0])))
     main = torch.cuda.current_stream(dev)
 
     tm = surrogate.transition_model
@@ -1162,8 +1146,8 @@ def _tbptt_forward(states, actions, owner, surrogate, tau, tbtt, after_chunk=Non
             seeds.append(out_all[k0 - 1:k0])
             lst = torch.empty((1, b, cs, hq), device=dev, dtype=torch.float32)
             ssaved.append(_encoder_saved_buffer(owner.state_enc, b, dev))
-            _check(lib.sur_encoder_forward(_stream(), ctypes.byref(owner.state_enc.c), _p(seeds[c]), b, _p(lst),
-                                           _p(ssaved[c])))
+            _check(lib.sur_encoder_forward(_stream(), ctypes.byref(owner.state_enc.c), _ptr(seeds[c]), b, _ptr(lst),
+                                           _ptr(ssaved[c])))
             lstates.append(lst)
             h0s.append(h_alls[-1][-1])
             c0s.append(c_alls[-1][-1])
@@ -1172,10 +1156,10 @@ def _tbptt_forward(states, actions, owner, surrogate, tau, tbtt, after_chunk=Non
         s_used = min(seeds[c].shape[0], k)
         if c in lat_ready:
             main.wait_event(lat_ready[c])    # this chunk's action latents (encoded on the side stream)
-        _check(lib.sur_chunk_forward(_stream(), ctypes.byref(owner.chunk.c), _p(lactions_t[k0:k1]), _p(lstates[c]),
-                                     _p(seeds[c]), _p(h0s[c]), _p(c0s[c]), 0 if c == 0 else s_lat, k, s_used, b,
-                                     _p(h_all), _p(c_all), _p(d_all[k0:k1]),
-                                     _p(out_all[k0:k1]) if (integrate_last or c < nchunks - 1) else None, _p(saved)))
+        _check(lib.sur_chunk_forward(_stream(), ctypes.byref(owner.chunk.c), _ptr(lactions_t[k0:k1]), _ptr(lstates[c]),
+                                     _ptr(seeds[c]), _ptr(h0s[c]), _ptr(c0s[c]), 0 if c == 0 else s_lat, k, s_used, b,
+                                     _ptr(h_all), _ptr(c_all), _ptr(d_all[k0:k1]),
+                                     _ptr(out_all[k0:k1]) if (integrate_last or c < nchunks - 1) else None, _ptr(saved)))
         h_alls.append(h_all)
         c_alls.append(c_all)
         saveds.append(saved)
@@ -1242,8 +1226,8 @@ def _tbptt_backward(owner, bounds, dims, saved_state, unified, dd_all):
         owner.chunk.ensure_rows(rows_all)
         owner.refresh_partials()
         work = _chunk_workspace(owner.chunk, t_total, b, dev)
-        _check(lib.sur_chunks_backward(_stream(), ctypes.byref(owner.chunk.c), nchunks, spans, _p(lactions_t), _p(h_all_u),
-                                       _p(c_all_u), _p(dd_all), t_total, b, _p(dxlat_all), 0, rows_all, _p(saved_u), _p(work)))
+        _check(lib.sur_chunks_backward(_stream(), ctypes.byref(owner.chunk.c), nchunks, spans, _ptr(lactions_t), _ptr(h_all_u),
+                                       _ptr(c_all_u), _ptr(dd_all), t_total, b, _ptr(dxlat_all), 0, rows_all, _ptr(saved_u), _ptr(work)))
     else:
         streams = _side_streams(owner, dev, nchunks)
         forks = []
@@ -1251,11 +1235,11 @@ def _tbptt_backward(owner, bounds, dims, saved_state, unified, dd_all):
             fork = _Fork(streams[c])
             with fork:
                 work = _chunk_workspace(owner.chunk, k1 - k0, b, dev)
-                _check(lib.sur_chunk_backward(_stream(), ctypes.byref(owner.chunk.c), _p(lactions_t[k0:k1]), _p(lstates[c]),
-                                              _p(h0s[c]), _p(c0s[c]), 0 if c == 0 else s_lat, _p(h_alls[c]), _p(c_alls[c]),
-                                              _p(dd_all[k0:k1]), None, None, None, k1 - k0, min(seeds[c].shape[0], k1 - k0), b,
-                                              _p(dxlat_all[k0:k1]), _p(dlsts[c]), None, None, c * rows, rows, _p(saveds[c]),
-                                              _p(work)))
+                _check(lib.sur_chunk_backward(_stream(), ctypes.byref(owner.chunk.c), _ptr(lactions_t[k0:k1]), _ptr(lstates[c]),
+                                              _ptr(h0s[c]), _ptr(c0s[c]), 0 if c == 0 else s_lat, _ptr(h_alls[c]), _ptr(c_alls[c]),
+                                              _ptr(dd_all[k0:k1]), None, None, None, k1 - k0, min(seeds[c].shape[0], k1 - k0), b,
+                                              _ptr(dxlat_all[k0:k1]), _ptr(dlsts[c]), None, None, c * rows, rows, _ptr(saveds[c]),
+                                              _ptr(work)))
                 for t in (work, dlsts[c]):
                     t.record_stream(fork.stream)
             forks.append(fork)
@@ -1359,9 +1343,9 @@ def fused_tbptt_train(surrogate, states, actions, tau, tbtt, delta, mean, stdv):
         # the last chunk's loss rows are on the critical path: rows only there (the reduction to loss / statistics and the
         # integration of its predictions follow on the side stream, `finish_last`)
         loss_rows = lib.sur_tbptt_delta_loss_rows if c == nchunks - 1 else lib.sur_tbptt_delta_loss_range
-        _check(loss_rows(_stream(), _p(states), states.stride(0), states.stride(1), _p(st.d_all), b, t_total, n, float(delta),
-                         float(mean), float(stdv), _p(deltas), _p(dd_all), _p(hstep), _p(loss), _p(stats), _p(partial),
-                         _p(ticket), k0, k1))
+        _check(loss_rows(_stream(), _ptr(states), states.stride(0), states.stride(1), _ptr(st.d_all), b, t_total, n, float(delta),
+                         float(mean), float(stdv), _ptr(deltas), _ptr(dd_all), _ptr(hstep), _ptr(loss), _ptr(stats), _ptr(partial),
+                         _ptr(ticket), k0, k1))
         if c == nchunks - 1:
             rows_done = torch.cuda.Event()
             rows_done.record(torch.cuda.current_stream(dev))
@@ -1369,10 +1353,10 @@ def fused_tbptt_train(surrogate, states, actions, tau, tbtt, delta, mean, stdv):
         dxlat = torch.empty_like(st.lactions_t[k0:k1])
         dlst = torch.empty_like(st.lstates[c])
         work = _chunk_workspace(owner.chunk, k, b, dev)
-        _check(lib.sur_chunk_backward(_stream(), ctypes.byref(owner.chunk.c), _p(st.lactions_t[k0:k1]), _p(st.lstates[c]),
-                                      _p(st.h0s[c]), _p(st.c0s[c]), 0 if c == 0 else st.s_lat, _p(st.h_alls[c]), _p(st.c_alls[c]),
-                                      _p(dd_all[k0:k1]), None, None, None, k, min(st.seeds[c].shape[0], k), b, _p(dxlat),
-                                      _p(dlst), None, None, chunk_base[c], chunk_rows[c], _p(st.saveds[c]), _p(work)))
+        _check(lib.sur_chunk_backward(_stream(), ctypes.byref(owner.chunk.c), _ptr(st.lactions_t[k0:k1]), _ptr(st.lstates[c]),
+                                      _ptr(st.h0s[c]), _ptr(st.c0s[c]), 0 if c == 0 else st.s_lat, _ptr(st.h_alls[c]), _ptr(st.c_alls[c]),
+                                      _ptr(dd_all[k0:k1]), None, None, None, k, min(st.seeds[c].shape[0], k), b, _ptr(dxlat),
+                                      _ptr(dlst), None, None, chunk_base[c], chunk_rows[c], _ptr(st.saveds[c]), _ptr(work)))
         _encoder_backward_multi(lib, [
             (owner.action_enc, st.actions_t[k0:k1], dxlat, k * b, act_base[c], act_rows[c], st.asaved[k0 * b:k1 * b]),
             (owner.state_enc, st.seeds[c], dlst, st.lstates[c].shape[0] * b, st_base[c], st_rows[c], st.ssaved[c])])
@@ -1391,10 +1375,10 @@ def fused_tbptt_train(surrogate, states, actions, tau, tbtt, delta, mean, stdv):
         k0, k1 = bounds[-1]
         fork = _Fork(side, after=tail[0])
         with fork:
-            _check(lib.sur_chunk_integrate(_stream(), ctypes.byref(owner.chunk.c), _p(st.seeds[-1]), _p(st.d_all[k0:k1]), k1 - k0,
-                                           min(st.seeds[-1].shape[0], k1 - k0), b, _p(st.out_all[k0:k1])))
-            _check(lib.sur_tbptt_delta_loss_finalize(_stream(), b, t_total, n, _p(hstep), _p(loss), _p(stats), _p(partial),
-                                                     _p(ticket)))
+            _check(lib.sur_chunk_integrate(_stream(), ctypes.byref(owner.chunk.c), _ptr(st.seeds[-1]), _ptr(st.d_all[k0:k1]), k1 - k0,
+                                           min(st.seeds[-1].shape[0], k1 - k0), b, _ptr(st.out_all[k0:k1])))
+            _check(lib.sur_tbptt_delta_loss_finalize(_stream(), b, t_total, n, _ptr(hstep), _ptr(loss), _ptr(stats), _ptr(partial),
+                                                     _ptr(ticket)))
         forks.append(fork)
 
     def after_chunk(c, st):
@@ -1446,9 +1430,9 @@ def fused_tbptt_forward_loss(surrogate, states, actions, tau, tbtt, delta, mean,
     if scratch is None:
         scratch = (torch.empty(40 * t_total, device=dev, dtype=torch.float64), torch.zeros(1, device=dev, dtype=torch.int32))
         owner.loss_scratch[t_total] = scratch
-    _check(load().sur_tbptt_delta_loss(_stream(), _p(states), states.stride(0), states.stride(1), _p(st.d_all), b, t_total, n,
-                                       float(delta), float(mean), float(stdv), _p(deltas), _p(st.dd_all), _p(hstep), _p(loss),
-                                       _p(stats), _p(scratch[0]), _p(scratch[1])))
+    _check(load().sur_tbptt_delta_loss(_stream(), _ptr(states), states.stride(0), states.stride(1), _ptr(st.d_all), b, t_total, n,
+                                       float(delta), float(mean), float(stdv), _ptr(deltas), _ptr(st.dd_all), _ptr(hstep), _ptr(loss),
+                                       _ptr(stats), _ptr(scratch[0]), _ptr(scratch[1])))
     st.owner = owner
     return st, (st.out_all.transpose(0, 1), st.d_all.transpose(0, 1), (st.h_alls[-1][-1], st.c_alls[-1][-1]), loss, hstep, stats,
                 deltas)

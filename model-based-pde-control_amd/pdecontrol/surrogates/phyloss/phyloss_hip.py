@@ -2,10 +2,9 @@
 the element-wise loss in ONE launch and its gradient in ONE launch, instead of about 25 small torch kernels per
 sub-step and direction.  ``_PhyLossFn`` is an ordinary autograd node: it launches on the current stream, allocates
 through torch only and never synchronises with the host, so it can be captured in a hipGraph."""
-import ctypes
-
 import torch
 
+from hipbind import ptr as _ptr, stream as _stream
 from pdecontrol.surrogates import ops
 
 WIDTHS = (64, 128, 256, 512, 1024)
@@ -19,14 +18,6 @@ def load():
 def _check(rc):
     from pdegym.burgers import _hip
     _hip.check(rc)
-
-
-def _stream():
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def unsupported(augmented):

@@ -21,13 +21,16 @@ import os
 import torch
 from torch import nn
 
+import hipbind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "lib", "libspectral_hip.so"))
 _p, _i = ctypes.c_void_p, ctypes.c_int
 SYMBOLS = (
-    ("spec_conv_forward", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
-    ("spec_conv_backward", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
-    ("spec_conv_supported", [_i, _i, _i, _i]),
+    ("spec_conv_forward", _i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    ("spec_conv_backward", _i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    ("spec_conv_supported", _i, [_i, _i, _i, _i]),
+    ("spec_last_error", ctypes.c_char_p, []),
 )
 _lib = None
 _LOG = logging.getLogger("pdecontrol.surrogates")
@@ -42,21 +45,12 @@ class SpectralHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise SpectralHipError(f"{LIB_PATH} not found: build it (python -c 'import __graft_entry__ as g; g.build()'). "
-                                   f"The fused spectral convolution has no fallback.")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, args in SYMBOLS:
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = ctypes.c_int, args
-        lib.spec_last_error.restype = ctypes.c_char_p
-        _lib = lib
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, SpectralHipError, "The fused spectral convolution has no fallback.")
     return _lib
 
 
-def _check(rc):
-    if rc != 0:
-        raise SpectralHipError(f"libspectral_hip error {rc}: {load().spec_last_error().decode(errors='replace')}")
+_check = hipbind.checker(SpectralHipError, "libspectral_hip", "spec_last_error", lambda: load())
+_stream, _ptr = hipbind.stream, hipbind.ptr
 
 
 def unsupported(cin, cout, n, modes):
@@ -67,14 +61,6 @@ def unsupported(cin, cout, n, modes):
         rc = lib.spec_conv_supported(*key)
         _GEOMETRY[key] = None if rc == 0 else f"error {rc}: {lib.spec_last_error().decode(errors='replace')}"
     return _GEOMETRY[key]
-
-
-def _stream():
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def spectral_conv1d_reference(x, wr, wi):

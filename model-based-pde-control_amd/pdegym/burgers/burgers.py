@@ -18,6 +18,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from hipbind import ptr as _ptr
 from pdegym._gym import gym
 from pdegym.burgers import _hip
 from pdegym.common.transforms import FuncTransform, GaussianForcing
@@ -25,10 +26,6 @@ from pdegym.common.transforms import FuncTransform, GaussianForcing
 
 def _stream(dev):
     return _hip.ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else 0))
-
-
-def _ptr(t):
-    return None if t is None else _hip.ctypes.c_void_p(t.data_ptr())
 
 
 class BurgersBatchedVecEnv(gym.vector.VectorEnv):

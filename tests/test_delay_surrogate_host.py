@@ -1,10 +1,9 @@
 """The delay-embedding surrogate ablation (KSDelayCNNSurrogateFactory) on the CPU: registry, seeded initial weights, rollout
 and training_step against the reference's recorded values (tests/golden/delay_golden.npz, written by
 tools/gen_delay_golden.py), bit for bit; the re-encoding the free-running delay step reads; the routing predicates; and
-the exports of libdelay_hip.so."""
+the host-side answers of libdelay_hip.so."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +13,6 @@ import _delay_models as dm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "model-based-pde-control_amd", "lib", "libdelay_hip.so")
-HEADER = os.path.join(ROOT, "include", "delay_hip.h")
 
 
 @pytest.fixture(scope="module")
@@ -162,21 +160,13 @@ def test_fused_routing_predicates():
     assert not delay_hip.fused_delay_supported(sur)
 
 
-def _header_functions():
-    text = open(HEADER).read()
-    return set(re.findall(r"\b(dly_\w+)\s*\(", text))
-
-
 def test_library_exports_every_header_function():
+    """load() types every row of the binding's table (a missing export raises); that the table is the header's:
+    tests/test_capi_symbols.py.  Then the host-side answers and refusals."""
     from pdecontrol.surrogates import delay_hip
-    declared = _header_functions()
-    assert declared == {name for name, _, _ in delay_hip.SYMBOLS}
     if not os.path.exists(LIB):
         pytest.skip("libdelay_hip.so not built")
-    lib = ctypes.CDLL(LIB)   # loads without a GPU
-    for name in declared:
-        assert hasattr(lib, name), name
-    lib = delay_hip.load()
+    lib = delay_hip.load()   # loads without a GPU
     assert lib.dly_param_count() == 39830
     assert lib.dly_supported(64, 3, 8, 8, 4, 8, 4, 39830) == 0
     assert lib.dly_supported(64, 2, 8, 8, 4, 8, 4, 39830) < 0 and b"delay" in lib.dly_last_error()

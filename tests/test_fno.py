@@ -3,8 +3,6 @@
 to the torch.fft spelling in fp32."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,8 +11,6 @@ import torch
 from pdecontrol.architectures import BurgersFNO
 from pdecontrol.surrogates import spectral
 from pdecontrol.surrogates.training import PDETrainingModule
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_reference_spelling_is_the_truncated_dft_definition():
@@ -62,13 +58,7 @@ def test_fno_surrogate_through_the_training_module_on_cpu():
 
 
 def test_spectral_c_abi_exports_and_rejects_bad_geometry():
-    text = open(os.path.join(ROOT, "include", "spectral_hip.h")).read()
-    declared = sorted(set(re.findall(r"\b(spec_[a-z_]+)\s*\(", text)))
-    lib = ctypes.CDLL(spectral.LIB_PATH)
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert sorted([n for n, _ in spectral.SYMBOLS] + ["spec_last_error"]) == declared
-    lib.spec_last_error.restype = ctypes.c_char_p
+    lib = spectral.load()
     one = ctypes.c_void_p(1)
     assert lib.spec_conv_forward(None, one, one, one, 2, 16, 16, 100, 8, one, None) < 0     # N not a power of two
     assert b"power of two" in lib.spec_last_error()
@@ -153,14 +143,9 @@ def test_fno_step_as_one_captured_graph():
 # no FNO); pinned against the per-operator torch spelling of the same module.
 # ---------------------------------------------------------------------------------------------------------------------
 def test_fno_c_abi_exports():
+    """load() types every fno_* row (a missing export raises); that the table is the header's: tests/test_capi_symbols.py."""
     from pdecontrol.surrogates import fno_hip
-    text = open(os.path.join(ROOT, "include", "spectral_hip.h")).read()
-    declared = sorted(set(re.findall(r"\b(fno_[a-z_]+)\s*\(", text)))
-    lib = ctypes.CDLL(spectral.LIB_PATH)
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert sorted(n for n, _, _ in fno_hip.SYMBOLS) == declared
-    lib.fno_row_width.restype = ctypes.c_int
+    lib = fno_hip.load()
     assert lib.fno_row_width() >= 96 + 4 * 1056 + 1089
 
 

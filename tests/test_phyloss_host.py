@@ -99,10 +99,7 @@ def test_entry_points_validate_on_the_host():
     """Refusals come back as a negative status with a message, before anything is launched (so this needs no GPU)."""
     import ctypes
     from pdegym.burgers import _hip
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    lib.bg_last_error.restype = ctypes.c_char_p
-    for name, args in _hip.SYMBOLS:
-        getattr(lib, name).argtypes = args
+    lib = _hip.load()
     one = ctypes.c_void_p(64)
     fwd = lambda B, T, N, S, diff, states, n: lib.bg_phyloss_forward(None, one, B, T, N, 0.1, 1e-3, 0.01, S, one, diff, states, n)
     bwd = lambda B, T, N, S, states, n: lib.bg_phyloss_backward(None, one, one, one, states, n, B, T, N, 0.1, 1e-3, 0.01, S, one)

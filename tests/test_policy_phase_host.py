@@ -102,18 +102,10 @@ def test_cpu_phase_with_zero_updates_does_nothing():
 # ---------------------------------------------------------------------------------------------------------------------
 # header and binding
 # ---------------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(rp_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_header_binding_and_library_agree():
+    """(that the header declares exactly the bound names and the library exports them: tests/test_capi_symbols.py)"""
     from pdecontrol.mbrl import replay_hip
-    names = _declared("replay_hip.h")
-    assert names == sorted(n for n, _, _ in replay_hip.SYMBOLS) == ["rp_gather", "rp_last_error", "rp_supported"]
-    lib = replay_hip.load()
-    assert all(hasattr(lib, n) for n in names)
+    assert sorted(n for n, _, _ in replay_hip.SYMBOLS) == ["rp_gather", "rp_last_error", "rp_supported"]
     header = open(os.path.join(ROOT, "include", "replay_hip.h")).read()
     for macro, value in (("RP_MAX_SOURCES", replay_hip.MAX_SOURCES), ("RP_MAX_OBS_DIM", replay_hip.MAX_OBS_DIM),
                          ("RP_MAX_ACT_DIM", replay_hip.MAX_ACT_DIM)):

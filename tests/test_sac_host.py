@@ -3,7 +3,6 @@ recorded from the reference's class by tools/gen_sac_golden.py, through the same
 ``update_many`` on the CPU and the host side of libsac_hip.so."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -11,7 +10,7 @@ import pytest
 import torch
 
 import _sac_models as sm
-from conftest import GOLDEN, ROOT, require_fma_sgemm
+from conftest import GOLDEN, require_fma_sgemm
 
 
 @pytest.fixture(scope="module")
@@ -143,12 +142,9 @@ def lib():
 
 
 def test_every_prototype_is_bound_and_exported(lib):
+    """(that the bound names are the header's prototypes: tests/test_capi_symbols.py)"""
     from pdecontrol.sac import sac_hip
-    header = open(os.path.join(ROOT, "include", "sac_hip.h")).read()
-    body = header[header.index("#ifdef __cplusplus"):]
-    protos = set(re.findall(r"^(?:const\s+)?\w[\w\s\*]*?\b(sac_\w+)\s*\(", body, flags=re.M))
-    assert protos == {name for name, _, _ in sac_hip.SYMBOLS}, protos
-    for name in protos:
+    for name, _, _ in sac_hip.SYMBOLS:
         assert hasattr(lib, name), name
     assert ctypes.sizeof(sac_hip.Config) == 5 * 4 + 3 * 4 + 12 * 4
     assert ctypes.sizeof(sac_hip.State) == 8 * (3 * 8 + 4 * 12 + 7)
