@@ -1,0 +1,469 @@
+"""The controller's imagined-rollout phase (reference ``pdecontrol/mbrl/mbrl.py:415-435``) behind one call.
+
+The reference runs, per controller iteration,
+
+    world.setup(starting); rollout = world_worker.rollout(agent, world_stop); world_replay.extend(rollout); world_worker.reset()
+
+where every imagined step crosses the host four times: ``select_action`` (H2D, launch, D2H), the five action wrappers in
+numpy, the world step (H2D, graph replay, reward, D2H) and ``Sample.split`` + ``ExperienceReplay.add`` (7 appends per env).
+``imagine(agent, stack, num_rollouts)`` returns the ``ExperienceReplay`` a fresh ``Worker(stack)`` returns for the stop
+condition ``eps >= num_rollouts``, on one of two tiers (chosen per call, announced once per reason):
+
+loop tier     ``Worker.rollout`` (pdecontrol/mbrl/worker.py): CPU agents, ``PDECONTROL_FUSED=0``, any stack
+              ``recognize_stack`` does not reduce to the controller's, worlds that are not device-resident.
+kernel tier   the closed loop stays in HBM for a whole round (one reset plus the steps up to the joint truncation of
+              ``WorldVecEnv.step_wait``, whose number is known on the host once the reset has drawn its windows).  One
+              step is ``noise.normal_()`` plus one hipGraph replay of
+                  sac_policy_forward -> ro_act_chain -> every member's fused one-step rollout -> ro_settle
+              (csrc/rollout.hip); the per-step elite draws are made on the host in the loop's order and uploaded once per
+              round; one D2H copy and one synchronisation per round bring the trajectory block back, and the replay is
+              built from it with one deque per episode and field.
+
+In both tiers the replay is the loop's (bit for bit but the rewards of the kernel tier, which are the fp64 row sums of
+``ro_settle`` where the loop squares an fp32 ``vector_norm``), numpy's global generator and torch's CPU and device
+generators are left where the loop leaves them, and so are the world's ``timesteps``, ``simulated``, state and hidden
+tensors.  ``deterministic`` reaches ``agent.select_action``, which ignores it as the reference's does: both tiers sample.
+The host-side stores of the wrapper stack are not written by the kernel tier: the controller drops them with
+``world_worker.reset()`` right after the phase.
+
+``imagine(...).device_rollout`` (kernel tier; None otherwise) keeps the phase's samples packed on the device in
+``DeviceSubSeqStore.tensors`` order and dtypes, episodes contiguous in the replay's key order, with the ``starts`` of
+every episode.
+"""
+import ctypes
+import time
+from collections import deque
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from pdecontrol.mbrl.policy_phase import FieldMap, Unrecognized, _flatten, field_map
+from pdecontrol.mbrl.replay import ExperienceReplay
+from pdecontrol.mbrl.worker import Worker
+from pdecontrol.surrogates import ops
+from pdegym.common import transforms as tr
+from pdegym.common import vec_wrappers as vw
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 1. stack recognition
+# ----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class StackGeometry:
+    """What a recognised stack does between the agent and the world.
+
+    ``act_in``      the scaling of the agent's action columns before the forcing (identity sensor)
+    ``forcing``     the ``GaussianForcing`` matrix [A, L] (fp32, host)
+    ``act_out``     sensor and scaling of the forcing columns: the world's action row
+    ``agent_obs``   the agent sensor over the world's observation columns
+    ``reward``      the rescaling of the world's observation before the l2control reward
+    """
+    world: object
+    act_in: FieldMap
+    forcing: torch.Tensor
+    act_out: FieldMap
+    agent_obs: FieldMap
+    reward: FieldMap
+
+
+def _is_forcing(t):
+    if isinstance(t, tr.BatchTransform):
+        t = t.transform
+    return t if type(t) is tr.GaussianForcing else None
+
+
+def _updates_statistics(wrapper):
+    """A ``TransformActionWrapper`` whose step changes its transform: not frozen, over a scaling that is not frozen."""
+    if wrapper.frozen or _is_forcing(wrapper.transform) is not None:
+        return False
+    return any(step[0] == "scale" and not step[1].frozen for step in _flatten(wrapper.transform))
+
+
+def recognize_stack(stack):
+    """``StackGeometry`` of the controller's imagined-rollout stack (mbrl.py:321-329), or raises ``Unrecognized``:
+    ``StoreNActionsVecWrapper`` outermost, then ``TransformActionWrapper``s that flatten to at most one scaling, exactly
+    one ``GaussianForcing``, at most one scaling and sensors; ``TransformObsWrapper``s holding only sensors over a
+    ``StoreNObsVecWrapper``; a ``WorldVecEnv`` whose observation connector is a stride-1 sensor and at most one scaling
+    and whose batched reward is a ``KuramotoSivashinskyEnv``'s l2control."""
+    from pdecontrol.mbrl.world.world import WorldVecEnv
+    from pdegym.kuramoto import KuramotoSivashinskyEnv
+    env = stack.envs
+    if type(env) is not vw.StoreNActionsVecWrapper or env is not stack.astore:
+        raise Unrecognized(f"a {type(env).__name__} in place of the action store on top of the stack")
+    if env.num_steps != 1:
+        raise Unrecognized(f"an action store of {env.num_steps} steps")
+    env = env.env
+    before, forcing, after = [], None, []
+    while type(env) is vw.TransformActionWrapper:
+        if _updates_statistics(env):
+            raise Unrecognized("an action transform that updates its statistics")
+        f = _is_forcing(env.transform)
+        if f is not None:
+            if forcing is not None:
+                raise Unrecognized("two forcings")
+            forcing = f
+        else:
+            (before if forcing is None else after).append(env.transform)
+        env = env.env
+    if forcing is None:
+        raise Unrecognized("an action stack without a GaussianForcing")
+    sensors = []
+    while type(env) is vw.TransformObsWrapper:
+        sensors.append(env.transform)
+        env = env.env
+    if type(env) is not vw.StoreNObsVecWrapper or env is not stack.ostore:
+        raise Unrecognized(f"a {type(env).__name__} in place of the observation store")
+    if env.num_steps != 1:
+        raise Unrecognized(f"an observation store of {env.num_steps} steps")
+    world = env.env
+    if not isinstance(world, WorldVecEnv):
+        raise Unrecognized(f"a {type(world).__name__} in place of the WorldVecEnv")
+    oshape, ashape = tuple(world.single_observation_space.shape), tuple(world.single_action_space.shape)
+    if len(oshape) != 2 or oshape[0] != 1 or len(ashape) != 2 or ashape[0] != 1:
+        raise Unrecognized(f"a world with observations {oshape} and actions {ashape} (one channel each)")
+    matrix = forcing.forcing.detach().cpu()
+    if matrix.dtype != torch.float32 or matrix.dim() != 2:
+        raise Unrecognized("a forcing matrix that is not fp32 [A, N]")
+    A, L = (int(v) for v in matrix.shape)
+    act_in = field_map(tr.Operation(before), A)
+    if (act_in.start, act_in.stride, act_in.width) != (0, 1, A):
+        raise Unrecognized("a sensor on the agent's actions")
+    act_out = field_map(tr.Operation(after), L)
+    if act_out.width != ashape[1]:
+        raise Unrecognized(f"an action stack that yields {act_out.width} columns for a world that takes {ashape[1]}")
+    agent_obs = field_map(tr.Operation(list(reversed(sensors))), oshape[1])
+    if agent_obs.coef is not None:
+        raise Unrecognized("a scaling on the agent's observations")
+    reward = field_map(world.stransf.otransf, oshape[1])
+    if (reward.start, reward.stride) != (0, 1):
+        raise Unrecognized("a world whose observation connector carries a sensor of stride above 1")
+    owner = getattr(world.batched_reward_func, "__self__", None)
+    if not isinstance(owner, KuramotoSivashinskyEnv):
+        raise Unrecognized("a world without the batched reward of a KuramotoSivashinskyEnv")
+    if not owner.objective:
+        raise Unrecognized("the dissipation objective")
+    if owner.N != oshape[1]:
+        raise Unrecognized(f"a reward over {owner.N} grid points for observations of {oshape[1]}")
+    return StackGeometry(world, act_in, matrix.contiguous(), act_out, agent_obs, reward)
+
+
+def round_length(timesteps0, horizon, max_episode_steps):
+    """Steps of the round that starts at env counters ``timesteps0``: the first ``s`` at which ``WorldVecEnv.step_wait``
+    truncates, that is ``s >= horizon`` or every ``timesteps0 + s >= max_episode_steps``."""
+    timesteps0 = np.asarray(timesteps0)
+    s = 1
+    while not (s >= horizon or np.all(timesteps0 + s >= max_episode_steps)):
+        s += 1
+    return s
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 2. the captured step
+# ----------------------------------------------------------------------------------------------------------------------
+class DeviceRollout:
+    """The phase's samples packed on the device: ``tensors`` in ``DeviceSubSeqStore.tensors`` order and dtypes, episodes
+    contiguous in key order, ``starts[key]`` the first row of each."""
+
+    def __init__(self, tensors, starts, device):
+        self.tensors, self.starts, self.device = tuple(tensors), dict(starts), device
+        self.total = int(self.tensors[0].shape[0])
+
+
+def _coef(fmap, device):
+    return None if fmap.coef is None else fmap.coef.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _same_coef(a, b):
+    return (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and torch.equal(a, b))
+
+
+class _CapturedStep:
+    """Static buffers and the hipGraph of one imagined step for one (world state, agent, stack geometry, horizon)."""
+
+    def __init__(self, agent, fused, geo):
+        from pdecontrol.mbrl import rollout_hip as ro
+        from pdecontrol.sac import sac_hip
+        from pdecontrol.surrogates.graph_step import capture_graph
+        from pdecontrol.surrogates.hipops import pooled_streams
+        world = geo.world
+        dev = world._dev
+        device = dev.device
+        self.dev, self.fused, self.version = dev, fused, fused.version
+        B, N, T = dev.b, dev.n, max(int(world.horizon), 1)
+        A, L = (int(v) for v in geo.forcing.shape)
+        O = geo.agent_obs.width
+        self.B, self.N, self.T, self.A, self.O = B, N, T, A, O
+        self.geometry = ro.Geometry(B, T, N, A, L, geo.act_out.start, geo.act_out.stride, geo.agent_obs.start,
+                                    geo.agent_obs.stride, len(dev.members))
+        self.maps = (geo.act_in, geo.act_out, geo.agent_obs, geo.reward)
+        self.forcing_host = geo.forcing
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=device)
+        self.forcing = geo.forcing.to(device)
+        self.coefs = [_coef(m, device) for m in (geo.act_in, geo.act_out, geo.reward)]
+        self.coefs_host = [m.coef for m in (geo.act_in, geo.act_out, geo.reward)]
+        # the trajectory block of one round, one D2H copy: [traj (T+1)BN | actions TBA | rewards TB | steps TB (int32)]
+        sizes = ((T + 1) * B * N, T * B * A, T * B, T * B)
+        self.block = f32(sum(sizes))
+        traj, actions, rewards, steps = torch.split(self.block, sizes)
+        self.traj, self.actions = traj.view(T + 1, B, N), actions.view(T, B, A)
+        self.rewards, self.steps = rewards.view(T, B), steps.view(torch.int32).view(T, B)
+        self.sizes = sizes
+        self.block_host = torch.empty(self.block.shape, dtype=torch.float32).pin_memory()
+        # per round one upload: [chosen T*B | steps0 B] int32
+        self.ints_host = torch.zeros(T * B + B, dtype=torch.int32).pin_memory()
+        self.ints = torch.zeros(T * B + B, dtype=torch.int32, device=device)
+        self.chosen, self.steps0 = self.ints[:T * B].view(T, B), self.ints[T * B:]
+        self.step = torch.zeros(2, dtype=torch.int32, device=device)
+        self.policy_obs = f32(B, 1, O)
+        self.action = f32(B, A)
+        shape = (B, agent.policy.achannels, agent.policy.aheight)
+        self.noise = f32(*shape)          # always drawn: ``select_action`` samples whatever ``deterministic`` says
+        assert dev.act.numel() == B * geo.act_out.width and dev.state.numel() == B * N and dev.state.is_contiguous()
+        act_args = ro.act_args(self.action, self.actions, self.coefs[0], self.forcing, self.coefs[1], dev.act, self.step)
+        self.keep = []
+        tstep = world.tstep
+
+        def step():
+            stream = sac_hip._stream()
+            sac_hip._check(sac_hip.load().sac_policy_forward(
+                stream, ctypes.byref(fused.cfg), ctypes.byref(fused.state), B, sac_hip._ptr(self.policy_obs), sac_hip._ptr(self.noise),
+                sac_hip._ptr(self.action), None, None))
+            ro.act_chain(stream, self.geometry, act_args)
+            outs = []
+            for sur, hid in zip(dev.members, dev.hidden):
+                r = sur.rollout(states=dev.state, actions=dev.act, times=0.0, targets=tstep, hidden=hid)
+                outs.append(r.outputs.reshape(B, N).contiguous())
+                for h, new in zip(hid, r.hidden):
+                    h.copy_(new)
+            self.keep = outs
+            ro.settle(stream, self.geometry, ro.settle_args(
+                outs, self.chosen if len(outs) > 1 else None, dev.state, self.traj, self.policy_obs, self.steps0, self.steps,
+                self.rewards, self.coefs[2], self.step))
+
+        saved = (dev.state.clone(), [tuple(h.clone() for h in hid) for hid in dev.hidden])
+        (stream,) = pooled_streams(device, 1, "capture")
+        stream.wait_stream(torch.cuda.current_stream(device))
+        world.surrogate.eval()
+        with torch.cuda.stream(stream), torch.no_grad():
+            step()                                                         # warm-up (kernels, allocator)
+        self.graph = torch.cuda.CUDAGraph()
+
+        def step_nograd():
+            with torch.no_grad():
+                step()
+
+        capture_graph(self.graph, step_nograd, stream)
+        world.surrogate.train()
+        torch.cuda.current_stream(device).wait_stream(stream)
+        dev.state.copy_(saved[0])
+        for hid, old in zip(dev.hidden, saved[1]):
+            for h, sv in zip(hid, old):
+                h.copy_(sv)
+
+    def valid(self, fused, geo):
+        """The graph still describes this world state, agent and stack; coefficient VALUES that changed are re-uploaded
+        into the tensors the graph reads (the controller's observation scaling keeps learning between iterations)."""
+        world = geo.world
+        if (world._dev is not self.dev or not self.dev.valid() or fused is not self.fused or fused.version != self.version
+                or max(int(world.horizon), 1) != self.T):
+            return False
+        now = (geo.act_in, geo.act_out, geo.agent_obs, geo.reward)
+        if any((a.start, a.stride, a.width, a.coef is None) != (b.start, b.stride, b.width, b.coef is None)
+               for a, b in zip(self.maps, now)):
+            return False
+        if geo.forcing.shape != self.forcing_host.shape:
+            return False
+        if not torch.equal(geo.forcing, self.forcing_host):
+            self.forcing.copy_(geo.forcing)
+            self.forcing_host = geo.forcing
+        for i, m in enumerate((geo.act_in, geo.act_out, geo.reward)):
+            if not _same_coef(m.coef, self.coefs_host[i]):
+                self.coefs[i].copy_(m.coef)
+                self.coefs_host[i] = m.coef
+        self.maps = now
+        return True
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 3. the phase
+# ----------------------------------------------------------------------------------------------------------------------
+def _notice(reason):
+    if reason not in ops._NOTIFIED:
+        ops._NOTIFIED.add(reason)
+        ops._LOG.warning("the fused imagined-rollout step does not implement %s: the imagined-rollout phase runs the "
+                         "per-step loop of Worker.rollout", reason)
+
+
+def _kernel_tier(agent, stack):
+    """(StackGeometry, FusedSAC) when this phase runs on the kernels, else (None, None)."""
+    from pdecontrol.mbrl import rollout_hip as ro
+    from pdecontrol.sac import sac_hip
+    if agent.device.type != "cuda" or not ops.fused_enabled():
+        return None, None
+    try:
+        geo = recognize_stack(stack)
+    except Unrecognized as e:
+        _notice(str(e))
+        return None, None
+    world = geo.world
+    if not world._use_device_path() or world._dev_starting is None:
+        _notice("a world that does not keep its trajectories on the device (members the device world path refuses, "
+                "no batched reward, or a starting-state dataset it cannot pack)")
+        return None, None
+    from pdecontrol.mbrl.world.world import _members, _surrogate_device
+    if _surrogate_device(world.surrogate) != torch.empty(0, device=agent.device).device:
+        _notice("an agent and a world on different devices")
+        return None, None
+    A, L = (int(v) for v in geo.forcing.shape)
+    geometry = ro.Geometry(world.num_envs, max(int(world.horizon), 1), geo.reward.width, A, L, geo.act_out.start,
+                           geo.act_out.stride, geo.agent_obs.start, geo.agent_obs.stride, len(_members(world.surrogate)[0]))
+    reason = ro.supported(geometry)
+    if reason is not None:
+        _notice(reason)
+        return None, None
+    obs = torch.empty((world.num_envs, 1, geo.agent_obs.width), dtype=torch.float32, device=agent.device)
+    if not sac_hip.use_kernels(agent, obs):                 # announces its own reason
+        return None, None
+    return geo, agent._fused_for(obs)
+
+
+def _build_replay(rounds, B):
+    """(the loop's ``ExperienceReplay``, the episode keys of every round) from the rounds' host blocks: one deque per
+    episode and field.  Items are what ``Sample.split`` yields: [1, N] / [1, A] fp32 rows, fp32 rewards, numpy bools,
+    int32 steps.  The keys are the ones ``ExperienceReplay.add`` hands out: an env's ``vindex`` entry is created by its
+    first sample and moved on by its truncated one, env by env, so rounds of several steps get the keys r * B + b and
+    a first round of ONE step interleaves them (0, 2, 4, ... then 1, 3, 5, ...)."""
+    replay = ExperienceReplay()
+    stores, keys = replay._stores(), []
+    for traj, actions, rewards, steps in rounds:
+        T = actions.shape[0]
+        obs, nxt, act = traj[:T, :, None, :], traj[1:T + 1, :, None, :], actions[:, :, None, :]
+        terminated = np.zeros(T, dtype=np.bool_)
+        truncated = np.zeros(T, dtype=np.bool_)
+        truncated[-1] = True
+        if T > 1:                                        # the first step's ``add`` touches every env before any moves on
+            for b in range(B):
+                replay.vindex[b]
+        keys.append([])
+        for b in range(B):
+            key = replay.vindex[b]
+            replay.vindex[b] = replay._next_episode_id()
+            keys[-1].append(key)
+            for store, column in zip(stores, (obs[:, b], act[:, b], nxt[:, b], rewards[:, b], terminated, truncated,
+                                              steps[:, b])):
+                store[key] = deque(column)
+    return replay, keys
+
+
+def _device_rollout(blocks, keys, B, device):
+    """``DeviceRollout`` from the rounds' device blocks (traj, actions, rewards, steps): episodes in the replay's key
+    order (the order of their first sample), ``keys[r][b]`` the episode of env b in round r."""
+    cols, starts, off = [[] for _ in range(7)], {}, 0
+    for (traj, actions, rewards, steps), round_keys in zip(blocks, keys):
+        T = actions.shape[0]
+        major = lambda t: t.transpose(0, 1).reshape((B * T, 1) + tuple(t.shape[2:]))
+        flags = torch.zeros((B, T), dtype=torch.bool, device=device)
+        last = flags.clone()
+        last[:, -1] = True
+        for col, t in zip(cols, (major(traj[:T]), major(actions), major(traj[1:T + 1]), rewards.t().reshape(-1),
+                                 flags.reshape(-1), last.reshape(-1), steps.t().reshape(-1))):
+            col.append(t)
+        for b, key in enumerate(round_keys):
+            starts[key] = off + b * T
+        off += B * T
+    return DeviceRollout([torch.cat(c) for c in cols], starts, device)
+
+
+def imagine(agent, stack, num_rollouts, deterministic=False, timings=None, noise=None):
+    """The ``ExperienceReplay`` ``Worker(stack).rollout(agent, lambda ts, eps: eps >= num_rollouts, deterministic)`` returns
+    on a fresh worker (module docstring).  ``deterministic`` is passed to the loop's ``agent.select_action``, which accepts
+    and ignores it as the reference's does; the kernel tier therefore samples and draws its noise whatever it says.
+    ``timings`` (tools/imagination_phase_bench.py) is an optional dict that receives
+    the host seconds of the resets, the steps, the copies back and the replay build, and the tier that ran; on the kernel
+    tier each of the four then ends in a device synchronisation, which the phase otherwise does once per round.
+    ``noise`` (tests; kernel tier only, like the ``noise`` of ``SAC.update``) is an optional iterable of standard-normal
+    tensors [num_envs, achannels, aheight], one per step, used in place of the draws."""
+    geo, fused = (None, None) if num_rollouts <= 0 else _kernel_tier(agent, stack)
+    if geo is None:
+        if noise is not None:
+            raise ValueError("stored noise is a hook of the kernel tier; this call runs the loop tier")
+        t0 = time.perf_counter()
+        replay = Worker(stack).rollout(agent, lambda ts, eps: eps >= num_rollouts, deterministic)
+        replay.device_rollout = None
+        if timings is not None:
+            timings["loop_s"] = timings.get("loop_s", 0.0) + time.perf_counter() - t0
+            timings["tier"] = "loop"
+        return replay
+
+    world, device = geo.world, agent.device
+    B = world.num_envs
+    clock = time.perf_counter
+
+    def lap(name, t0):
+        if timings is not None:
+            torch.cuda.synchronize(device)
+            timings[name] = timings.get(name, 0.0) + clock() - t0
+        return clock()
+
+    t = clock()
+    fused.refresh(need_adam=fused._keys[1] if fused._keys else False)
+    world._reset_state()                         # the fresh worker's reset; (re)builds the device world state if stale
+    cap = getattr(world, "_imagination", None)
+    if cap is None or not cap.valid(fused, geo):
+        cap = world._imagination = _CapturedStep(agent, fused, geo)
+    dev = world._dev
+    elite = None if dev.ensemble is None else dev.ensemble.elite_idx
+    start, stride, O = geo.agent_obs.start, geo.agent_obs.stride, geo.agent_obs.width
+    stream = torch.cuda.current_stream(device)
+    rounds, blocks = [], []
+    stored = None if noise is None else iter(noise)
+    num_rounds = -(-int(num_rollouts) // B)
+    t = lap("reset_s", t)
+    for _ in range(num_rounds):
+        T = round_length(world.timesteps, world.horizon, world.max_episode_steps)
+        ints = cap.ints_host.numpy()
+        if elite is not None:                    # the draw of every step of the round, in the loop's order
+            for s in range(T):
+                ints[s * B:(s + 1) * B] = np.random.choice(elite, size=B)
+        ints[cap.T * B:] = world.timesteps
+        cap.ints.copy_(cap.ints_host, non_blocking=True)
+        state = dev.state.view(B, cap.N)
+        cap.traj[0].copy_(state)
+        cap.policy_obs.view(B, O).copy_(state[:, start::stride][:, :O])
+        cap.step.zero_()
+        world.surrogate.eval()
+        t = lap("reset_s", t)
+        for _s in range(T):
+            if stored is not None:
+                cap.noise.copy_(next(stored).reshape(cap.noise.shape), non_blocking=True)
+            else:
+                cap.noise.normal_()              # the draw of ``SAC.act``: same call, shape and device
+            cap.graph.replay()
+        world.surrogate.train()
+        world.simulated += T
+        world.timesteps += T
+        t = lap("steps_s", t)
+        blocks.append(cap.block.clone())
+        cap.block_host.copy_(cap.block, non_blocking=True)
+        stream.synchronize()                     # the round's one synchronisation
+        host = cap.block_host.numpy()
+        traj, actions, rewards, steps = np.split(host, np.cumsum(cap.sizes)[:-1])
+        rounds.append((traj.reshape(cap.T + 1, B, cap.N)[:T + 1].copy(), actions.reshape(cap.T, B, cap.A)[:T].copy(),
+                       rewards.reshape(cap.T, B)[:T].copy(), steps.view(np.int32).reshape(cap.T, B)[:T].copy()))
+        t = lap("copy_s", t)
+        world._reset_state()                     # the reset ``step_wait`` makes at the joint truncation
+        assert world._dev is dev and cap.valid(fused, geo), "the world changed inside the phase"
+        t = lap("reset_s", t)
+    replay, keys = _build_replay(rounds, B)
+    views = []
+    for block, (_, actions, _, _) in zip(blocks, rounds):
+        T = actions.shape[0]
+        traj, act, rew, steps = torch.split(block, cap.sizes)
+        views.append((traj.view(cap.T + 1, B, cap.N)[:T + 1], act.view(cap.T, B, cap.A)[:T], rew.view(cap.T, B)[:T],
+                      steps.view(torch.int32).view(cap.T, B)[:T]))
+    replay.device_rollout = _device_rollout(views, keys, B, device)
+    lap("build_s", t)
+    if timings is not None:
+        timings["tier"] = "kernel"
+    return replay

@@ -278,6 +278,7 @@ class WorldVecEnv(BaseWorldVecEnv):
         self.capture_reset = os.environ.get("PDECONTROL_WORLD_CAPTURE_RESET", "1") != "0"   # device path: reset = a graph replay
         self._dev = None
         self._dev_starting = None
+        self._imagination = None    # the captured closed-loop step of pdecontrol/mbrl/imagination_phase.py, kept with the world
         # spaces as seen through the replay->world transforms (stransf is their inverse)
         unbatch = lambda fn, x: np.squeeze(fn(x[np.newaxis, ...]), axis=0)
         low = unbatch(self.stransf.atransf.Inverse, action_space.low)
@@ -311,6 +312,16 @@ class WorldVecEnv(BaseWorldVecEnv):
         return self.output.outputs.detach().squeeze(1).cpu().numpy()
 
     def reset(self, **kwargs):
+        self._reset_state()
+        obs = self._dev.host_obs() if self._dev is not None else self._host_obs()
+        self._host_cache = obs
+        if kwargs.get("return_info", False):
+            return obs, {"step": self.timesteps.copy()}
+        return obs
+
+    def _reset_state(self):
+        """Everything of ``reset`` but the copy of the observations to the host: the warm-up draw and rollout, the step
+        counters.  (The imagined-rollout phase resets its device-resident rounds through this.)"""
         self.surrogate.eval()
         with torch.no_grad():
             dev = _surrogate_device(self.surrogate)
@@ -343,11 +354,6 @@ class WorldVecEnv(BaseWorldVecEnv):
         self.simulated = 0
         self.tmp = None
         self.surrogate.train()
-        obs = self._dev.host_obs() if self._dev is not None else self._host_obs()
-        self._host_cache = obs
-        if kwargs.get("return_info", False):
-            return obs, {"step": self.timesteps.copy()}
-        return obs
 
     def step_async(self, actions: Sequence[Any]) -> None:
         self.surrogate.eval()
