@@ -1,6 +1,7 @@
 /*
  * replay_hip.h -- C ABI of libreplay_hip.so: the batch gather of the controller's policy-update phase on gfx950
- * (pdecontrol/mbrl/policy_phase.py: update_policy; kernel: csrc/replay.hip).
+ * (pdecontrol/mbrl/policy_phase.py: update_policy; kernel: csrc/replay.hip).  The same library exports the append and
+ * the episode returns of the device-resident replay: include/replay/replay_slab_hip.h.
  *
  * The controller samples its SAC batches from several replays at once (imagined and real transitions), each with its own
  * connector transform.  `rp_gather` assembles one batch in ONE launch: for each of B rows of the concatenated row space it

@@ -1,5 +1,5 @@
-// replay.hip -- the fused batch gather of the policy-update phase (C ABI: include/replay_hip.h; binding:
-// pdecontrol/mbrl/replay_hip.py).
+// replay.hip -- the fused batch gather of the policy-update phase, and the append and episode returns of the
+// device-resident replay (C ABI: include/replay_hip.h and include/replay/replay_slab_hip.h; binding: pdecontrol/mbrl/replay_hip.py).
 //
 // One launch assembles one SAC batch from several packed replays.  A wave owns a sample: it reads the sample's row in the
 // concatenated row space, finds the source by comparing against the (at most RP_MAX_SOURCES) first rows -- the sources
@@ -15,7 +15,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <vector>
 
+#include "../../include/replay/replay_slab_hip.h"
 #include "../../include/replay_hip.h"
 #include "capi_error.h"
 
@@ -123,6 +125,65 @@ __global__ __launch_bounds__(NT) void rp_gather_kernel(const GatherArgs g)
     }
 }
 
+// ---- the device-resident replay: append of a rollout round, episode returns -----------------------------------------
+struct AppendArgs {
+    const float* traj;                 // [T_cap + 1][B][N]
+    const float* actions;              // [T_cap][B][A]
+    const float* rewards;              // [T_cap][B]
+    const int* steps;                  // [T_cap][B]
+    const long* dst;                   // [T][B]
+    rp_slab slab;
+    int T, B, N, A;
+    int vec_obs, vec_act;
+};
+
+__device__ __forceinline__ void place_row(const float* __restrict__ in, float* __restrict__ out, int n, bool vec, int lane)
+{
+    if (vec) {
+        for (int j = 4 * lane; j < n; j += 4 * WAVE) *reinterpret_cast<f4*>(out + j) = *reinterpret_cast<const f4*>(in + j);
+    } else {
+        for (int j = lane; j < n; j += WAVE) out[j] = in[j];
+    }
+}
+
+__global__ __launch_bounds__(NT) void rp_append_kernel(const AppendArgs a)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (w >= (long)a.T * a.B) return;
+    const long r = a.dst[w];
+    if (r < 0 || r >= a.slab.rows) return;           // negative: skipped by contract; beyond the slab: never written
+    const int t = (int)(w / a.B);
+    place_row(a.traj + w * a.N, a.slab.obs + r * a.N, a.N, a.vec_obs, lane);
+    place_row(a.traj + (w + a.B) * a.N, a.slab.nxtobs + r * a.N, a.N, a.vec_obs, lane);
+    place_row(a.actions + w * a.A, a.slab.actions + r * a.A, a.A, a.vec_act, lane);
+    if (lane == 0) {
+        a.slab.rewards[r] = a.rewards[w];
+        a.slab.steps[r] = a.steps[w];
+        a.slab.terminated[r] = 0;
+        a.slab.truncated[r] = t == a.T - 1 ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(NT) void rp_episode_returns_kernel(const float* __restrict__ rewards, long slab_rows,
+                                                                const long* __restrict__ rows, long nrows,
+                                                                const long* __restrict__ offsets, int E, float* __restrict__ returns)
+{
+    const int e = blockIdx.x * NT + threadIdx.x;
+    if (e >= E) return;
+    const long lo = offsets[e], hi = offsets[e + 1];
+    if (lo < 0 || hi < lo || hi > nrows) {
+        returns[e] = NAN;
+        return;
+    }
+    float acc = 0.0f;
+    for (long i = lo; i < hi; ++i) {
+        const long r = rows[i];
+        acc = __fadd_rn(acc, r >= 0 && r < slab_rows ? rewards[r] : NAN);
+    }
+    returns[e] = acc;
+}
+
 int obs_dim_of(const rp_source& s)
 {
     return (s.obs_width - s.sensor_start + s.sensor_stride - 1) / s.sensor_stride;
@@ -193,6 +254,55 @@ int rp_gather(void* stream, int nsrc, const rp_source* srcs, int B, const long* 
     g.total = first;
     hipLaunchKernelGGL(rp_gather_kernel, dim3((B + WAVES - 1) / WAVES), dim3(NT), 0, static_cast<hipStream_t>(stream), g);
     return launch_status(-20, "rp_gather");
+}
+
+int rp_append(void* stream, const float* block, int T, int T_cap, int B, int N, int A, const long* dst, const long* dst_host,
+              const rp_slab* slab)
+{
+    if (!block || !dst || !dst_host || !slab) return fail(-30, "rp_append: NULL block, dst, dst_host or slab");
+    if (!slab->obs || !slab->actions || !slab->nxtobs || !slab->rewards || !slab->terminated || !slab->truncated || !slab->steps)
+        return fail(-30, "rp_append: the slab has a NULL field pointer");
+    if (T < 1 || T > T_cap) return fail(-31, "rp_append: %d steps of a block laid out for %d (1 ... %d)", T, T_cap, T_cap);
+    if (B < 1) return fail(-32, "rp_append: %d envs (at least 1)", B);
+    if (N < 1 || N > RP_MAX_OBS_DIM) return fail(-33, "rp_append: observation width %d (1 ... %d are supported)", N, RP_MAX_OBS_DIM);
+    if (A < 1 || A > RP_MAX_ACT_DIM) return fail(-34, "rp_append: action width %d (1 ... %d are supported)", A, RP_MAX_ACT_DIM);
+    if (slab->rows < 1) return fail(-35, "rp_append: a slab of %ld rows (at least 1)", slab->rows);
+    const long n = (long)T * B;
+    std::vector<bool> seen(static_cast<size_t>(slab->rows), false);
+    for (long i = 0; i < n; ++i) {
+        const long r = dst_host[i];
+        if (r < 0) continue;
+        if (r >= slab->rows) return fail(-36, "rp_append: dst[%ld] = %ld is beyond the slab's %ld rows", i, r, slab->rows);
+        if (seen[r]) return fail(-37, "rp_append: row %ld is named twice (again at dst[%ld])", r, i);
+        seen[r] = true;
+    }
+    AppendArgs a = {};
+    a.traj = block;
+    a.actions = a.traj + (long)(T_cap + 1) * B * N;
+    a.rewards = a.actions + (long)T_cap * B * A;
+    a.steps = reinterpret_cast<const int*>(a.rewards + (long)T_cap * B);
+    a.dst = dst;
+    a.slab = *slab;
+    a.T = T;
+    a.B = B;
+    a.N = N;
+    a.A = A;
+    a.vec_obs = N % 4 == 0 && aligned16(a.traj) && aligned16(slab->obs) && aligned16(slab->nxtobs);
+    a.vec_act = A % 4 == 0 && aligned16(a.actions) && aligned16(slab->actions);
+    hipLaunchKernelGGL(rp_append_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(NT), 0, static_cast<hipStream_t>(stream), a);
+    return launch_status(-40, "rp_append");
+}
+
+int rp_episode_returns(void* stream, const float* rewards, long slab_rows, const long* rows, long nrows, const long* offsets,
+                       int E, float* returns)
+{
+    if (!rewards || !rows || !offsets || !returns) return fail(-50, "rp_episode_returns: NULL rewards, rows, offsets or returns");
+    if (E < 1) return fail(-51, "rp_episode_returns: %d episodes (at least 1)", E);
+    if (nrows < 1 || slab_rows < 1)
+        return fail(-52, "rp_episode_returns: %ld rows of a slab of %ld (at least 1 each)", nrows, slab_rows);
+    hipLaunchKernelGGL(rp_episode_returns_kernel, dim3((E + NT - 1) / NT), dim3(NT), 0, static_cast<hipStream_t>(stream), rewards,
+                       slab_rows, rows, nrows, offsets, E, returns);
+    return launch_status(-60, "rp_episode_returns");
 }
 
 const char* rp_last_error(void) { return g_err; }

@@ -28,7 +28,9 @@ The host-side stores of the wrapper stack are not written by the kernel tier: th
 
 ``imagine(...).device_rollout`` (kernel tier; None otherwise) keeps the phase's samples packed on the device in
 ``DeviceSubSeqStore.tensors`` order and dtypes, episodes contiguous in the replay's key order, with the ``starts`` of
-every episode.
+every episode.  With ``sink=`` (a ``DeviceExperienceReplay``, pdecontrol/mbrl/device_replay.py) the kernel tier
+writes the samples into the sink's slabs instead, one ``rp_append`` launch per round, and returns the ``StagedRollout`` that
+``sink.extend`` commits: nothing is copied back and nothing is built on the host.
 """
 import ctypes
 import time
@@ -38,6 +40,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from pdecontrol.mbrl.device_replay import DeviceExperienceReplay, episode_keys
 from pdecontrol.mbrl.policy_phase import FieldMap, Unrecognized, _flatten, field_map
 from pdecontrol.mbrl.replay import ExperienceReplay
 from pdecontrol.mbrl.worker import Worker
@@ -331,9 +334,8 @@ def _kernel_tier(agent, stack):
 def _build_replay(rounds, B):
     """(the loop's ``ExperienceReplay``, the episode keys of every round) from the rounds' host blocks: one deque per
     episode and field.  Items are what ``Sample.split`` yields: [1, N] / [1, A] fp32 rows, fp32 rewards, numpy bools,
-    int32 steps.  The keys are the ones ``ExperienceReplay.add`` hands out: an env's ``vindex`` entry is created by its
-    first sample and moved on by its truncated one, env by env, so rounds of several steps get the keys r * B + b and
-    a first round of ONE step interleaves them (0, 2, 4, ... then 1, 3, 5, ...)."""
+    int32 steps.  The keys are the ones ``ExperienceReplay.add`` hands out (``device_replay.episode_keys``): rounds of
+    several steps get the keys r * B + b and a first round of ONE step interleaves them (0, 2, 4, ... then 1, 3, 5, ...)."""
     replay = ExperienceReplay()
     stores, keys = replay._stores(), []
     for traj, actions, rewards, steps in rounds:
@@ -342,14 +344,8 @@ def _build_replay(rounds, B):
         terminated = np.zeros(T, dtype=np.bool_)
         truncated = np.zeros(T, dtype=np.bool_)
         truncated[-1] = True
-        if T > 1:                                        # the first step's ``add`` touches every env before any moves on
-            for b in range(B):
-                replay.vindex[b]
-        keys.append([])
-        for b in range(B):
-            key = replay.vindex[b]
-            replay.vindex[b] = replay._next_episode_id()
-            keys[-1].append(key)
+        keys.append(episode_keys(replay.vindex, B, T))
+        for b, key in enumerate(keys[-1]):
             for store, column in zip(stores, (obs[:, b], act[:, b], nxt[:, b], rewards[:, b], terminated, truncated,
                                               steps[:, b])):
                 store[key] = deque(column)
@@ -375,7 +371,18 @@ def _device_rollout(blocks, keys, B, device):
     return DeviceRollout([torch.cat(c) for c in cols], starts, device)
 
 
-def imagine(agent, stack, num_rollouts, deterministic=False, timings=None, noise=None):
+class _SinkBuffers:
+    """Per-round staging of a phase that writes into a sink: without a synchronisation per round every round needs pinned
+    host memory of its own for the ints and the destination rows it uploads."""
+
+    def __init__(self, cap, num_rounds):
+        self.num_rounds = num_rounds
+        self.ints_host = torch.zeros((num_rounds, cap.ints.numel()), dtype=torch.int32).pin_memory()
+        self.dst_host = torch.zeros((num_rounds, cap.T * cap.B), dtype=torch.int64).pin_memory()
+        self.dst = torch.zeros(cap.T * cap.B, dtype=torch.int64, device=cap.ints.device)
+
+
+def imagine(agent, stack, num_rollouts, deterministic=False, timings=None, noise=None, sink=None):
     """The ``ExperienceReplay`` ``Worker(stack).rollout(agent, lambda ts, eps: eps >= num_rollouts, deterministic)`` returns
     on a fresh worker (module docstring).  ``deterministic`` is passed to the loop's ``agent.select_action``, which accepts
     and ignores it as the reference's does; the kernel tier therefore samples and draws its noise whatever it says.
@@ -383,7 +390,15 @@ def imagine(agent, stack, num_rollouts, deterministic=False, timings=None, noise
     the host seconds of the resets, the steps, the copies back and the replay build, and the tier that ran; on the kernel
     tier each of the four then ends in a device synchronisation, which the phase otherwise does once per round.
     ``noise`` (tests; kernel tier only, like the ``noise`` of ``SAC.update``) is an optional iterable of standard-normal
-    tensors [num_envs, achannels, aheight], one per step, used in place of the draws."""
+    tensors [num_envs, achannels, aheight], one per step, used in place of the draws.
+    ``sink`` (a ``DeviceExperienceReplay`` on the agent's device): on the kernel tier the samples are placed into the
+    sink's slabs by one ``rp_append`` launch per round, reading the round's block in place -- no clone, no copy to the
+    host, no deques, one synchronisation at the end of the phase -- and the call returns the ``StagedRollout`` that
+    ``sink.extend`` commits (``sink.discard`` frees); ``timings`` then receives ``append_s`` in place of ``copy_s`` and
+    ``build_s``.  On the loop tier the host replay is returned as without a sink and ``sink.extend`` uploads it.
+    Generators, the world's end state and ``simulated`` / ``timesteps`` do not depend on ``sink``."""
+    if sink is not None and not isinstance(sink, DeviceExperienceReplay):
+        raise TypeError(f"sink is a {type(sink).__name__}, not a DeviceExperienceReplay")
     geo, fused = (None, None) if num_rollouts <= 0 else _kernel_tier(agent, stack)
     if geo is None:
         if noise is not None:
@@ -419,42 +434,76 @@ def imagine(agent, stack, num_rollouts, deterministic=False, timings=None, noise
     rounds, blocks = [], []
     stored = None if noise is None else iter(noise)
     num_rounds = -(-int(num_rollouts) // B)
-    t = lap("reset_s", t)
-    for _ in range(num_rounds):
-        T = round_length(world.timesteps, world.horizon, world.max_episode_steps)
-        ints = cap.ints_host.numpy()
-        if elite is not None:                    # the draw of every step of the round, in the loop's order
-            for s in range(T):
-                ints[s * B:(s + 1) * B] = np.random.choice(elite, size=B)
-        ints[cap.T * B:] = world.timesteps
-        cap.ints.copy_(cap.ints_host, non_blocking=True)
-        state = dev.state.view(B, cap.N)
-        cap.traj[0].copy_(state)
-        cap.policy_obs.view(B, O).copy_(state[:, start::stride][:, :O])
-        cap.step.zero_()
-        world.surrogate.eval()
+    staged = buffers = None
+    if sink is not None:
+        from pdecontrol.mbrl import replay_hip
+        import hipbind
+        replay_hip.load()
+        if sink.device != torch.empty(0, device=device).device:
+            raise ValueError(f"the sink lives on {sink.device}, the imagined rollouts on {device}")
+        staged = sink.stage(B, cap.N, cap.A, expect=num_rounds * B * cap.T)
+        buffers = getattr(cap, "sink_buffers", None)
+        if buffers is None or buffers.num_rounds < num_rounds:
+            buffers = cap.sink_buffers = _SinkBuffers(cap, num_rounds)
+    try:
         t = lap("reset_s", t)
-        for _s in range(T):
-            if stored is not None:
-                cap.noise.copy_(next(stored).reshape(cap.noise.shape), non_blocking=True)
-            else:
-                cap.noise.normal_()              # the draw of ``SAC.act``: same call, shape and device
-            cap.graph.replay()
-        world.surrogate.train()
-        world.simulated += T
-        world.timesteps += T
-        t = lap("steps_s", t)
-        blocks.append(cap.block.clone())
-        cap.block_host.copy_(cap.block, non_blocking=True)
-        stream.synchronize()                     # the round's one synchronisation
-        host = cap.block_host.numpy()
-        traj, actions, rewards, steps = np.split(host, np.cumsum(cap.sizes)[:-1])
-        rounds.append((traj.reshape(cap.T + 1, B, cap.N)[:T + 1].copy(), actions.reshape(cap.T, B, cap.A)[:T].copy(),
-                       rewards.reshape(cap.T, B)[:T].copy(), steps.view(np.int32).reshape(cap.T, B)[:T].copy()))
-        t = lap("copy_s", t)
-        world._reset_state()                     # the reset ``step_wait`` makes at the joint truncation
-        assert world._dev is dev and cap.valid(fused, geo), "the world changed inside the phase"
-        t = lap("reset_s", t)
+        for r in range(num_rounds):
+            T = round_length(world.timesteps, world.horizon, world.max_episode_steps)
+            ints_host = cap.ints_host if staged is None else buffers.ints_host[r]
+            ints = ints_host.numpy()
+            if elite is not None:                    # the draw of every step of the round, in the loop's order
+                for s in range(T):
+                    ints[s * B:(s + 1) * B] = np.random.choice(elite, size=B)
+            ints[cap.T * B:] = world.timesteps
+            cap.ints.copy_(ints_host, non_blocking=True)
+            if staged is not None:                   # the rows of this round's samples, uploaded with its ints
+                dst_host = buffers.dst_host[r, :T * B]
+                dst_host.copy_(torch.from_numpy(staged.reserve(T).reshape(-1)))
+                buffers.dst[:T * B].copy_(dst_host, non_blocking=True)
+            state = dev.state.view(B, cap.N)
+            cap.traj[0].copy_(state)
+            cap.policy_obs.view(B, O).copy_(state[:, start::stride][:, :O])
+            cap.step.zero_()
+            world.surrogate.eval()
+            t = lap("reset_s", t)
+            for _s in range(T):
+                if stored is not None:
+                    cap.noise.copy_(next(stored).reshape(cap.noise.shape), non_blocking=True)
+                else:
+                    cap.noise.normal_()              # the draw of ``SAC.act``: same call, shape and device
+                cap.graph.replay()
+            world.surrogate.train()
+            world.simulated += T
+            world.timesteps += T
+            t = lap("steps_s", t)
+            if staged is not None:
+                replay_hip.append(hipbind.stream(), cap.block.data_ptr(), T, cap.T, B, cap.N, cap.A, buffers.dst.data_ptr(),
+                                  dst_host.numpy(), sink.slab())
+                t = lap("append_s", t)
+                world._reset_state()                 # the reset ``step_wait`` makes at the joint truncation
+                assert world._dev is dev and cap.valid(fused, geo), "the world changed inside the phase"
+                t = lap("reset_s", t)
+                continue
+            blocks.append(cap.block.clone())
+            cap.block_host.copy_(cap.block, non_blocking=True)
+            stream.synchronize()                     # the round's one synchronisation
+            host = cap.block_host.numpy()
+            traj, actions, rewards, steps = np.split(host, np.cumsum(cap.sizes)[:-1])
+            rounds.append((traj.reshape(cap.T + 1, B, cap.N)[:T + 1].copy(), actions.reshape(cap.T, B, cap.A)[:T].copy(),
+                           rewards.reshape(cap.T, B)[:T].copy(), steps.view(np.int32).reshape(cap.T, B)[:T].copy()))
+            t = lap("copy_s", t)
+            world._reset_state()                     # the reset ``step_wait`` makes at the joint truncation
+            assert world._dev is dev and cap.valid(fused, geo), "the world changed inside the phase"
+            t = lap("reset_s", t)
+    except BaseException:
+        if staged is not None:
+            sink.discard(staged)             # a phase that did not finish leaves no rows behind
+        raise
+    if staged is not None:
+        stream.synchronize()                     # the phase's one synchronisation: the pinned staging may be reused
+        if timings is not None:
+            timings["tier"] = "kernel"
+        return staged
     replay, keys = _build_replay(rounds, B)
     views = []
     for block, (_, actions, _, _) in zip(blocks, rounds):

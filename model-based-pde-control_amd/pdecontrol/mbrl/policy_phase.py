@@ -39,6 +39,16 @@ from pdegym.common import transforms as tr
 # ----------------------------------------------------------------------------------------------------------------------
 # 1. the index plan
 # ----------------------------------------------------------------------------------------------------------------------
+def _is_view(dataset):
+    """A ``DeviceReplayView``: a dataset whose samples already lie in device slabs."""
+    return hasattr(dataset, "physical_rows")
+
+
+def _store(dataset, device):
+    """The tensors the batches of ``dataset`` are gathered from: one pack of its replay, or a view's slabs as they stand."""
+    return dataset.slab_store(device) if _is_view(dataset) else DeviceSubSeqStore(dataset.fields, device)
+
+
 class PolicyBatchPlan:
     """The U x B samples the reference loader draws from ``ConcatDataset(datasets)``, in its order.
 
@@ -47,6 +57,9 @@ class PolicyBatchPlan:
     ``rows``   [U, B]   its row in that dataset's packed replay (``DeviceSubSeqStore`` order: episodes in key order)
     ``concat_rows``     its row in the concatenation of the packed replays (``first[source] + rows``)
     ``totals``          rows of each packed replay
+
+    A ``DeviceReplayView`` (pdecontrol/mbrl/device_replay.py) among the datasets is a source that is not packed: its
+    ``rows`` are physical rows of the replay's slab and its entry of ``totals`` is the slab's rows.
 
     Construction consumes from torch's global CPU generator exactly what the loader consumes: the ``DataLoader`` iterator's
     base seed, then ``RandomSampler``'s seed; the indices come from a private generator seeded with the latter, in
@@ -75,6 +88,12 @@ class PolicyBatchPlan:
         rows = np.empty_like(idx)
         self.totals = []
         for s, d in enumerate(self.datasets):
+            if _is_view(d):                   # a device-resident replay: the source is the slab, rows are physical
+                self.totals.append(int(d.slab_rows))
+                sel = source == s
+                if sel.any():
+                    rows[sel] = d.physical_rows(local[sel])
+                continue
             keys = list(d.fields[0].keys())
             lengths = np.fromiter((len(d.fields[0][k]) for k in keys), dtype=np.int64, count=len(keys))
             starts = dict(zip(keys, np.concatenate(([0], np.cumsum(lengths)[:-1])) if keys else ()))
@@ -212,6 +231,8 @@ def recognize(stransf, obs_width, act_width):
 
 def _widths(dataset):
     """(channels, columns) of the stored observations and actions of a dataset's replay."""
+    if _is_view(dataset):
+        return dataset.widths()
     out = []
     for store in dataset.fields[:2]:
         shape = np.shape(next(iter(store.values()))[0])
@@ -262,7 +283,7 @@ def _transform_items(stransf, sample):
 def host_batches(plan, stores=None):
     """The loader's batches (lists of seven CPU tensors, ``default_collate``'s layout) from the replays packed on the
     host: per source and field one ``index_select``, the connector applied to the gathered block."""
-    stores = stores or [DeviceSubSeqStore(d.fields, "cpu") for d in plan.datasets]
+    stores = stores or [_store(d, "cpu") for d in plan.datasets]
     whole = []
     for d in plan.datasets:
         try:
@@ -307,7 +328,7 @@ class _KernelTier:
 
     def __init__(self, plan, connectors, device):
         from pdecontrol.mbrl import replay_hip
-        self.stores = [DeviceSubSeqStore(d.fields, device) for d in plan.datasets]    # one pack per source per phase
+        self.stores = [_store(d, device) for d in plan.datasets]       # one pack per source per phase; a view: no pack
         self.coefs, entries = [], []
         for store, con in zip(self.stores, connectors):
             obs, actions, nxtobs, rewards, terminated = store.tensors[:5]
@@ -377,7 +398,7 @@ def update_policy(agent, datasets, batch_size, num_updates, timings=None):
     if plan.num_updates == 0:
         return 0
     if not cuda:
-        stores = [DeviceSubSeqStore(d.fields, "cpu") for d in plan.datasets]
+        stores = [_store(d, "cpu") for d in plan.datasets]
         t = lap("pack_s", t)
         for batch in host_batches(plan, stores):
             agent.update(batch)
@@ -387,7 +408,7 @@ def update_policy(agent, datasets, batch_size, num_updates, timings=None):
         return plan.num_updates
     tier, fused = _kernel_tier(agent, plan)
     if tier is None:
-        stores = [DeviceSubSeqStore(d.fields, agent.device) for d in plan.datasets]
+        stores = [_store(d, agent.device) for d in plan.datasets]
         t = lap("pack_s", t)
         for batch in device_batches(plan, stores):
             agent.update(batch)

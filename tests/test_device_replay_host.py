@@ -1,0 +1,337 @@
+"""The device-resident replay without a GPU (pdecontrol/mbrl/device_replay.py with ``device="cpu"``): metadata and contents
+against ``ExperienceReplay`` call for call, the allocator (holes, split episodes, growth, discard), the dataset view against
+``SubSeqDataset`` in the policy-update phase, ``statistics`` bit for bit, and the host-side refusals of the two entries of
+include/replay/replay_slab_hip.h.  Rollout rounds and the numpy twin of ``rp_append``: tests/_device_replay_scenario.py."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import _device_replay_scenario as sc
+import _policy_phase_scenario as pp_sc
+import _sac_models as sm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "model-based-pde-control_amd", "lib", "libreplay_hip.so")
+
+
+def _pair(capacity=None, **kwargs):
+    from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
+    from pdecontrol.mbrl.replay import ExperienceReplay
+    return ExperienceReplay(capacity), DeviceExperienceReplay(capacity, device="cpu", **kwargs)
+
+
+def _phase(host, sink, rs, B, lengths, what):
+    """One ``imagine -> extend`` on both routes, compared after every call."""
+    rounds = sc.make_rounds(rs, B, lengths)
+    rollout = sc.host_rollout(rounds, B)
+    staged = sc.stage(sink, rounds, B)
+    assert (staged.episodes, staged.nepisodes, staged.ntimesteps) == (rollout.episodes, rollout.nepisodes, rollout.ntimesteps)
+    assert len(staged.vindex) == len(rollout.vindex) == B
+    before = sink.to_host()
+    sc.same_replay(staged.to_host(), rollout, f"{what}: the staged rollout")
+    sc.same_replay(sink.to_host(), before, f"{what}: staged rows are invisible")
+    host.extend(rollout)
+    sink.extend(staged)
+    sc.same_replay(sink.to_host(), host, f"{what}: after extend")
+    assert (sink.episodes, sink.nepisodes, sink.ntimesteps, sink.stopped, sink.nstopped) == \
+        (host.episodes, host.nepisodes, host.ntimesteps, host.stopped, host.nstopped)
+    return staged
+
+
+def _resize(host, sink, size, what):
+    host.resize(size)
+    sink.resize(size)
+    sc.same_replay(sink.to_host(), host, f"{what}: after resize({size})")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# metadata and contents against ExperienceReplay
+# ---------------------------------------------------------------------------------------------------------------------
+def test_scenario_equals_the_host_replay_call_for_call():
+    """Capacity 40, five phases of 3 envs x 3 rounds with horizons 2, 2, 3, 3, 3: eviction by smallest key opens holes in
+    the middle of the slab, the orders interleave and the episode length changes; the slab grows once on the way."""
+    host, sink = _pair(sc.CAPACITY)
+    rs = np.random.RandomState(0)
+    sizes = []
+    for i, horizon in enumerate(sc.HORIZONS):
+        _resize(host, sink, sc.CAPACITY, f"phase {i}")
+        _phase(host, sink, rs, sc.ENVS, [horizon] * sc.ROUNDS, f"phase {i}")
+        assert sink.episodes == sc.ORDERS[i] and sink.ntimesteps == sc.NTIMESTEPS[i], (i, sink.episodes, sink.ntimesteps)
+        sizes.append(sink.rows)
+    assert sizes[0] == sc.CAPACITY + sc.ENVS * sc.HORIZONS[0], "capacity plus the first reservation"
+    assert sizes[-1] > sizes[0], "36 live + 27 staged rows exceed the first slab: it grew, and kept its rows (compared above)"
+    assert sink._free.total + sink.ntimesteps == sink.rows and sink._staged == 0
+
+
+def test_small_capacity_zero_capacity_and_a_first_round_of_one_step():
+    host, sink = _pair(5)                                      # smaller than one phase of 18 rows
+    rs = np.random.RandomState(1)
+    _phase(host, sink, rs, 3, [1, 3, 3], "one-step first round")
+    assert host.ntimesteps <= 5 and sink._free.total == sink.rows - sink.ntimesteps
+    _resize(host, sink, 0, "empty")
+    assert sink.episodes == [] and sink.ntimesteps == 0 and sink._free.total == sink.rows
+    _resize(host, sink, 30, "again")
+    staged = _phase(host, sink, rs, 3, [1, 2], "after emptying")
+    assert sorted(staged.episodes) != staged.episodes, "a first round of one step interleaves the keys"
+    host, sink = _pair()
+    staged = _phase(host, sink, np.random.RandomState(2), 3, [1, 2, 2], "unbounded")
+    assert staged.episodes == sink.episodes == [0, 2, 4, 1, 3, 5, 6, 7, 8] and sink.capacity == np.inf
+
+
+def test_an_episode_splits_across_extents_where_the_holes_are_small():
+    host, sink = _pair(12, rows=16)
+    rs = np.random.RandomState(3)
+    _phase(host, sink, rs, 3, [1, 2], "A")                     # 9 rows: episodes of 1 and 2 steps, keys interleaved
+    _phase(host, sink, rs, 3, [2], "B")                        # 15 rows > 12: the keys 0 and 1 leave rows 0 and 5, 6
+    _resize(host, sink, 10, "C")                               # the key 2 leaves rows 3, 4
+    assert (sink._free.starts, sink._free.lengths) == ([0, 3, 15], [1, 4, 1])
+    _resize(host, sink, 40, "C")
+    staged = _phase(host, sink, rs, 2, [3], "C")               # two episodes of 3 rows into holes of 1, 4 and 1
+    assert [sink._eps[k].extents for k in sink.episodes[-2:]] == [[(0, 1), (3, 2)], [(5, 2), (15, 1)]]
+    assert sink.rows == 16, "free rows >= needed is sufficient: nothing grew, nothing was compacted"
+    assert staged.state == "committed"
+    rows = sink.dataset().physical_rows(np.arange(sink.ntimesteps))
+    assert len(set(rows.tolist())) == sink.ntimesteps and rows[-6:].tolist() == [0, 3, 4, 5, 6, 15]
+
+
+def test_discard_frees_the_staged_rows():
+    host, sink = _pair(40)
+    rs = np.random.RandomState(4)
+    _phase(host, sink, rs, 3, [2, 2], "A")
+    free, version = sink._free.total, sink._version
+    staged = sc.stage(sink, sc.make_rounds(rs, 3, [3, 3]), 3)
+    assert sink._free.total == free - 18 and sink._staged == 18 and sink.ntimesteps == 12
+    sink.discard(staged)
+    assert sink._free.total == free and sink._staged == 0 and sink._version == version and staged.state == "discarded"
+    sc.same_replay(sink.to_host(), host, "after discard")
+    with pytest.raises(ValueError):
+        sink.extend(staged)
+    with pytest.raises(ValueError):
+        sink.discard(staged)
+    _phase(host, sink, rs, 3, [3], "B")
+
+
+def test_extend_takes_a_host_replay_like_a_staged_rollout():
+    from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
+    host, sink = _pair(30)
+    other = DeviceExperienceReplay(30, device="cpu")
+    rs = np.random.RandomState(5)
+    for lengths in ([1, 2, 2], [3, 3], [2]):
+        rounds = sc.make_rounds(rs, 3, lengths)
+        host.extend(sc.host_rollout(rounds, 3))
+        sink.extend(sc.stage(sink, rounds, 3))
+        other.extend(sc.host_rollout(rounds, 3))
+        sc.same_replay(other.to_host(), host, "extend(host replay)")
+        sc.same_replay(other.to_host(), sink.to_host(), "extend(host replay) against extend(staged)")
+    # a ragged host replay with an episode still open: appended to, and vindex stays
+    ragged = pp_sc.scripted_replay(8, 4, 9, 7, {0: (4,), 1: (), 2: (2, 5)})
+    host, sink = _pair()
+    for _ in range(2):
+        host.extend(ragged)
+        sink.extend(ragged)
+        sc.same_replay(sink.to_host(), host, "ragged")
+    assert any(len(ep.extents) > 1 for ep in sink._eps.values()), "an open episode was appended to"
+
+
+def test_add_is_refused_with_the_reason():
+    _, sink = _pair()
+    with pytest.raises(NotImplementedError, match="extend"):
+        sink.add([])
+
+
+def test_sample_equals_the_host_replays():
+    host, sink = _pair(40)
+    _phase(host, sink, np.random.RandomState(6), 3, [2, 3], "A")
+    for key in host.episodes:
+        for a, b in zip(sink.sample(key), host.sample(key)):
+            assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
+    np.random.seed(3)
+    a = sink.sample()
+    np.random.seed(3)
+    b = host.sample()
+    assert torch.equal(a.obs, b.obs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# statistics
+# ---------------------------------------------------------------------------------------------------------------------
+def test_statistics_equal_the_host_replays_bit_for_bit():
+    host, sink = sc.stats_pair()
+    want, got = host.statistics(), sink.statistics()
+    for w, g in zip(want, got):
+        assert type(w) is type(g) is np.float32 and w.tobytes() == g.tobytes(), (want, got)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the view in the policy-update phase
+# ---------------------------------------------------------------------------------------------------------------------
+def _datasets(seed=0, device="cpu", obs_dim=8, scale=1):
+    """([host imagined dataset, real], [view, real]) over replays that went through the same extend and resize calls."""
+    from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
+    from pdecontrol.mbrl.replay import ExperienceReplay
+    from pdecontrol.surrogates.common.dataset import SubSeqDataset
+    world = pp_sc.scripted_replay(obs_dim, 4, seed + 1, 21 * scale, {0: (4, 11, 30), 1: (9,), 2: (15, 16)})
+    real_replay = pp_sc.scripted_replay(obs_dim, 4, seed + 2, 14 * scale, {0: (5, 12), 1: (8,)})
+    to_agent_world, to_agent = pp_sc.controller_connectors(4, 1, False, obs_dim, seed=seed)
+    real = SubSeqDataset(data=real_replay.data, length=1, stride=1, bootstrapping=False, stransf=to_agent)
+    host, sink = ExperienceReplay(), DeviceExperienceReplay(device=device)
+    for r in (host, sink):
+        r.extend(world)
+        r.resize(r.ntimesteps - 12)          # the oldest episodes leave: physical rows are no longer item indices
+        r.extend(world)
+    make = lambda: SubSeqDataset(data=host.data, length=1, stride=1, bootstrapping=False, stransf=to_agent_world)
+    return make, (lambda: sink.dataset(to_agent_world)), real, host, sink
+
+
+def test_view_stands_where_the_subseq_dataset_stands():
+    make, view_of, real, host, sink = _datasets()
+    np.random.seed(11)
+    dataset = make()
+    want_state = np.random.get_state()
+    np.random.seed(11)
+    view = view_of()
+    got_state = np.random.get_state()
+    assert want_state[0] == got_state[0] and np.array_equal(want_state[1], got_state[1]) and want_state[2:] == got_state[2:]
+    assert len(view) == len(dataset) == host.ntimesteps and view.length == 1
+    assert type(len(view)) is type(len(dataset))
+    rows = view.physical_rows(np.arange(len(view)))
+    assert not np.array_equal(rows, np.arange(len(view))), "the scenario is meant to leave holes"
+    for i in range(len(dataset)):
+        for name, a, b in zip(pp_sc.FIELDS, view[i], dataset[i]):
+            assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (i, name)
+    sink.resize(3)
+    with pytest.raises(RuntimeError, match="changed"):
+        view.physical_rows([0])
+
+
+@pytest.mark.parametrize("B,U", [(1, 3), (33, 4)])
+def test_plan_and_host_batches_over_the_view_equal_those_over_the_dataset(B, U):
+    from pdecontrol.mbrl import policy_phase as pp
+    make, view_of, real, host, sink = _datasets(seed=2)
+    torch.manual_seed(5)
+    want_plan = pp.PolicyBatchPlan([make(), real], B, U)
+    want_state = torch.get_rng_state()
+    want = list(pp.host_batches(want_plan))
+    torch.manual_seed(5)
+    plan = pp.PolicyBatchPlan([view_of(), real], B, U)
+    assert torch.equal(torch.get_rng_state(), want_state)
+    assert np.array_equal(plan.source, want_plan.source) and np.array_equal(plan.local, want_plan.local)
+    assert plan.totals == [sink.rows, want_plan.totals[1]], "the source is the slab as it stands"
+    sel = plan.source == 0
+    assert (plan.rows[sel] < sink.rows).all() and np.array_equal(plan.rows[~sel], want_plan.rows[~sel])
+    got = list(pp.host_batches(plan))
+    assert len(got) == len(want) == U
+    for u, (g, w) in enumerate(zip(got, want)):
+        pp_sc.same_batch(g, w, f"update {u}")
+    if B * U >= 32:
+        assert set(np.unique(plan.source)) == {0, 1}
+
+
+def test_cpu_policy_phase_over_the_view_equals_the_one_over_the_datasets():
+    from pdecontrol.mbrl import policy_phase as pp
+    make, view_of, real, host, sink = _datasets(seed=3)
+    B, U = 33, 4
+    out = []
+    for first in (make, view_of):
+        agent = sm.build(32, auto=True, interval=2, obs_dim=8, act_dim=4, seed=5, low=-2.0, high=1.0)
+        torch.manual_seed(11)
+        np.random.seed(12)
+        timings = {}
+        assert pp.update_policy(agent, [first(), real], B, U, timings=timings) == U
+        assert timings["tier"] == "cpu"
+        state = sm.full_state(agent)
+        state["rng"] = torch.get_rng_state()
+        state["numpy"] = torch.from_numpy(np.random.get_state()[1].astype(np.int64))
+        out.append(state)
+    assert set(out[0]) == set(out[1])
+    for k in out[0]:
+        assert torch.equal(out[0][k], out[1][k]), k
+
+
+def test_imagine_with_a_sink_on_the_loop_tier_returns_the_host_replay():
+    import _rollout_scenario as ro
+    from pdecontrol.mbrl import imagination_phase as ip
+    from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
+    from pdecontrol.mbrl.replay import ExperienceReplay
+    replays = []
+    for with_sink in (False, True):
+        s = ro.build(ro.repo_namespace(), "cpu")
+        s.world.setup(s.starting)
+        ro.seed()
+        sink = DeviceExperienceReplay(10, device="cpu") if with_sink else None
+        timings = {}
+        replay = ip.imagine(s.agent, s.stack, ro.NUM_ROLLOUTS, timings=timings, sink=sink) if with_sink else \
+            ip.imagine(s.agent, s.stack, ro.NUM_ROLLOUTS, timings=timings)
+        assert type(replay) is ExperienceReplay and timings["tier"] == "loop"
+        replays.append((replay, torch.get_rng_state(), np.random.get_state()[1].copy()))
+    (plain, t0, n0), (sunk, t1, n1) = replays
+    sc.same_replay(sunk, plain, "loop tier with a sink")
+    assert torch.equal(t0, t1) and np.array_equal(n0, n1)
+    host = ExperienceReplay(10)
+    host.extend(plain)
+    sink.extend(sunk)
+    sc.same_replay(sink.to_host(), host, "the sink takes the host replay")
+    with pytest.raises(TypeError):
+        ip.imagine(s.agent, s.stack, 1, sink=host)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# header, binding and the host-side refusals
+# ---------------------------------------------------------------------------------------------------------------------
+def test_slab_header_binding_and_library_agree():
+    """The second header of libreplay_hip.so lives in include/replay/ ; its functions are the binding's second table and the
+    library's exports, and its struct is the binding's."""
+    from pdecontrol.mbrl import replay_hip
+    text = open(os.path.join(ROOT, "include", "replay", "replay_slab_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    names = sorted(set(re.findall(r"\b(rp_[a-z0-9_]+)\s*\(", text)))
+    assert names == ["rp_append", "rp_episode_returns"] == sorted(n for n, _, _ in replay_hip.SLAB_SYMBOLS)
+    fields = re.search(r"typedef struct rp_slab \{(.*?)\} rp_slab;", text, re.S).group(1)
+    declared = [n for decl in fields.split(";") for n in re.findall(r"\*?\s*([a-z_]+)\s*(?:,|$)", decl.strip())]
+    assert declared == [n for n, _ in replay_hip.Slab._fields_]
+    if not os.path.exists(LIB):
+        pytest.skip("libreplay_hip.so not built (run __graft_entry__.build())")
+    handle = ctypes.CDLL(LIB)
+    assert not [n for n in names if not hasattr(handle, n)]
+
+
+def test_append_and_episode_returns_refuse_before_any_device_call():
+    if not os.path.exists(LIB):
+        pytest.skip("libreplay_hip.so not built (run __graft_entry__.build())")
+    from pdecontrol.mbrl import replay_hip
+    lib = replay_hip.load()
+    p = ctypes.c_void_p(4096)                   # never dereferenced: every call below is refused on the host
+    T, B = 2, 3
+    good_dst = np.arange(T * B, dtype=np.int64)
+
+    def slab(rows=6, **null):
+        fields = {n: (None if n in null else p) for n, _ in replay_hip.Slab._fields_[:7]}
+        return replay_hip.Slab(rows=rows, **fields)
+
+    def append(block=p, T=T, T_cap=5, B=B, N=64, A=4, dst=p, dst_host=good_dst, slab_=None, null_slab=False):
+        host = None if dst_host is None else dst_host.ctypes.data
+        s = slab() if slab_ is None else slab_
+        return lib.rp_append(None, block, T, T_cap, B, N, A, dst, host, None if null_slab else ctypes.byref(s))
+
+    cases = [(-30, dict(block=None)), (-30, dict(dst=None)), (-30, dict(dst_host=None)), (-30, dict(null_slab=True)),
+             (-30, dict(slab_=slab(truncated=True))), (-30, dict(slab_=slab(obs=True))),
+             (-31, dict(T=0)), (-31, dict(T=6)), (-32, dict(B=0)), (-33, dict(N=0)), (-33, dict(N=replay_hip.MAX_OBS_DIM + 1)),
+             (-34, dict(A=0)), (-34, dict(A=replay_hip.MAX_ACT_DIM + 1)), (-35, dict(slab_=slab(rows=0))),
+             (-36, dict(dst_host=np.asarray([0, 1, 2, 3, 4, 6], dtype=np.int64))),
+             (-36, dict(slab_=slab(rows=5))),
+             (-37, dict(dst_host=np.asarray([0, 1, 2, 3, -1, 2], dtype=np.int64)))]
+    for code, change in cases:
+        assert append(**change) == code, (code, change, replay_hip.last_error())
+        assert replay_hip.last_error().startswith("rp_append:"), replay_hip.last_error()
+    assert "dst[5] = 6" in (append(dst_host=np.asarray([0, 1, 2, 3, 4, 6], dtype=np.int64)), replay_hip.last_error())[1]
+
+    returns = lambda rewards=p, slab_rows=6, rows=p, nrows=6, offsets=p, E=2, out=p: \
+        lib.rp_episode_returns(None, rewards, slab_rows, rows, nrows, offsets, E, out)
+    for code, change in [(-50, dict(rewards=None)), (-50, dict(rows=None)), (-50, dict(offsets=None)), (-50, dict(out=None)),
+                         (-51, dict(E=0)), (-52, dict(nrows=0)), (-52, dict(slab_rows=0))]:
+        assert returns(**change) == code, (code, change)
+        assert replay_hip.last_error().startswith("rp_episode_returns:"), replay_hip.last_error()
