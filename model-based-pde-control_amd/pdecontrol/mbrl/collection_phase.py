@@ -1,0 +1,511 @@
+"""The controller's real-env collection phases (reference ``pdecontrol/mbrl/mbrl.py:397-449``: ``worker.rollout(agent,
+sampling)`` and ``eval_worker.rollout(agent, eval_stop)``) behind one call.
+
+``Worker.rollout`` crosses the host four times per step: ``select_action`` (H2D, launch, D2H), the action wrappers in
+numpy, the KS step (H2D, launch, D2H of the ``[E, 1, N]`` block, a synchronisation), the observation wrappers in numpy (a
+running min / max over the whole block, then an affine map), and ``Sample.split`` + ``ExperienceReplay.add`` (seven
+appends per env) under a stop test that re-counts every deque.  ``collect(worker, agent, stop)`` returns the
+``ExperienceReplay`` ``worker.rollout(agent, stop)`` returns, on one of two tiers (chosen per call, announced once per
+reason; the result carries ``tier``, ``tier_reason`` and ``host_steps``):
+
+loop tier     ``Worker.rollout`` itself: CPU agents and agents that are not a ``SAC``, ``PDECONTROL_FUSED=0``, a SAC
+              geometry the fused kernels refuse, the CPU twin and ``KSShardedVecEnv``, an env on another device than the
+              agent, any stack ``recognize_real_stack`` does not reduce to the controller's.
+kernel tier   truncation is the only way an episode ends, so ``plan_phase`` knows from host integers alone how many steps
+              the phase takes, at which of them an env truncates, and every sample's ``steps``, calling ``stop`` exactly
+              as the loop does.  The plan is cut into segments of consecutive steps without a truncation (and under
+              ``SEGMENT_BYTES``).  Inside a segment a step is, eagerly on torch's current stream and with no host
+              synchronisation,
+                  noise.normal_() -> sac_policy_forward -> co_act -> ks_step_device -> co_observe
+              (csrc/collect.hip): the stepper writes its observations straight into the segment's trajectory block.  One
+              D2H copy and one synchronisation per segment bring the block back; rewards are formed on the host from the
+              fp64 sums with ``KSBatchedVecEnv._finish_step``'s expression and the replay is built with one deque per
+              episode and field.  A step at which an env truncates is one ordinary host step of the stack between two
+              segments, on the state just written back: the autoreset and the final-observation quirks of
+              ``TransformObsWrapper`` are the stack's own.
+
+In both tiers everything the loop mutates ends where the loop leaves it: the worker's two observations, the stores, the
+scaling's bounds, ``env.timestep``, the stepper's state, the env's MT19937 streams, numpy's and torch's generators, and
+the calls to ``callback.on_rollout_end``.  The worker is not reset between calls: consecutive ``collect`` calls continue
+the running episodes as consecutive ``rollout`` calls do.
+"""
+import gc
+from collections import deque
+from dataclasses import dataclass
+from itertools import chain
+from typing import Any, List, Optional
+
+import ctypes
+
+import numpy as np
+import torch
+
+from pdecontrol.mbrl.imagination_phase import _is_forcing, _updates_statistics
+from pdecontrol.mbrl.policy_phase import FieldMap, Unrecognized, _flatten, field_map
+from pdecontrol.mbrl.replay import ExperienceReplay
+from pdecontrol.mbrl.types import Sample
+from pdecontrol.mbrl.worker import _stored
+from pdecontrol.surrogates import ops
+from pdegym.common import transforms as tr
+from pdegym.common import vec_wrappers as vw
+
+#: byte budget of one segment's trajectory block (an evaluation phase is 400 steps of 4 MB at 4096 x 256)
+SEGMENT_BYTES = 256 << 20
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 1. stack recognition
+# ----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class RealStackGeometry:
+    """What a recognised real-env stack does between the agent and the KS stepper.
+
+    ``env``         the ``KSBatchedVecEnv`` at the bottom
+    ``action``      the scaling of the agent's action columns (identity sensor; ``coef`` None: identity)
+    ``record_raw``  the action store sits on top of the scaling: it holds the raw action, else the env-side one
+    ``scaling``     the observation ``ScaleTransform`` (scalar bounds) or None
+    ``update``      1 when a step joins the block's extrema with the scaling's running bounds first
+    ``agent_obs``   the agent sensor over the state columns
+    """
+    env: Any
+    action: FieldMap
+    record_raw: bool
+    scaling: Optional[tr.ScaleTransform]
+    update: int
+    agent_obs: FieldMap
+
+
+def _bare_scale(t):
+    """The ``ScaleTransform`` a wrapper's transform IS (its ``update`` then runs the scalar numpy path), else None."""
+    return t if type(t) is tr.ScaleTransform else None
+
+
+def recognize_real_stack(stack):
+    """``RealStackGeometry`` of the controller's collection stack (mbrl.py:259-272) or evaluation stack (:275-291), or
+    raises ``Unrecognized`` with the reason.  From the outside in: frozen ``TransformActionWrapper``s that flatten to at
+    most one scaling and hold no forcing and no sensor, with the one-step ``StoreNActionsVecWrapper`` that is
+    ``stack.astore`` under or on top of them; ``TransformObsWrapper``s and the pass-through ``BaseWorldVecEnvWrapper`` in
+    any order, holding sensors and at most one ``ScaleTransform`` with scalar bounds (``aggregate`` and ``batched``), which,
+    where it updates, sits directly above the observation store; the one-step ``StoreNObsVecWrapper`` that is
+    ``stack.ostore``; a ``KSBatchedVecEnv``."""
+    from pdecontrol.mbrl.world.wrappers import BaseWorldVecEnvWrapper
+    from pdegym.kuramoto.batched import KSBatchedVecEnv
+    env = stack.envs
+    above, below, astore = [], [], None
+    while True:
+        if type(env) is vw.StoreNActionsVecWrapper:
+            if astore is not None:
+                raise Unrecognized("two action stores")
+            if env is not stack.astore:
+                raise Unrecognized("an action store that is not the stack's astore")
+            if env.num_steps != 1:
+                raise Unrecognized(f"an action store of {env.num_steps} steps")
+            astore = env
+        elif type(env) is vw.TransformActionWrapper:
+            if _is_forcing(env.transform) is not None:
+                raise Unrecognized("a forcing in the action stack")
+            if _updates_statistics(env):
+                raise Unrecognized("an action transform that updates its statistics")
+            (above if astore is None else below).append(env.transform)
+        else:
+            break
+        env = env.env
+    if astore is None:
+        raise Unrecognized(f"a {type(env).__name__} in place of the action store")
+    chains = []                                           # (steps, wrapper frozen, bare scaling or None), outermost first
+    while type(env) in (vw.TransformObsWrapper, BaseWorldVecEnvWrapper):
+        if type(env) is vw.TransformObsWrapper:
+            chains.append((_flatten(env.transform), bool(env.frozen), _bare_scale(env.transform)))
+        env = env.env
+    if type(env) is not vw.StoreNObsVecWrapper or env is not stack.ostore:
+        raise Unrecognized(f"a {type(env).__name__} in place of the observation store")
+    if env.num_steps != 1:
+        raise Unrecognized(f"an observation store of {env.num_steps} steps")
+    ks = env.env
+    if type(ks) is not KSBatchedVecEnv:
+        raise Unrecognized(f"a {type(ks).__name__} in place of the KSBatchedVecEnv")
+    oshape, ashape = tuple(ks.single_observation_space.shape), tuple(ks.single_action_space.shape)
+    if len(oshape) != 2 or oshape[0] != 1 or len(ashape) != 2 or ashape[0] != 1:
+        raise Unrecognized(f"an env with observations {oshape} and actions {ashape} (one channel each)")
+    N, A = oshape[1], ashape[1]
+
+    action = field_map(tr.Operation(above + below), A)
+    if (action.start, action.stride, action.width) != (0, 1, A):
+        raise Unrecognized("a sensor on the agent's actions")
+    scaled_above = any(step[0] == "scale" for t in above for step in _flatten(t))
+    record_raw = action.coef is not None and not scaled_above
+
+    scaling, update, strides = None, 0, []
+    for steps, frozen, bare in reversed(chains):          # innermost first: the order the observations pass them
+        for step in steps:
+            if step[0] == "sensor":
+                strides.append(step[1])
+                continue
+            _, scale, inverse = step
+            if scaling is not None:
+                raise Unrecognized("two observation scalings")
+            if inverse:
+                raise Unrecognized("an inverse scaling on the observations")
+            if not (scale.aggregate and scale.batched):
+                raise Unrecognized("an observation scaling with per-column running bounds (aggregate and batched are not both set)")
+            stats = [torch.as_tensor(s) for s in (scale.vmin, scale.vmax, scale.lower, scale.upper)]
+            if any(s.numel() != 1 or s.dtype != torch.float32 or s.is_cuda for s in stats):
+                raise Unrecognized("an observation scaling whose bounds are not scalar fp32 host values")
+            scaling = scale
+            if not frozen and not scale.frozen:
+                if bare is not scale:
+                    raise Unrecognized("a running scaling inside a composite transform")
+                if strides:
+                    raise Unrecognized("a sensor under the running scaling")
+                update = 1
+    agent_obs = field_map(tr.Operation([tr.SensorTransform(r) for r in strides]), N)
+    return RealStackGeometry(ks, action, record_raw, scaling, update, agent_obs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 2. the plan
+# ----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class PhasePlan:
+    """``K`` steps; ``truncations``: the steps (0-based) at which some env truncates; ``steps`` [K, E]: the ``steps``
+    column of every sample (``infos["step"]``: the env counter after the step, before an autoreset zeroes it);
+    ``timestep``: the env counters after the phase."""
+    K: int
+    truncations: List[int]
+    steps: np.ndarray
+    timestep: np.ndarray
+
+
+def plan_phase(timestep0, max_episode_steps, E, stop):
+    """The phase ``Worker.rollout`` runs from env counters ``timestep0``, from host integers only: ``stop`` is called
+    with the loop's arguments ``(k * E, nstopped_k)``, k = 0, 1, ..., until it holds, exactly as often as the loop calls
+    it.  An env truncates at the step that brings its counter to ``max_episode_steps`` and restarts at 0."""
+    ts = np.asarray(timestep0, dtype=np.int64).copy()
+    assert ts.shape == (E,), (ts.shape, E)
+    k, nstopped, truncations, steps = 0, 0, [], []
+    while not stop(k * E, nstopped):
+        ts += 1
+        steps.append(ts.copy())
+        cut = ts >= max_episode_steps
+        if cut.any():
+            truncations.append(k)
+            nstopped += int(cut.sum())
+            ts[cut] = 0
+        k += 1
+    return PhasePlan(k, truncations, np.asarray(steps, dtype=np.int64).reshape(k, E), ts)
+
+
+def segment_steps(E, N, A, budget=None):
+    """Most steps of one segment: its block (trajectory rows, actions, fp64 sums, status) stays under ``budget`` bytes."""
+    budget = SEGMENT_BYTES if budget is None else budget
+    per_step = E * (4 * N + 4 * A + 8 + 4)
+    return max(1, (int(budget) - 4 * E * N) // per_step)
+
+
+def segments(plan, limit):
+    """The plan as ("kernel", first step, steps) runs without a truncation, at most ``limit`` steps each, and
+    ("host", step, 1) entries for the steps at which an env truncates."""
+    out, k, cuts = [], 0, set(plan.truncations)
+    while k < plan.K:
+        if k in cuts:
+            out.append(("host", k, 1))
+            k += 1
+            continue
+        n = 1
+        while n < limit and k + n < plan.K and k + n not in cuts:
+            n += 1
+        out.append(("kernel", k, n))
+        k += n
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 3. the replay
+# ----------------------------------------------------------------------------------------------------------------------
+def build_replay(pieces, E):
+    """The ``ExperienceReplay`` that ``Sample.split`` + ``ExperienceReplay.add`` build step by step, from the phase's
+    pieces in time order, with one deque per episode and field.  A piece is a segment ``(traj [T + 1, E, N], actions
+    [T, E, A], rewards [T, E] fp64, steps [T, E] int64)`` without a truncation, or one host step as the ``Sample`` of
+    ``[E, ...]`` arrays the loop hands to ``split``.  Items are what ``split`` yields: ``[1, N]`` / ``[1, A]`` fp32
+    rows, fp64 rewards, numpy bools, int64 steps; the observation a step ends with and the next step starts with are one
+    view of the segment's block.  Episode keys and ``vindex`` follow ``add``: an env moves to the next free key the moment
+    its sample truncates, in env order."""
+    # hundreds of thousands of containers that all stay alive: the cyclic collector would walk them again and again
+    # (150 ms against 35 ms at 4096 x 256 x 8 steps on the host this was written on)
+    paused = gc.isenabled()
+    gc.disable()
+    try:
+        return _build_replay(pieces, E)
+    finally:
+        if paused:
+            gc.enable()
+
+
+def _build_replay(pieces, E):
+    replay = ExperienceReplay()
+    vindex, columns = replay.vindex, {}                  # columns[key][field] = list of per-piece columns, in time order
+    free = [0]                                           # ``_next_episode_id`` without its pass over every entry
+
+    def slot(e):
+        key = vindex.get(e)
+        if key is None:
+            key = vindex[e] = free[0]
+            free[0] += 1
+        cols = columns.get(key)
+        if cols is None:
+            cols = columns[key] = [[] for _ in range(7)]
+        return cols
+
+    for piece in pieces:
+        if isinstance(piece, Sample):
+            fields = tuple(piece)
+            ended = np.logical_or(fields[4], fields[5])
+            for e in range(E):
+                for col, value in zip(slot(e), fields):
+                    col.append(value[e:e + 1])
+                if ended[e]:
+                    vindex[e] = free[0]
+                    free[0] += 1
+            continue
+        traj, actions, rewards, steps = piece
+        T = actions.shape[0]
+        # every item once, step by step (numpy hands out the E rows of a step in one pass), then regrouped per env
+        rows = [list(traj[t][:, None, :]) for t in range(T + 1)]
+        per_env = lambda per_step: list(zip(*per_step))
+        obs, nxt = per_env(rows[:T]), per_env(rows[1:])
+        act = per_env([list(actions[t][:, None, :]) for t in range(T)])
+        rew, stp = per_env([list(rewards[t]) for t in range(T)]), per_env([list(steps[t]) for t in range(T)])
+        flags = tuple(np.zeros(T, dtype=np.bool_))
+        for e, column in enumerate(zip(obs, act, nxt, rew, stp)):
+            cols = slot(e)
+            for i, value in zip((0, 1, 2, 3, 6), column):
+                cols[i].append(value)
+            cols[4].append(flags)
+            cols[5].append(flags)
+    for key, cols in columns.items():
+        for store, col in zip(replay._stores(), cols):
+            store[key] = deque(col[0]) if len(col) == 1 else deque(chain.from_iterable(col))
+    return replay
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# 4. the phase
+# ----------------------------------------------------------------------------------------------------------------------
+def _notice(reason, expected=False):
+    if reason not in ops._NOTIFIED:
+        ops._NOTIFIED.add(reason)
+        log = ops._LOG.info if expected else ops._LOG.warning
+        log("the device-resident collection step does not implement %s: the collection phase runs the per-step loop of "
+            "Worker.rollout", reason)
+
+
+def _kernel_tier(worker, agent):
+    """(RealStackGeometry, FusedSAC, None) when this phase runs on the kernels, else (None, None, reason)."""
+    from pdecontrol.sac.sac import SAC
+
+    def loop(reason, expected=False):
+        _notice(reason, expected)
+        return None, None, reason
+
+    if not isinstance(agent, SAC):
+        return loop(f"a {type(agent).__name__} agent (not a SAC)", True)
+    if agent.device.type != "cuda":
+        return loop("a SAC agent on the CPU", True)
+    if not ops.fused_enabled():
+        return loop("PDECONTROL_FUSED=0", True)
+    try:
+        geo = recognize_real_stack(worker.stack)
+    except Unrecognized as e:
+        return loop(str(e))
+    env = geo.env
+    if env.stepper.device < 0:
+        return loop("the CPU twin of the KS stepper")
+    if torch.device("cuda", env.stepper.device) != torch.empty(0, device=agent.device).device:
+        return loop("an agent and an env on different devices")
+    from pdecontrol.mbrl import collect_hip as co
+    from pdecontrol.sac import sac_hip
+    if env.stepper.n_act != geo.action.width:
+        return loop(f"a stepper with {env.stepper.n_act} actuators under {geo.action.width} action columns")
+    reason = co.supported(co.Geometry(env.num_envs, 1, env.N, geo.action.width, geo.agent_obs.start, geo.agent_obs.stride))
+    if reason is not None:
+        return loop(reason)
+    obs = torch.empty((env.num_envs, 1, geo.agent_obs.width), dtype=torch.float32, device=agent.device)
+    if not sac_hip.use_kernels(agent, obs):                 # announces its own reason
+        return loop("a SAC geometry the fused kernels refuse")
+    return geo, agent._fused_for(obs), None
+
+
+class _Buffers:
+    """Device and pinned host memory of the kernel tier, kept on the worker between phases: the segment block (grown on
+    demand), the agent-side buffers and the workspace."""
+
+    def __init__(self, agent, geo):
+        from pdecontrol.mbrl import collect_hip as co
+        env = geo.env
+        self.device = torch.empty(0, device=agent.device).device
+        self.E, self.N, self.A, self.O = env.num_envs, env.N, geo.action.width, geo.agent_obs.width
+        self.sensor = (geo.agent_obs.start, geo.agent_obs.stride)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.noise = f32(self.E, agent.policy.achannels, agent.policy.aheight)
+        self.action, self.env_action = f32(self.E, self.A), f32(self.E, self.A)
+        probe = co.Geometry(self.E, 1, self.N, self.A, *self.sensor)
+        self.workspace = f32(co.workspace_floats(probe))
+        self.coef = f32(4, self.A)
+        self.block = self.block_host = None
+        self.capacity = 0
+
+    def matches(self, agent, geo):
+        env = geo.env
+        return ((self.device, self.E, self.N, self.A, self.O, self.sensor) ==
+                (torch.empty(0, device=agent.device).device, env.num_envs, env.N, geo.action.width, geo.agent_obs.width,
+                 (geo.agent_obs.start, geo.agent_obs.stride))
+                and tuple(self.noise.shape[1:]) == (agent.policy.achannels, agent.policy.aheight))
+
+    def layout(self, T):
+        """Offsets (in floats) of [traj (T+1)EN | actions TEA | policy_obs EO | bounds 4 | pad | ssq TE fp64 | status TE]."""
+        E, N, A, O = self.E, self.N, self.A, self.O
+        sizes = [(T + 1) * E * N, T * E * A, E * O, 4]
+        sizes.append(sum(sizes) % 2)                      # the fp64 sums start 8-byte aligned
+        sizes += [2 * T * E, T * E]
+        return np.concatenate(([0], np.cumsum(sizes)))
+
+    def views(self, T):
+        """(device views, host views) of a segment of ``T`` steps: traj, actions, policy_obs, bounds, ssq, status."""
+        off = self.layout(T)
+        if off[-1] > self.capacity:
+            self.capacity = int(off[-1])
+            self.block = torch.empty(self.capacity, dtype=torch.float32, device=self.device)
+            self.block_host = torch.empty(self.capacity, dtype=torch.float32).pin_memory()
+        E, N, A, O = self.E, self.N, self.A, self.O
+
+        def cut(block):
+            part = lambda i: block[int(off[i]):int(off[i + 1])]
+            return (part(0).view(T + 1, E, N), part(1).view(T, E, A), part(2).view(E, 1, O), part(3),
+                    part(5).view(torch.float64).view(T, E), part(6).view(torch.int32).view(T, E))
+
+        return cut(self.block), cut(self.block_host), int(off[-1])
+
+
+def _host_step(worker, agent, deterministic):
+    """One pass of the loop body of ``Worker.rollout``: the ``Sample`` of ``[E, ...]`` arrays it hands to ``split``."""
+    envs, ostore, astore = worker.stack.envs, worker.stack.ostore, worker.stack.astore
+    with torch.no_grad():
+        actions = agent.select_action(worker._last_obs, deterministic=deterministic)
+    worker._last_obs, rewards, terminated, truncated, infos = envs.step(actions)
+    obs = worker._last_stored_obs.copy()
+    worker._last_stored_obs = _stored(ostore, ostore.obs)
+    nxtobs = worker._last_stored_obs.copy()
+    actions = _stored(astore, astore.actions)
+    if "final_observation" in infos:
+        index = infos["_final_observation"]
+        nxtobs[index] = ostore.finals[index].copy()[ostore.mask[index]]
+    return Sample(obs, actions, nxtobs, rewards, terminated, truncated, infos["step"])
+
+
+def _run_segment(worker, agent, fused, geo, buf, T, steps):
+    """``T`` steps without a truncation in HBM, from the state the worker and the stack hold, written back to them."""
+    from pdecontrol.mbrl import collect_hip as co
+    from pdecontrol.sac import sac_hip
+    env, scaling = geo.env, geo.scaling
+    E, N = buf.E, buf.N
+    (traj, actions, pobs, bounds, ssq, status), (h_traj, h_actions, h_pobs, h_bounds, h_ssq, h_status), used = buf.views(T)
+    # slot 0, the policy's observation and the running bounds: written to the pinned block, uploaded once
+    h_traj[0].copy_(torch.from_numpy(np.ascontiguousarray(worker._last_stored_obs, dtype=np.float32).reshape(E, N)))
+    h_pobs.copy_(torch.from_numpy(np.ascontiguousarray(worker._last_obs, dtype=np.float32).reshape(h_pobs.shape)))
+    if scaling is not None:
+        h_bounds[0] = h_bounds[2] = float(scaling.vmin)
+        h_bounds[1] = h_bounds[3] = float(scaling.vmax)
+    for dst, src in ((traj[0], h_traj[0]), (pobs, h_pobs), (bounds, h_bounds)):
+        dst.copy_(src, non_blocking=True)
+    geometry = co.Geometry(E, T, N, buf.A, *buf.sensor)
+    coef = None
+    if geo.action.coef is not None:
+        buf.coef.copy_(geo.action.coef)
+        coef = buf.coef
+    act_args = co.act_args(buf.action, coef, buf.env_action, actions, geo.record_raw)
+    obs_args = co.observe_args(traj, pobs, None if scaling is None else bounds,
+                               0.0 if scaling is None else float(scaling.lower), 0.0 if scaling is None else float(scaling.upper),
+                               geo.update, buf.workspace)
+    current = torch.cuda.current_stream(buf.device)
+    if getattr(env, "_stream_handle", None) != current.cuda_stream:     # as ``KSBatchedVecEnv.step_torch`` binds it
+        env.stepper.set_stream(current.cuda_stream)
+        env._stream_handle = current.cuda_stream
+    env._set_objective(env.proto.step_objective)
+    fused.refresh(need_adam=fused._keys[1] if fused._keys else False)
+    stream, forward = co.stream(), sac_hip.load().sac_policy_forward
+    cfg, state = ctypes.byref(fused.cfg), ctypes.byref(fused.state)
+    p_obs, p_noise, p_action = (sac_hip._ptr(t) for t in (pobs, buf.noise, buf.action))
+    d_env_action, substeps = buf.env_action.data_ptr(), env.cfg_steps
+    row, slot = E * N * 4, traj.data_ptr()
+    d_ssq, d_status = ssq.data_ptr(), status.data_ptr()
+    for t in range(T):                                    # eager launches, ``t`` by value, no host synchronisation
+        buf.noise.normal_()                               # the draw of ``SAC.act``: same call, shape and device
+        sac_hip._check(forward(stream, cfg, state, E, p_obs, p_noise, p_action, None, None))
+        co.act(stream, geometry, act_args, t)
+        env.stepper.step_device(d_actions=d_env_action, n_substeps=substeps, d_obs=slot + (t + 1) * row,
+                                d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)
+        co.observe(stream, geometry, obs_args, t)
+    buf.block_host[:used].copy_(buf.block[:used], non_blocking=True)
+    current.synchronize()                                 # the segment's one synchronisation
+    return _write_back(worker, geo, T, h_traj.numpy(), h_actions.numpy(), h_pobs.numpy(), h_bounds.numpy(), h_ssq.numpy(),
+                       h_status.numpy(), steps)
+
+
+def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, steps):
+    """A segment's host block (views of the pinned staging: copied here) into the state the loop would hold after these
+    ``T`` steps -- stores, bounds, ``env.timestep``, the worker's two observations -- and the segment's replay piece."""
+    env, scaling = geo.env, geo.scaling
+    ostore, astore = worker.stack.ostore, worker.stack.astore
+    bad = np.nonzero(status.any(axis=1))[0]
+    if bad.size:
+        env._raise_on(status[bad[0]])                     # the first step that shows an overflow, as the loop raises it
+    traj, actions = traj.copy(), actions.copy()
+    rewards = (-1.0) * (1 / env.N) * ssq / env.cfg_steps  # ``KSBatchedVecEnv._finish_step``, every step at once
+    ostore.obs[:, -1] = traj[T][:, None, :]
+    ostore.mask[:, -1] = True
+    astore.actions[:, -1] = actions[T - 1][:, None, :]
+    astore.mask[:, -1] = True
+    if geo.update:
+        cell = 2 * (T & 1)                                # step T - 1 wrote cell T & 1
+        as_stat = lambda v: torch.from_numpy(np.asarray(v, dtype=np.float32).reshape(1, 1, 1).copy())
+        scaling.vmin, scaling.vmax = as_stat(bounds[cell]), as_stat(bounds[cell + 1])
+    env.timestep += T
+    worker._last_obs = policy_obs.copy()
+    worker._last_stored_obs = _stored(ostore, ostore.obs)
+    return traj, actions, rewards, steps
+
+
+def collect(worker, agent, stop, deterministic=False):
+    """The ``ExperienceReplay`` ``worker.rollout(agent, stop, deterministic)`` returns, with everything the loop mutates
+    left where the loop leaves it (module docstring).  The result carries ``tier`` ("loop" or "kernel"), ``tier_reason``
+    (why the loop ran; None on the kernel tier) and ``host_steps`` (steps that went through the stack on the host: all of
+    them on the loop tier, the truncation steps on the kernel tier).  ``deterministic`` reaches ``agent.select_action``,
+    which a ``SAC`` ignores as the reference's does: both tiers sample."""
+    geo, fused, reason = _kernel_tier(worker, agent)
+    if geo is None:
+        replay = worker.rollout(agent, stop, deterministic)
+        replay.tier, replay.tier_reason, replay.host_steps = "loop", reason, replay.ntimesteps // max(len(replay.vindex), 1)
+        return replay
+    env = geo.env
+    E = env.num_envs
+    with torch.cuda.device(env.stepper.device):
+        if worker._last_obs is None:                      # the loop's first act on a fresh worker
+            worker._last_obs = worker.stack.envs.reset()
+            worker._last_stored_obs = _stored(worker.stack.ostore, worker.stack.ostore.obs)
+        plan = plan_phase(env.timestep, env.max_episode_steps, E, stop)
+        buf = getattr(worker, "_collect_buffers", None)
+        if buf is None or not buf.matches(agent, geo):
+            buf = worker._collect_buffers = _Buffers(agent, geo)
+        pieces, host_steps = [], 0
+        for kind, first, n in segments(plan, segment_steps(E, env.N, buf.A)):
+            if kind == "host":
+                pieces.append(_host_step(worker, agent, deterministic))
+                host_steps += 1
+            else:
+                pieces.append(_run_segment(worker, agent, fused, geo, buf, n, plan.steps[first:first + n]))
+        assert np.array_equal(env.timestep, plan.timestep), "the env counters left the plan"
+    replay = build_replay(pieces, E)
+    replay.tier, replay.tier_reason, replay.host_steps = "kernel", None, host_steps
+    for callback in worker.callbacks:
+        callback.on_rollout_end(replay)
+    return replay
