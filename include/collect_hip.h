@@ -31,7 +31,7 @@
  *
  * The running bounds.  `bounds` points at FOUR device floats, two cells of (vmin, vmax).  Step t reads cell t & 1; with
  * update = 1 it writes the joined bounds to cell (t + 1) & 1.  No workgroup reads a cell that another workgroup of the
- * same launch writes (the step[2] rule of rollout/rollout_hip.h).  The host sets cell 0 before step 0 of an updating
+ * same launch writes (the step[2] rule of rollout_hip.h).  The host sets cell 0 before step 0 of an updating
  * scaling and both cells of a frozen one.
  *
  * One wave per env row, four per workgroup; plain vector stores; float4 accesses where N % 4 == 0, the sensor is
@@ -39,10 +39,6 @@
  * structs read during the call and passed to the kernels by value; every pointer in them is a DEVICE pointer.  `t` is
  * passed by value.  Everything is enqueued on `stream`: no host synchronisation, no device allocation.  Arguments are
  * validated on the host before any HIP call.  Return 0 on success, negative on error (co_last_error()).
- *
- * This header sits in include/collect/ for the reason given in include/rollout/rollout_hip.h: tests/test_capi_symbols.py
- * pins the headers directly under include/.  Its declarations, binding and exports are checked by
- * tests/test_collection_phase_host.py.
  */
 #ifndef COLLECT_HIP_H
 #define COLLECT_HIP_H

@@ -31,12 +31,6 @@
  * where the widths and alignments allow (decided on the host per launch).  The structs are HOST structs read during the
  * call and passed to the kernel by value; every pointer in them is a DEVICE pointer.  Everything is enqueued on `stream`:
  * no host synchronisation, no device allocation.  Return 0 on success, negative on error (ro_last_error()).
- *
- * This header sits in include/rollout/ and not beside the others: tests/test_capi_symbols.py keeps a table of every
- * include/ *.h and asserts that it is complete, and the change that added this library left that file as it was.  Its
- * declarations, binding and exports are checked by tests/test_imagination_phase_gpu.py instead.  A later change should
- * move it to include/rollout_hip.h and add its row ("rollout_hip.h", "librollout_hip.so", "ro",
- * ["pdecontrol.mbrl.rollout_hip"]) to that table.
  */
 #ifndef ROLLOUT_HIP_H
 #define ROLLOUT_HIP_H

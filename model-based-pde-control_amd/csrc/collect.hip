@@ -1,4 +1,4 @@
-// collect.hip -- the kernels that keep the real-env collection loop in HBM (C ABI: include/collect/collect_hip.h;
+// collect.hip -- the kernels that keep the real-env collection loop in HBM (C ABI: include/collect_hip.h;
 // binding: pdecontrol/mbrl/collect_hip.py; caller: pdecontrol/mbrl/collection_phase.py).
 //
 // co_act is the wrapper stack's action side (frozen action scaling, action-store record), co_observe its observation
@@ -7,29 +7,18 @@
 // (min, max) partials, then every wave folds the partials itself.  No atomics, no spin-wait; every store is a plain
 // vector store.
 //
-// The affine maps are four separately rounded fp32 operations; the file is also built with -ffp-contract=off, so the
-// results equal the host wrappers' bit for bit.
+// The affine maps are row_ops.h's, so the results equal the host wrappers' bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/collect/collect_hip.h"
+#include "../../include/collect_hip.h"
 #include "capi_error.h"
+#include "row_ops.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int WAVE = 64;
-constexpr int WAVES = 4;               // env rows per workgroup
-constexpr int NT = WAVE * WAVES;
-
-__device__ __forceinline__ float affine(float v, float a, float ba, float dc, float c)
-{
-    return __fadd_rn(__fmul_rn(__fdiv_rn(__fsub_rn(v, a), ba), dc), c);
-}
 
 // torch.minimum / torch.maximum and numpy's min / max: a NaN on either side gives NaN
 __device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
@@ -56,8 +45,7 @@ __global__ __launch_bounds__(NT) void co_act_kernel(const ActKernelArgs k)
     if (e >= k.E || lane >= k.A) return;
     const long at = (long)e * k.A + lane;
     const float raw = k.a.action[at];
-    const float* __restrict__ coef = k.a.coef;
-    const float env = coef ? affine(raw, coef[lane], coef[k.A + lane], coef[2 * k.A + lane], coef[3 * k.A + lane]) : raw;
+    const float env = affine_col(k.a.coef, k.A, lane, raw);
     k.a.env_action[at] = env;
     k.a.actions[(long)k.t * k.E * k.A + at] = k.a.record_raw ? raw : env;
 }
@@ -158,10 +146,6 @@ __global__ __launch_bounds__(NT) void co_scale_kernel(const ObserveKernelArgs k)
         pol[j] = scaled ? affine(v, vmin, ba, dc, c) : v;
     }
 }
-
-int width_of(int n, int start, int stride) { return (n - start + stride - 1) / stride; }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int blocks_of(int E) { return (E + WAVES - 1) / WAVES; }
 

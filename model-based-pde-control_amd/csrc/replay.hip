@@ -1,5 +1,5 @@
 // replay.hip -- the fused batch gather of the policy-update phase, and the append and episode returns of the
-// device-resident replay (C ABI: include/replay_hip.h and include/replay/replay_slab_hip.h; binding: pdecontrol/mbrl/replay_hip.py).
+// device-resident replay (C ABI: include/replay_hip.h; binding: pdecontrol/mbrl/replay_hip.py).
 //
 // One launch assembles one SAC batch from several packed replays.  A wave owns a sample: it reads the sample's row in the
 // concatenated row space, finds the source by comparing against the (at most RP_MAX_SOURCES) first rows -- the sources
@@ -7,9 +7,8 @@
 // row with lanes along the columns: obs and nxtobs through the sensor and the observation coefficients, actions through
 // the action coefficients, reward and terminated flag by lane 0.  float4 where the source allows it (see `vec` below).
 //
-// The affine map is four separately rounded fp32 operations (__fsub_rn, __fdiv_rn, __fmul_rn, __fadd_rn; the file is also
-// built with -ffp-contract=off), the operations of ScaleTransform._affine, so the batch equals the host loader's bit for
-// bit.  Plain vector stores only; nothing is stored through the scalar unit.
+// The affine map is row_ops.h's, so the batch equals the host loader's bit for bit.  Plain vector stores only; nothing is
+// stored through the scalar unit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -17,17 +16,11 @@
 #include <cstdio>
 #include <vector>
 
-#include "../../include/replay/replay_slab_hip.h"
 #include "../../include/replay_hip.h"
 #include "capi_error.h"
+#include "row_ops.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int WAVE = 64;
-constexpr int WAVES = 4;               // samples per workgroup
-constexpr int NT = WAVE * WAVES;
 
 struct GatherArgs {
     rp_source src[RP_MAX_SOURCES];
@@ -43,40 +36,19 @@ struct GatherArgs {
     float* terminated;
 };
 
-__device__ __forceinline__ float affine(float v, float a, float ba, float dc, float c)
-{
-    return __fadd_rn(__fmul_rn(__fdiv_rn(__fsub_rn(v, a), ba), dc), c);
-}
-
 // n output columns of one row: out[j] = affine(in[start + j * stride]); coef is [4][n] or NULL
 __device__ __forceinline__ void copy_row(const float* __restrict__ in, const float* __restrict__ coef, float* __restrict__ out,
                                          int n, int start, int stride, int lane)
 {
-    for (int j = lane; j < n; j += WAVE) {
-        float v = in[start + (long)j * stride];
-        if (coef) v = affine(v, coef[j], coef[n + j], coef[2 * n + j], coef[3 * n + j]);
-        out[j] = v;
-    }
+    for (int j = lane; j < n; j += WAVE) out[j] = affine_col(coef, n, j, in[start + (long)j * stride]);
 }
 
 // the same for stride 1 with every address a multiple of 16 bytes and n a multiple of 4
 __device__ __forceinline__ void copy_row4(const float* __restrict__ in, const float* __restrict__ coef, float* __restrict__ out,
                                           int n, int start, int lane)
 {
-    for (int j = 4 * lane; j < n; j += 4 * WAVE) {
-        f4 v = *reinterpret_cast<const f4*>(in + start + j);
-        if (coef) {
-            const f4 a = *reinterpret_cast<const f4*>(coef + j);
-            const f4 ba = *reinterpret_cast<const f4*>(coef + n + j);
-            const f4 dc = *reinterpret_cast<const f4*>(coef + 2 * n + j);
-            const f4 c = *reinterpret_cast<const f4*>(coef + 3 * n + j);
-            v.x = affine(v.x, a.x, ba.x, dc.x, c.x);
-            v.y = affine(v.y, a.y, ba.y, dc.y, c.y);
-            v.z = affine(v.z, a.z, ba.z, dc.z, c.z);
-            v.w = affine(v.w, a.w, ba.w, dc.w, c.w);
-        }
-        *reinterpret_cast<f4*>(out + j) = v;
-    }
+    for (int j = 4 * lane; j < n; j += 4 * WAVE)
+        *reinterpret_cast<f4*>(out + j) = affine_col4(coef, n, j, *reinterpret_cast<const f4*>(in + start + j));
 }
 
 __global__ __launch_bounds__(NT) void rp_gather_kernel(const GatherArgs g)
@@ -184,12 +156,7 @@ __global__ __launch_bounds__(NT) void rp_episode_returns_kernel(const float* __r
     returns[e] = acc;
 }
 
-int obs_dim_of(const rp_source& s)
-{
-    return (s.obs_width - s.sensor_start + s.sensor_stride - 1) / s.sensor_stride;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+int obs_dim_of(const rp_source& s) { return width_of(s.obs_width, s.sensor_start, s.sensor_stride); }
 
 }  // namespace
 

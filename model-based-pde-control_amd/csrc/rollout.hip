@@ -1,4 +1,4 @@
-// rollout.hip -- the two kernels that close the imagined-rollout loop in HBM (C ABI: include/rollout/rollout_hip.h;
+// rollout.hip -- the two kernels that close the imagined-rollout loop in HBM (C ABI: include/rollout_hip.h;
 // binding: pdecontrol/mbrl/rollout_hip.py; caller: pdecontrol/mbrl/imagination_phase.py).
 //
 // ro_act_chain is the wrapper stack's action side (raw-action record, action scaling, Gaussian forcing, forcing scaling,
@@ -7,49 +7,19 @@
 // kernel arguments and are picked by wave-uniform selects over constant indices, so the argument struct is never indexed
 // dynamically and nothing spills.  No LDS, no atomics; every store is a plain vector store.
 //
-// The affine maps are four separately rounded fp32 operations and the forcing chain is explicit fmaf; the file is also
-// built with -ffp-contract=off, so the results equal the host wrappers' bit for bit.
+// The affine maps are row_ops.h's and the forcing chain is explicit fmaf, so the results equal the host wrappers' bit for
+// bit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/rollout/rollout_hip.h"
+#include "../../include/rollout_hip.h"
 #include "capi_error.h"
+#include "row_ops.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int WAVE = 64;
-constexpr int WAVES = 4;               // envs per workgroup
-constexpr int NT = WAVE * WAVES;
-
-__device__ __forceinline__ float affine(float v, float a, float ba, float dc, float c)
-{
-    return __fadd_rn(__fmul_rn(__fdiv_rn(__fsub_rn(v, a), ba), dc), c);
-}
-
-// coef is [4][n] or NULL
-__device__ __forceinline__ float affine_col(const float* __restrict__ coef, int n, int j, float v)
-{
-    return coef ? affine(v, coef[j], coef[n + j], coef[2 * n + j], coef[3 * n + j]) : v;
-}
-
-__device__ __forceinline__ f4 affine_col4(const float* __restrict__ coef, int n, int j, f4 v)
-{
-    if (!coef) return v;
-    const f4 a = *reinterpret_cast<const f4*>(coef + j);
-    const f4 ba = *reinterpret_cast<const f4*>(coef + n + j);
-    const f4 dc = *reinterpret_cast<const f4*>(coef + 2 * n + j);
-    const f4 c = *reinterpret_cast<const f4*>(coef + 3 * n + j);
-    v.x = affine(v.x, a.x, ba.x, dc.x, c.x);
-    v.y = affine(v.y, a.y, ba.y, dc.y, c.y);
-    v.z = affine(v.z, a.z, ba.z, dc.z, c.z);
-    v.w = affine(v.w, a.w, ba.w, dc.w, c.w);
-    return v;
-}
 
 struct ActKernelArgs {
     ro_act_args a;
@@ -165,10 +135,6 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const SettleKernelArgs k)
         k.a.steps[slot] = k.a.steps0[b] + t + 1;
     }
 }
-
-int width_of(int n, int start, int stride) { return (n - start + stride - 1) / stride; }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libcollect_hip.so (C ABI: include/collect/collect_hip.h ``co_*``; kernels: csrc/collect.hip): the
+"""ctypes binding of libcollect_hip.so (C ABI: include/collect_hip.h ``co_*``; kernels: csrc/collect.hip): the
 action side and the observation side of the device-resident collection step.  ``co_supported``, ``co_workspace_floats``
 and ``co_last_error`` are pure host functions and work without a GPU.  A missing library raises: the kernel tier of
 pdecontrol/mbrl/collection_phase.py has no silent fallback.
@@ -16,7 +16,7 @@ _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
 
 class Geometry(ctypes.Structure):
-    """``co_geometry`` of include/collect/collect_hip.h"""
+    """``co_geometry`` of include/collect_hip.h"""
     _fields_ = [("E", _i), ("T", _i), ("N", _i), ("A", _i), ("obs_start", _i), ("obs_stride", _i)]
 
 

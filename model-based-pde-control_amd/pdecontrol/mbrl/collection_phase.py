@@ -35,13 +35,11 @@ from dataclasses import dataclass
 from itertools import chain
 from typing import Any, List, Optional
 
-import ctypes
-
 import numpy as np
 import torch
 
-from pdecontrol.mbrl.imagination_phase import _is_forcing, _updates_statistics
-from pdecontrol.mbrl.policy_phase import FieldMap, Unrecognized, _flatten, field_map
+from pdecontrol.mbrl.recognition import (FieldMap, Unrecognized, action_store, field_map, flatten, is_forcing, notice,
+                                         observation_store, one_channel_each, same_device, updates_statistics)
 from pdecontrol.mbrl.replay import ExperienceReplay
 from pdecontrol.mbrl.types import Sample
 from pdecontrol.mbrl.worker import _stored
@@ -96,15 +94,12 @@ def recognize_real_stack(stack):
         if type(env) is vw.StoreNActionsVecWrapper:
             if astore is not None:
                 raise Unrecognized("two action stores")
-            if env is not stack.astore:
-                raise Unrecognized("an action store that is not the stack's astore")
-            if env.num_steps != 1:
-                raise Unrecognized(f"an action store of {env.num_steps} steps")
+            action_store(env, stack, "an action store that is not the stack's astore")
             astore = env
         elif type(env) is vw.TransformActionWrapper:
-            if _is_forcing(env.transform) is not None:
+            if is_forcing(env.transform) is not None:
                 raise Unrecognized("a forcing in the action stack")
-            if _updates_statistics(env):
+            if updates_statistics(env):
                 raise Unrecognized("an action transform that updates its statistics")
             (above if astore is None else below).append(env.transform)
         else:
@@ -115,24 +110,17 @@ def recognize_real_stack(stack):
     chains = []                                           # (steps, wrapper frozen, bare scaling or None), outermost first
     while type(env) in (vw.TransformObsWrapper, BaseWorldVecEnvWrapper):
         if type(env) is vw.TransformObsWrapper:
-            chains.append((_flatten(env.transform), bool(env.frozen), _bare_scale(env.transform)))
+            chains.append((flatten(env.transform), bool(env.frozen), _bare_scale(env.transform)))
         env = env.env
-    if type(env) is not vw.StoreNObsVecWrapper or env is not stack.ostore:
-        raise Unrecognized(f"a {type(env).__name__} in place of the observation store")
-    if env.num_steps != 1:
-        raise Unrecognized(f"an observation store of {env.num_steps} steps")
-    ks = env.env
+    ks = observation_store(env, stack)
     if type(ks) is not KSBatchedVecEnv:
         raise Unrecognized(f"a {type(ks).__name__} in place of the KSBatchedVecEnv")
-    oshape, ashape = tuple(ks.single_observation_space.shape), tuple(ks.single_action_space.shape)
-    if len(oshape) != 2 or oshape[0] != 1 or len(ashape) != 2 or ashape[0] != 1:
-        raise Unrecognized(f"an env with observations {oshape} and actions {ashape} (one channel each)")
-    N, A = oshape[1], ashape[1]
+    N, A = one_channel_each(ks, "an env")
 
     action = field_map(tr.Operation(above + below), A)
     if (action.start, action.stride, action.width) != (0, 1, A):
         raise Unrecognized("a sensor on the agent's actions")
-    scaled_above = any(step[0] == "scale" for t in above for step in _flatten(t))
+    scaled_above = any(step[0] == "scale" for t in above for step in flatten(t))
     record_raw = action.coef is not None and not scaled_above
 
     scaling, update, strides = None, 0, []
@@ -292,11 +280,8 @@ def _build_replay(pieces, E):
 # 4. the phase
 # ----------------------------------------------------------------------------------------------------------------------
 def _notice(reason, expected=False):
-    if reason not in ops._NOTIFIED:
-        ops._NOTIFIED.add(reason)
-        log = ops._LOG.info if expected else ops._LOG.warning
-        log("the device-resident collection step does not implement %s: the collection phase runs the per-step loop of "
-            "Worker.rollout", reason)
+    notice("the device-resident collection step does not implement %s: the collection phase runs the per-step loop of "
+           "Worker.rollout", reason, expected)
 
 
 def _kernel_tier(worker, agent):
@@ -320,7 +305,7 @@ def _kernel_tier(worker, agent):
     env = geo.env
     if env.stepper.device < 0:
         return loop("the CPU twin of the KS stepper")
-    if torch.device("cuda", env.stepper.device) != torch.empty(0, device=agent.device).device:
+    if not same_device(torch.device("cuda", env.stepper.device), agent.device):
         return loop("an agent and an env on different devices")
     from pdecontrol.mbrl import collect_hip as co
     from pdecontrol.sac import sac_hip
@@ -356,9 +341,9 @@ class _Buffers:
 
     def matches(self, agent, geo):
         env = geo.env
-        return ((self.device, self.E, self.N, self.A, self.O, self.sensor) ==
-                (torch.empty(0, device=agent.device).device, env.num_envs, env.N, geo.action.width, geo.agent_obs.width,
-                 (geo.agent_obs.start, geo.agent_obs.stride))
+        return (same_device(self.device, agent.device)
+                and (self.E, self.N, self.A, self.O, self.sensor) ==
+                (env.num_envs, env.N, geo.action.width, geo.agent_obs.width, (geo.agent_obs.start, geo.agent_obs.stride))
                 and tuple(self.noise.shape[1:]) == (agent.policy.achannels, agent.policy.aheight))
 
     def layout(self, T):
@@ -405,7 +390,6 @@ def _host_step(worker, agent, deterministic):
 def _run_segment(worker, agent, fused, geo, buf, T, steps):
     """``T`` steps without a truncation in HBM, from the state the worker and the stack hold, written back to them."""
     from pdecontrol.mbrl import collect_hip as co
-    from pdecontrol.sac import sac_hip
     env, scaling = geo.env, geo.scaling
     E, N = buf.E, buf.N
     (traj, actions, pobs, bounds, ssq, status), (h_traj, h_actions, h_pobs, h_bounds, h_ssq, h_status), used = buf.views(T)
@@ -431,16 +415,14 @@ def _run_segment(worker, agent, fused, geo, buf, T, steps):
         env.stepper.set_stream(current.cuda_stream)
         env._stream_handle = current.cuda_stream
     env._set_objective(env.proto.step_objective)
-    fused.refresh(need_adam=fused._keys[1] if fused._keys else False)
-    stream, forward = co.stream(), sac_hip.load().sac_policy_forward
-    cfg, state = ctypes.byref(fused.cfg), ctypes.byref(fused.state)
-    p_obs, p_noise, p_action = (sac_hip._ptr(t) for t in (pobs, buf.noise, buf.action))
+    fused.refresh_current()
+    stream, forward = co.stream(), fused.forward_launcher(E, pobs, buf.noise, buf.action)
     d_env_action, substeps = buf.env_action.data_ptr(), env.cfg_steps
     row, slot = E * N * 4, traj.data_ptr()
     d_ssq, d_status = ssq.data_ptr(), status.data_ptr()
     for t in range(T):                                    # eager launches, ``t`` by value, no host synchronisation
         buf.noise.normal_()                               # the draw of ``SAC.act``: same call, shape and device
-        sac_hip._check(forward(stream, cfg, state, E, p_obs, p_noise, p_action, None, None))
+        forward()
         co.act(stream, geometry, act_args, t)
         env.stepper.step_device(d_actions=d_env_action, n_substeps=substeps, d_obs=slot + (t + 1) * row,
                                 d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)

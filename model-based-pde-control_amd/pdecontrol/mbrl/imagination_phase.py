@@ -32,7 +32,6 @@ every episode.  With ``sink=`` (a ``DeviceExperienceReplay``, pdecontrol/mbrl/de
 writes the samples into the sink's slabs instead, one ``rp_append`` launch per round, and returns the ``StagedRollout`` that
 ``sink.extend`` commits: nothing is copied back and nothing is built on the host.
 """
-import ctypes
 import time
 from collections import deque
 from dataclasses import dataclass
@@ -41,7 +40,8 @@ import numpy as np
 import torch
 
 from pdecontrol.mbrl.device_replay import DeviceExperienceReplay, episode_keys
-from pdecontrol.mbrl.policy_phase import FieldMap, Unrecognized, _flatten, field_map
+from pdecontrol.mbrl.recognition import (FieldMap, Unrecognized, action_store, field_map, is_forcing, notice, observation_store,
+                                         one_channel_each, same_device, updates_statistics)
 from pdecontrol.mbrl.replay import ExperienceReplay
 from pdecontrol.mbrl.worker import Worker
 from pdecontrol.surrogates import ops
@@ -70,19 +70,6 @@ class StackGeometry:
     reward: FieldMap
 
 
-def _is_forcing(t):
-    if isinstance(t, tr.BatchTransform):
-        t = t.transform
-    return t if type(t) is tr.GaussianForcing else None
-
-
-def _updates_statistics(wrapper):
-    """A ``TransformActionWrapper`` whose step changes its transform: not frozen, over a scaling that is not frozen."""
-    if wrapper.frozen or _is_forcing(wrapper.transform) is not None:
-        return False
-    return any(step[0] == "scale" and not step[1].frozen for step in _flatten(wrapper.transform))
-
-
 def recognize_stack(stack):
     """``StackGeometry`` of the controller's imagined-rollout stack (mbrl.py:321-329), or raises ``Unrecognized``:
     ``StoreNActionsVecWrapper`` outermost, then ``TransformActionWrapper``s that flatten to at most one scaling, exactly
@@ -92,16 +79,13 @@ def recognize_stack(stack):
     from pdecontrol.mbrl.world.world import WorldVecEnv
     from pdegym.kuramoto import KuramotoSivashinskyEnv
     env = stack.envs
-    if type(env) is not vw.StoreNActionsVecWrapper or env is not stack.astore:
-        raise Unrecognized(f"a {type(env).__name__} in place of the action store on top of the stack")
-    if env.num_steps != 1:
-        raise Unrecognized(f"an action store of {env.num_steps} steps")
+    action_store(env, stack, f"a {type(env).__name__} in place of the action store on top of the stack")
     env = env.env
     before, forcing, after = [], None, []
     while type(env) is vw.TransformActionWrapper:
-        if _updates_statistics(env):
+        if updates_statistics(env):
             raise Unrecognized("an action transform that updates its statistics")
-        f = _is_forcing(env.transform)
+        f = is_forcing(env.transform)
         if f is not None:
             if forcing is not None:
                 raise Unrecognized("two forcings")
@@ -115,16 +99,10 @@ def recognize_stack(stack):
     while type(env) is vw.TransformObsWrapper:
         sensors.append(env.transform)
         env = env.env
-    if type(env) is not vw.StoreNObsVecWrapper or env is not stack.ostore:
-        raise Unrecognized(f"a {type(env).__name__} in place of the observation store")
-    if env.num_steps != 1:
-        raise Unrecognized(f"an observation store of {env.num_steps} steps")
-    world = env.env
+    world = observation_store(env, stack)
     if not isinstance(world, WorldVecEnv):
         raise Unrecognized(f"a {type(world).__name__} in place of the WorldVecEnv")
-    oshape, ashape = tuple(world.single_observation_space.shape), tuple(world.single_action_space.shape)
-    if len(oshape) != 2 or oshape[0] != 1 or len(ashape) != 2 or ashape[0] != 1:
-        raise Unrecognized(f"a world with observations {oshape} and actions {ashape} (one channel each)")
+    N, W = one_channel_each(world, "a world")
     matrix = forcing.forcing.detach().cpu()
     if matrix.dtype != torch.float32 or matrix.dim() != 2:
         raise Unrecognized("a forcing matrix that is not fp32 [A, N]")
@@ -133,12 +111,12 @@ def recognize_stack(stack):
     if (act_in.start, act_in.stride, act_in.width) != (0, 1, A):
         raise Unrecognized("a sensor on the agent's actions")
     act_out = field_map(tr.Operation(after), L)
-    if act_out.width != ashape[1]:
-        raise Unrecognized(f"an action stack that yields {act_out.width} columns for a world that takes {ashape[1]}")
-    agent_obs = field_map(tr.Operation(list(reversed(sensors))), oshape[1])
+    if act_out.width != W:
+        raise Unrecognized(f"an action stack that yields {act_out.width} columns for a world that takes {W}")
+    agent_obs = field_map(tr.Operation(list(reversed(sensors))), N)
     if agent_obs.coef is not None:
         raise Unrecognized("a scaling on the agent's observations")
-    reward = field_map(world.stransf.otransf, oshape[1])
+    reward = field_map(world.stransf.otransf, N)
     if (reward.start, reward.stride) != (0, 1):
         raise Unrecognized("a world whose observation connector carries a sensor of stride above 1")
     owner = getattr(world.batched_reward_func, "__self__", None)
@@ -146,8 +124,8 @@ def recognize_stack(stack):
         raise Unrecognized("a world without the batched reward of a KuramotoSivashinskyEnv")
     if not owner.objective:
         raise Unrecognized("the dissipation objective")
-    if owner.N != oshape[1]:
-        raise Unrecognized(f"a reward over {owner.N} grid points for observations of {oshape[1]}")
+    if owner.N != N:
+        raise Unrecognized(f"a reward over {owner.N} grid points for observations of {N}")
     return StackGeometry(world, act_in, matrix.contiguous(), act_out, agent_obs, reward)
 
 
@@ -186,7 +164,6 @@ class _CapturedStep:
 
     def __init__(self, agent, fused, geo):
         from pdecontrol.mbrl import rollout_hip as ro
-        from pdecontrol.sac import sac_hip
         from pdecontrol.surrogates.graph_step import capture_graph
         from pdecontrol.surrogates.hipops import pooled_streams
         world = geo.world
@@ -228,10 +205,8 @@ class _CapturedStep:
         tstep = world.tstep
 
         def step():
-            stream = sac_hip._stream()
-            sac_hip._check(sac_hip.load().sac_policy_forward(
-                stream, ctypes.byref(fused.cfg), ctypes.byref(fused.state), B, sac_hip._ptr(self.policy_obs), sac_hip._ptr(self.noise),
-                sac_hip._ptr(self.action), None, None))
+            fused.forward_launcher(B, self.policy_obs, self.noise, self.action)()
+            stream = ro.stream()
             ro.act_chain(stream, self.geometry, act_args)
             outs = []
             for sur, hid in zip(dev.members, dev.hidden):
@@ -292,10 +267,8 @@ class _CapturedStep:
 # 3. the phase
 # ----------------------------------------------------------------------------------------------------------------------
 def _notice(reason):
-    if reason not in ops._NOTIFIED:
-        ops._NOTIFIED.add(reason)
-        ops._LOG.warning("the fused imagined-rollout step does not implement %s: the imagined-rollout phase runs the "
-                         "per-step loop of Worker.rollout", reason)
+    notice("the fused imagined-rollout step does not implement %s: the imagined-rollout phase runs the per-step loop of "
+           "Worker.rollout", reason)
 
 
 def _kernel_tier(agent, stack):
@@ -315,7 +288,7 @@ def _kernel_tier(agent, stack):
                 "no batched reward, or a starting-state dataset it cannot pack)")
         return None, None
     from pdecontrol.mbrl.world.world import _members, _surrogate_device
-    if _surrogate_device(world.surrogate) != torch.empty(0, device=agent.device).device:
+    if not same_device(_surrogate_device(world.surrogate), agent.device):
         _notice("an agent and a world on different devices")
         return None, None
     A, L = (int(v) for v in geo.forcing.shape)
@@ -422,7 +395,7 @@ def imagine(agent, stack, num_rollouts, deterministic=False, timings=None, noise
         return clock()
 
     t = clock()
-    fused.refresh(need_adam=fused._keys[1] if fused._keys else False)
+    fused.refresh_current()
     world._reset_state()                         # the fresh worker's reset; (re)builds the device world state if stale
     cap = getattr(world, "_imagination", None)
     if cap is None or not cap.valid(fused, geo):
@@ -439,7 +412,7 @@ def imagine(agent, stack, num_rollouts, deterministic=False, timings=None, noise
         from pdecontrol.mbrl import replay_hip
         import hipbind
         replay_hip.load()
-        if sink.device != torch.empty(0, device=device).device:
+        if not same_device(sink.device, device):
             raise ValueError(f"the sink lives on {sink.device}, the imagined rollouts on {device}")
         staged = sink.stage(B, cap.N, cap.A, expect=num_rounds * B * cap.T)
         buffers = getattr(cap, "sink_buffers", None)

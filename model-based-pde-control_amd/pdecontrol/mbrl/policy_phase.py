@@ -25,11 +25,11 @@ left where the loader would leave it, and the agent ends where the reference loo
 """
 import time
 from dataclasses import dataclass
-from typing import Optional
 
 import numpy as np
 import torch
 
+from pdecontrol.mbrl.recognition import FieldMap, Unrecognized, field_map, notice
 from pdecontrol.mbrl.types import Sample
 from pdecontrol.surrogates import ops
 from pdecontrol.surrogates.common.dataset import DeviceSubSeqStore
@@ -124,98 +124,10 @@ class PolicyBatchPlan:
 # ----------------------------------------------------------------------------------------------------------------------
 # 3. transform recognition
 # ----------------------------------------------------------------------------------------------------------------------
-class Unrecognized(Exception):
-    """A connector the fused gather does not implement; ``str()`` is the reason."""
-
-
-@dataclass
-class FieldMap:
-    """What a recognised chain does to the last axis of a field: output column j reads input column
-    ``start + j * stride`` and maps it through ``((v - a) / (b - a)) * (d - c) + c`` with ``coef[:, j]`` =
-    (a, b - a, d - c, c); ``coef`` None is the identity."""
-    start: int
-    stride: int
-    width: int
-    coef: Optional[torch.Tensor]
-
-    def apply_numpy(self, values):
-        """The map in numpy, in the four separately rounded fp32 steps of ``ScaleTransform._affine``."""
-        v = np.asarray(values, dtype=np.float32)[..., self.start::self.stride][..., :self.width]
-        if self.coef is None:
-            return v.copy()
-        a, ba, dc, c = (self.coef[i].numpy() for i in range(4))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return (((v - a) / ba) * dc + c).astype(np.float32)
-
-
 @dataclass
 class Connector:
     obs: FieldMap
     actions: FieldMap
-
-
-def _flatten(t):
-    """The chain as a list of ("sensor", stride) / ("scale", ScaleTransform, inverse) steps."""
-    if t is None or isinstance(t, tr.Identity):
-        return []
-    if isinstance(t, tr.Operation):
-        return [step for inner in t.transforms for step in _flatten(inner)]
-    if isinstance(t, tr._OperationInverse):
-        return [step for inner in t.transfs for step in _flatten(inner)]
-    if isinstance(t, tr._BatchInverse):
-        return _flatten(t.transform)
-    if isinstance(t, tr.BatchTransform):
-        return _flatten(t.transform)
-    if isinstance(t, tr.SensorTransform):
-        return [("sensor", int(t.stride))]
-    if type(t) is tr.ScaleTransform:
-        return [("scale", t, False)]
-    if type(t) is tr._InverseView:
-        inner = t.transf
-        if isinstance(inner, tr.Identity):
-            return []
-        if type(inner) is tr.ScaleTransform:
-            return [("scale", inner, True)]
-        if isinstance(inner, tr.SensorTransform) and int(inner.stride) == 1:
-            return []
-        raise Unrecognized(f"the inverse of a {type(inner).__name__}")
-    raise Unrecognized(f"a {type(t).__name__}")
-
-
-def _columns(stat, width, what):
-    stat = torch.as_tensor(stat).detach().cpu()
-    if stat.dtype != torch.float32:
-        raise Unrecognized(f"a ScaleTransform with {what} in {str(stat.dtype).replace('torch.', '')}")
-    if stat.numel() == 1:
-        return stat.reshape(1).expand(width)
-    if stat.shape[-1] == width and stat.numel() == width:
-        return stat.reshape(width)
-    raise Unrecognized(f"a ScaleTransform whose {what} of shape {tuple(stat.shape)} is not one value or one per column")
-
-
-def field_map(chain, width):
-    """``FieldMap`` of a chain over a field whose rows are ``width`` columns wide; raises ``Unrecognized``."""
-    start, stride, coef = 0, 1, None
-    for step in _flatten(chain):
-        if step[0] == "sensor":
-            r = step[1]
-            if r < 1:
-                raise Unrecognized(f"a SensorTransform of stride {r}")
-            start, stride = start + (r // 2) * stride, stride * r
-            if coef is not None:
-                coef = coef[:, r // 2::r]
-            width = len(range(r // 2, width, r))
-            if width < 1:
-                raise Unrecognized("sensors that leave no column")
-        else:
-            if coef is not None:
-                raise Unrecognized("two scalings in a row")
-            _, scale, inverse = step
-            vmin, vmax, lower, upper = (torch.as_tensor(s).detach().cpu() for s in (scale.vmin, scale.vmax, scale.lower, scale.upper))
-            a, b, c, d = (lower, upper, vmin, vmax) if inverse else (vmin, vmax, lower, upper)
-            coef = torch.stack([_columns(a, width, "bounds"), _columns(b - a, width, "bounds"),
-                                _columns(d - c, width, "bounds"), _columns(c, width, "bounds")])
-    return FieldMap(start, stride, width, None if coef is None else coef.contiguous())
 
 
 def recognize(stransf, obs_width, act_width):
@@ -254,10 +166,8 @@ def _connector(dataset):
 # 4. the phase
 # ----------------------------------------------------------------------------------------------------------------------
 def _notice(reason):
-    if reason not in ops._NOTIFIED:
-        ops._NOTIFIED.add(reason)
-        ops._LOG.warning("the fused batch gather does not implement %s: the policy-update phase assembles its batches "
-                         "with plain PyTorch-ROCm kernels", reason)
+    notice("the fused batch gather does not implement %s: the policy-update phase assembles its batches with plain "
+           "PyTorch-ROCm kernels", reason)
 
 
 def _merge(parts, positions, B):

@@ -1,0 +1,153 @@
+"""What the controller's three device-resident phases (policy_phase.py, imagination_phase.py, collection_phase.py) share
+when they decide whether the kernels implement a connector or a wrapper stack: transform chains reduced to a column
+sensor and per-column affine coefficients, the checks both stack recognisers make, and the once-per-reason notice of a
+phase that runs on its other tier."""
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from pdecontrol.surrogates import ops
+from pdegym.common import transforms as tr
+from pdegym.common import vec_wrappers as vw
+
+
+class Unrecognized(Exception):
+    """A connector or a stack the kernels do not implement; ``str()`` is the reason."""
+
+
+@dataclass
+class FieldMap:
+    """What a recognised chain does to the last axis of a field: output column j reads input column
+    ``start + j * stride`` and maps it through ``((v - a) / (b - a)) * (d - c) + c`` with ``coef[:, j]`` =
+    (a, b - a, d - c, c); ``coef`` None is the identity."""
+    start: int
+    stride: int
+    width: int
+    coef: Optional[torch.Tensor]
+
+    def apply_numpy(self, values):
+        """The map in numpy, in the four separately rounded fp32 steps of ``ScaleTransform._affine``."""
+        v = np.asarray(values, dtype=np.float32)[..., self.start::self.stride][..., :self.width]
+        if self.coef is None:
+            return v.copy()
+        a, ba, dc, c = (self.coef[i].numpy() for i in range(4))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (((v - a) / ba) * dc + c).astype(np.float32)
+
+
+def flatten(t):
+    """The chain as a list of ("sensor", stride) / ("scale", ScaleTransform, inverse) steps."""
+    if t is None or isinstance(t, tr.Identity):
+        return []
+    if isinstance(t, tr.Operation):
+        return [step for inner in t.transforms for step in flatten(inner)]
+    if isinstance(t, tr._OperationInverse):
+        return [step for inner in t.transfs for step in flatten(inner)]
+    if isinstance(t, tr._BatchInverse):
+        return flatten(t.transform)
+    if isinstance(t, tr.BatchTransform):
+        return flatten(t.transform)
+    if isinstance(t, tr.SensorTransform):
+        return [("sensor", int(t.stride))]
+    if type(t) is tr.ScaleTransform:
+        return [("scale", t, False)]
+    if type(t) is tr._InverseView:
+        inner = t.transf
+        if isinstance(inner, tr.Identity):
+            return []
+        if type(inner) is tr.ScaleTransform:
+            return [("scale", inner, True)]
+        if isinstance(inner, tr.SensorTransform) and int(inner.stride) == 1:
+            return []
+        raise Unrecognized(f"the inverse of a {type(inner).__name__}")
+    raise Unrecognized(f"a {type(t).__name__}")
+
+
+def _columns(stat, width, what):
+    stat = torch.as_tensor(stat).detach().cpu()
+    if stat.dtype != torch.float32:
+        raise Unrecognized(f"a ScaleTransform with {what} in {str(stat.dtype).replace('torch.', '')}")
+    if stat.numel() == 1:
+        return stat.reshape(1).expand(width)
+    if stat.shape[-1] == width and stat.numel() == width:
+        return stat.reshape(width)
+    raise Unrecognized(f"a ScaleTransform whose {what} of shape {tuple(stat.shape)} is not one value or one per column")
+
+
+def field_map(chain, width):
+    """``FieldMap`` of a chain over a field whose rows are ``width`` columns wide; raises ``Unrecognized``."""
+    start, stride, coef = 0, 1, None
+    for step in flatten(chain):
+        if step[0] == "sensor":
+            r = step[1]
+            if r < 1:
+                raise Unrecognized(f"a SensorTransform of stride {r}")
+            start, stride = start + (r // 2) * stride, stride * r
+            if coef is not None:
+                coef = coef[:, r // 2::r]
+            width = len(range(r // 2, width, r))
+            if width < 1:
+                raise Unrecognized("sensors that leave no column")
+        else:
+            if coef is not None:
+                raise Unrecognized("two scalings in a row")
+            _, scale, inverse = step
+            vmin, vmax, lower, upper = (torch.as_tensor(s).detach().cpu() for s in (scale.vmin, scale.vmax, scale.lower, scale.upper))
+            a, b, c, d = (lower, upper, vmin, vmax) if inverse else (vmin, vmax, lower, upper)
+            coef = torch.stack([_columns(a, width, "bounds"), _columns(b - a, width, "bounds"),
+                                _columns(d - c, width, "bounds"), _columns(c, width, "bounds")])
+    return FieldMap(start, stride, width, None if coef is None else coef.contiguous())
+
+
+# ---- what both stack recognisers check -------------------------------------------------------------------------------
+def is_forcing(t):
+    if isinstance(t, tr.BatchTransform):
+        t = t.transform
+    return t if type(t) is tr.GaussianForcing else None
+
+
+def updates_statistics(wrapper):
+    """A ``TransformActionWrapper`` whose step changes its transform: not frozen, over a scaling that is not frozen."""
+    if wrapper.frozen or is_forcing(wrapper.transform) is not None:
+        return False
+    return any(step[0] == "scale" and not step[1].frozen for step in flatten(wrapper.transform))
+
+
+def action_store(env, stack, otherwise):
+    """``env`` is the one-step ``StoreNActionsVecWrapper`` that is ``stack.astore``; ``otherwise`` is the reason when it
+    is not that store."""
+    if type(env) is not vw.StoreNActionsVecWrapper or env is not stack.astore:
+        raise Unrecognized(otherwise)
+    if env.num_steps != 1:
+        raise Unrecognized(f"an action store of {env.num_steps} steps")
+
+
+def observation_store(env, stack):
+    """``env`` is the one-step ``StoreNObsVecWrapper`` that is ``stack.ostore``; returns what it wraps."""
+    if type(env) is not vw.StoreNObsVecWrapper or env is not stack.ostore:
+        raise Unrecognized(f"a {type(env).__name__} in place of the observation store")
+    if env.num_steps != 1:
+        raise Unrecognized(f"an observation store of {env.num_steps} steps")
+    return env.env
+
+
+def one_channel_each(env, what):
+    """(observation columns, action columns) of ``env`` (``what``: "a world", "an env"), one channel each."""
+    oshape, ashape = tuple(env.single_observation_space.shape), tuple(env.single_action_space.shape)
+    if len(oshape) != 2 or oshape[0] != 1 or len(ashape) != 2 or ashape[0] != 1:
+        raise Unrecognized(f"{what} with observations {oshape} and actions {ashape} (one channel each)")
+    return oshape[1], ashape[1]
+
+
+def same_device(a, b):
+    """``a``, a device with its index, is the device ``b`` names ("cuda" is the current device)."""
+    return a == torch.empty(0, device=b).device
+
+
+def notice(sentence, reason, expected=False):
+    """Logs ``sentence % reason`` the first time ``reason`` is met: a warning, or an info line for an ``expected`` one."""
+    if reason not in ops._NOTIFIED:
+        ops._NOTIFIED.add(reason)
+        (ops._LOG.info if expected else ops._LOG.warning)(sentence, reason)

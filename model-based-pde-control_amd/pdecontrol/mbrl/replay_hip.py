@@ -1,6 +1,6 @@
-"""ctypes binding of libreplay_hip.so (C ABI: include/replay_hip.h and include/replay/replay_slab_hip.h ``rp_*``; kernel:
-csrc/replay.hip): the fused batch gather of the policy-update phase, and the append and episode returns of the
-device-resident replay (pdecontrol/mbrl/device_replay.py).  ``rp_supported`` and ``rp_last_error`` are pure host functions and work without a GPU.
+"""ctypes binding of libreplay_hip.so (C ABI: include/replay_hip.h ``rp_*``; kernel: csrc/replay.hip): the fused batch
+gather of the policy-update phase, and the append and episode returns of the device-resident replay
+(pdecontrol/mbrl/device_replay.py).  ``rp_supported`` and ``rp_last_error`` are pure host functions and work without a GPU.
 A missing library raises: the kernel tier of pdecontrol/mbrl/policy_phase.py has no silent fallback.
 """
 import ctypes
@@ -23,7 +23,7 @@ class Source(ctypes.Structure):
 
 
 class Slab(ctypes.Structure):
-    """``rp_slab`` of include/replay/replay_slab_hip.h"""
+    """``rp_slab`` of include/replay_hip.h"""
     _fields_ = [("obs", _p), ("actions", _p), ("nxtobs", _p), ("rewards", _p), ("terminated", _p), ("truncated", _p),
                 ("steps", _p), ("rows", _l)]
 
@@ -32,12 +32,9 @@ _src = ctypes.POINTER(Source)
 SYMBOLS = (
     ("rp_supported", _i, [_i, _src, _i]),
     ("rp_gather", _i, [_p, _i, _src, _i, _p, _p, _p, _p, _p, _p]),
-    ("rp_last_error", ctypes.c_char_p, []),
-)
-# the library's second header, include/replay/replay_slab_hip.h
-SLAB_SYMBOLS = (
     ("rp_append", _i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, ctypes.POINTER(Slab)]),
     ("rp_episode_returns", _i, [_p, _p, _l, _p, _l, _p, _i, _p]),
+    ("rp_last_error", ctypes.c_char_p, []),
 )
 _lib = None
 
@@ -49,12 +46,15 @@ class ReplayHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + SLAB_SYMBOLS, ReplayHipError, "The fused batch gather has no fallback.")
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, ReplayHipError, "The fused batch gather has no fallback.")
     return _lib
 
 
 def last_error():
     return load().rp_last_error().decode(errors="replace")
+
+
+_check = hipbind.checker(ReplayHipError, "libreplay_hip", "rp_last_error", lambda: load())
 
 
 def sources(entries):
@@ -70,10 +70,8 @@ def supported(srcs, B):
 def gather(stream, srcs, B, rows_ptr, obs, actions, nxtobs, rewards, terminated):
     """One launch on ``stream`` (a raw hipStream_t): ``rows_ptr`` is the device address of B int64 rows, the outputs are
     fp32 device tensors [B, obs_dim], [B, act_dim], [B, obs_dim], [B], [B]."""
-    rc = load().rp_gather(stream, len(srcs), srcs, int(B), rows_ptr, obs.data_ptr(), actions.data_ptr(), nxtobs.data_ptr(),
-                          rewards.data_ptr(), terminated.data_ptr())
-    if rc != 0:
-        raise ReplayHipError(f"libreplay_hip error {rc}: {last_error()}")
+    _check(load().rp_gather(stream, len(srcs), srcs, int(B), rows_ptr, obs.data_ptr(), actions.data_ptr(), nxtobs.data_ptr(),
+                            rewards.data_ptr(), terminated.data_ptr()))
 
 
 def slab(tensors):
@@ -88,16 +86,12 @@ def append(stream, block_ptr, T, T_cap, B, N, A, dst_ptr, dst_host, slab_struct)
     go to the rows ``dst_ptr`` (device int64 [T][B]) names; ``dst_host`` is the contiguous int64 numpy array it was
     uploaded from, validated against the slab before the launch."""
     assert dst_host.dtype.kind == "i" and dst_host.dtype.itemsize == 8 and dst_host.flags.c_contiguous and dst_host.size == T * B
-    rc = load().rp_append(stream, block_ptr, int(T), int(T_cap), int(B), int(N), int(A), dst_ptr, dst_host.ctypes.data,
-                          ctypes.byref(slab_struct))
-    if rc != 0:
-        raise ReplayHipError(f"libreplay_hip error {rc}: {last_error()}")
+    _check(load().rp_append(stream, block_ptr, int(T), int(T_cap), int(B), int(N), int(A), dst_ptr, dst_host.ctypes.data,
+                            ctypes.byref(slab_struct)))
 
 
 def episode_returns(stream, rewards, rows, offsets, returns):
     """One ``rp_episode_returns`` launch on ``stream``: ``rewards`` the slab's fp32 [slab rows], ``rows`` int64 [n] and
     ``offsets`` int64 [E + 1] device tensors, ``returns`` fp32 [E]."""
-    rc = load().rp_episode_returns(stream, rewards.data_ptr(), int(rewards.numel()), rows.data_ptr(), int(rows.numel()),
-                                   offsets.data_ptr(), int(offsets.numel()) - 1, returns.data_ptr())
-    if rc != 0:
-        raise ReplayHipError(f"libreplay_hip error {rc}: {last_error()}")
+    _check(load().rp_episode_returns(stream, rewards.data_ptr(), int(rewards.numel()), rows.data_ptr(), int(rows.numel()),
+                                     offsets.data_ptr(), int(offsets.numel()) - 1, returns.data_ptr()))

@@ -1,4 +1,4 @@
-"""ctypes binding of librollout_hip.so (C ABI: include/rollout/rollout_hip.h ``ro_*``; kernels: csrc/rollout.hip): the
+"""ctypes binding of librollout_hip.so (C ABI: include/rollout_hip.h ``ro_*``; kernels: csrc/rollout.hip): the
 action chain and the settle kernel of the captured imagined step.  ``ro_supported`` and ``ro_last_error`` are pure host
 functions and work without a GPU.  A missing library raises: the kernel tier of pdecontrol/mbrl/imagination_phase.py has
 no silent fallback.
@@ -16,7 +16,7 @@ _p, _i = ctypes.c_void_p, ctypes.c_int
 
 
 class Geometry(ctypes.Structure):
-    """``ro_geometry`` of include/rollout/rollout_hip.h"""
+    """``ro_geometry`` of include/rollout_hip.h"""
     _fields_ = [("B", _i), ("T", _i), ("N", _i), ("A", _i), ("L", _i), ("act_start", _i), ("act_stride", _i),
                 ("obs_start", _i), ("obs_stride", _i), ("members", _i)]
 

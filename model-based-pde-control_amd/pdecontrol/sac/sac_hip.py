@@ -224,6 +224,10 @@ class FusedSAC:
         st.act_scale, st.act_bias = self.scale.data_ptr(), self.bias.data_ptr()
         self.cfg, self.state = cfg, st
 
+    def refresh_current(self):
+        """``refresh`` for a launch that needs the Adam moments only where the structs already hold them."""
+        self.refresh(need_adam=self._keys[1] if self._keys else False)
+
     def workspace(self, B):
         if B not in self.work:
             n = load().sac_workspace_floats(self.obs_dim, self.act_dim, self.cfg.hidden, B)
@@ -264,7 +268,7 @@ class FusedSAC:
     # ---- launches ---------------------------------------------------------------------------------------------------
     def forward(self, obs, noise, want_logp=False, want_mean=False):
         """obs [B, obs_dim] fp32 on the device; noise [B, act_dim] or None.  Returns (action, logp or None, mean or None)."""
-        self.refresh(need_adam=self._keys[1] if self._keys else False)
+        self.refresh_current()
         B = obs.shape[0]
         action = torch.empty((B, self.act_dim), dtype=torch.float32, device=obs.device)
         logp = torch.empty((B, 1), dtype=torch.float32, device=obs.device) if want_logp else None
@@ -272,6 +276,21 @@ class FusedSAC:
         _check(load().sac_policy_forward(_stream(), ctypes.byref(self.cfg), ctypes.byref(self.state), B, _ptr(obs), _ptr(noise),
                                          _ptr(action), _ptr(logp), _ptr(mean)))
         return action, logp, mean
+
+    def forward_launcher(self, B, obs, noise, action):
+        """A zero-argument callable that launches the policy forward of ``B`` rows from the static buffers ``obs`` and
+        ``noise`` into ``action`` (no log-probability, no mean) and raises on a non-zero status.  The structs as they
+        stand (``refresh_current`` first), the pointers and the raw handle of torch's current stream are resolved here,
+        once: a call costs the launch alone."""
+        forward, stream = load().sac_policy_forward, _stream()
+        cfg, state = ctypes.byref(self.cfg), ctypes.byref(self.state)
+        p_obs, p_noise, p_action = _ptr(obs), _ptr(noise), _ptr(action)
+
+        def launch():
+            rc = forward(stream, cfg, state, B, p_obs, p_noise, p_action, None, None)
+            if rc != 0:
+                _check(rc)
+        return launch
 
     def launch_update(self, obs, actions, nxtobs, rewards, terminated, noise_next, noise_cur):
         """The five launches of one update on the current stream (no host bookkeeping: ``update`` / ``update_many`` do it)."""
@@ -290,7 +309,7 @@ class FusedSAC:
         """The test hook ``sac_grads``: ({critic name: grad}, {policy name: grad}, log_alpha grad or None, statistics);
         no parameter, moment, counter or target is written."""
         a = self.agent
-        self.refresh(need_adam=self._keys[1] if self._keys else False)
+        self.refresh_current()
         self.sync_in()
         gc = [torch.zeros_like(p) for p in a.critic.parameters()]
         gp = [torch.zeros_like(p) for p in a.policy.parameters()]

@@ -21,6 +21,8 @@ HEADERS = [
     ("delay_hip.h", "libdelay_hip.so", "dly", ["pdecontrol.surrogates.delay_hip"]),
     ("sac_hip.h", "libsac_hip.so", "sac", ["pdecontrol.sac.sac_hip"]),
     ("replay_hip.h", "libreplay_hip.so", "rp", ["pdecontrol.mbrl.replay_hip"]),
+    ("rollout_hip.h", "librollout_hip.so", "ro", ["pdecontrol.mbrl.rollout_hip"]),
+    ("collect_hip.h", "libcollect_hip.so", "co", ["pdecontrol.mbrl.collect_hip"]),
 ]
 
 

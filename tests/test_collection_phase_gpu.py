@@ -29,7 +29,7 @@ def test_co_act_equals_the_host_wrapper(A):
     """The stepper's action rows and the action-store record, bit for bit: with and without the affine map, env-side and
     raw record; only slot ``t`` of ``actions`` is written."""
     from pdecontrol.mbrl import collect_hip as co
-    from pdecontrol.mbrl.policy_phase import field_map
+    from pdecontrol.mbrl.recognition import field_map
     from pdegym.common import transforms as T
     dev, stream = _dev(), None
     rs = np.random.RandomState(A)

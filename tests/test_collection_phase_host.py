@@ -16,7 +16,7 @@ from test_capi_symbols import LIBDIR, declared_functions  # noqa: E402
 
 from pdecontrol.mbrl import collect_hip as co  # noqa: E402
 from pdecontrol.mbrl import collection_phase as cp  # noqa: E402
-from pdecontrol.mbrl.policy_phase import Unrecognized  # noqa: E402
+from pdecontrol.mbrl.recognition import Unrecognized  # noqa: E402
 from pdecontrol.mbrl.replay import ExperienceReplay  # noqa: E402
 from pdecontrol.mbrl.types import Sample  # noqa: E402
 
@@ -25,13 +25,11 @@ from pdecontrol.mbrl.types import Sample  # noqa: E402
 # header and binding
 # ----------------------------------------------------------------------------------------------------------------------
 def test_collect_library_exports_what_its_header_declares():
-    names = declared_functions(os.path.join("collect", "collect_hip.h"), "co")
-    assert names == ["co_act", "co_last_error", "co_observe", "co_supported", "co_workspace_floats"]
-    assert sorted(n for n, _, _ in co.SYMBOLS) == names
-    path = os.path.join(LIBDIR, "libcollect_hip.so")
-    assert os.path.exists(path), "libcollect_hip.so not built (run __graft_entry__.build())"
-    handle = ctypes.CDLL(path)
-    assert not [n for n in names if not hasattr(handle, n)]
+    """(that the binding's table holds exactly these names and the library exports them: tests/test_capi_symbols.py,
+    which skips without the library where this test fails)"""
+    assert declared_functions("collect_hip.h", "co") == ["co_act", "co_last_error", "co_observe", "co_supported",
+                                                         "co_workspace_floats"]
+    assert os.path.exists(os.path.join(LIBDIR, "libcollect_hip.so")), "libcollect_hip.so not built (run __graft_entry__.build())"
 
 
 def test_collect_geometry_refusals_are_numbered():

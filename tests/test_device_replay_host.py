@@ -1,7 +1,7 @@
 """The device-resident replay without a GPU (pdecontrol/mbrl/device_replay.py with ``device="cpu"``): metadata and contents
 against ``ExperienceReplay`` call for call, the allocator (holes, split episodes, growth, discard), the dataset view against
-``SubSeqDataset`` in the policy-update phase, ``statistics`` bit for bit, and the host-side refusals of the two entries of
-include/replay/replay_slab_hip.h.  Rollout rounds and the numpy twin of ``rp_append``: tests/_device_replay_scenario.py."""
+``SubSeqDataset`` in the policy-update phase, ``statistics`` bit for bit, and the host-side refusals of ``rp_append`` and
+``rp_episode_returns`` (include/replay_hip.h).  Rollout rounds and the numpy twin of ``rp_append``: tests/_device_replay_scenario.py."""
 import ctypes
 import os
 import re
@@ -13,6 +13,7 @@ import torch
 import _device_replay_scenario as sc
 import _policy_phase_scenario as pp_sc
 import _sac_models as sm
+from test_capi_symbols import declared_functions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "model-based-pde-control_amd", "lib", "libreplay_hip.so")
@@ -283,20 +284,15 @@ def test_imagine_with_a_sink_on_the_loop_tier_returns_the_host_replay():
 # header, binding and the host-side refusals
 # ---------------------------------------------------------------------------------------------------------------------
 def test_slab_header_binding_and_library_agree():
-    """The second header of libreplay_hip.so lives in include/replay/ ; its functions are the binding's second table and the
-    library's exports, and its struct is the binding's."""
+    """The slab entries are declared beside the gather's, and the header's struct is the binding's (that the binding's
+    table holds exactly these names and the library exports them: tests/test_capi_symbols.py)."""
     from pdecontrol.mbrl import replay_hip
-    text = open(os.path.join(ROOT, "include", "replay", "replay_slab_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
-    names = sorted(set(re.findall(r"\b(rp_[a-z0-9_]+)\s*\(", text)))
-    assert names == ["rp_append", "rp_episode_returns"] == sorted(n for n, _, _ in replay_hip.SLAB_SYMBOLS)
+    assert declared_functions("replay_hip.h", "rp") == ["rp_append", "rp_episode_returns", "rp_gather", "rp_last_error",
+                                                        "rp_supported"]
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "replay_hip.h")).read(), flags=re.S)
     fields = re.search(r"typedef struct rp_slab \{(.*?)\} rp_slab;", text, re.S).group(1)
     declared = [n for decl in fields.split(";") for n in re.findall(r"\*?\s*([a-z_]+)\s*(?:,|$)", decl.strip())]
     assert declared == [n for n, _ in replay_hip.Slab._fields_]
-    if not os.path.exists(LIB):
-        pytest.skip("libreplay_hip.so not built (run __graft_entry__.build())")
-    handle = ctypes.CDLL(LIB)
-    assert not [n for n in names if not hasattr(handle, n)]
 
 
 def test_append_and_episode_returns_refuse_before_any_device_call():

@@ -22,15 +22,10 @@ DEVICE_REWARD = {"batched_reward_func": lambda env: env.batched_reward_func}
 
 
 def test_rollout_library_exports_what_its_header_declares():
-    """The header lives in include/rollout/ ; its functions are the binding's table and the library's exports."""
-    from pdecontrol.mbrl import rollout_hip
-    names = declared_functions(os.path.join("rollout", "rollout_hip.h"), "ro")
-    assert names == ["ro_act_chain", "ro_last_error", "ro_settle", "ro_supported"]
-    assert sorted(n for n, _, _ in rollout_hip.SYMBOLS) == names
-    path = os.path.join(LIBDIR, "librollout_hip.so")
-    assert os.path.exists(path), "librollout_hip.so not built (run __graft_entry__.build())"
-    handle = ctypes.CDLL(path)
-    assert not [n for n in names if not hasattr(handle, n)]
+    """(that the binding's table holds exactly these names and the library exports them: tests/test_capi_symbols.py,
+    which skips without the library where this test fails)"""
+    assert declared_functions("rollout_hip.h", "ro") == ["ro_act_chain", "ro_last_error", "ro_settle", "ro_supported"]
+    assert os.path.exists(os.path.join(LIBDIR, "librollout_hip.so")), "librollout_hip.so not built (run __graft_entry__.build())"
 
 
 def test_rollout_geometry_refusals_are_numbered():
@@ -79,7 +74,7 @@ def test_ro_act_chain_equals_the_host_wrappers(N, A, stride):
     chain (an Intel MKL; tests/conftest.py::require_fma_sgemm says why other hosts round it differently); a host where it
     does not is reported with a TOLERANT MODE warning.  N = 98 (no multiple of 4) and stride 4 take the scalar path."""
     from pdecontrol.mbrl import rollout_hip as ro
-    from pdecontrol.mbrl.policy_phase import field_map
+    from pdecontrol.mbrl.recognition import field_map
     from pdegym.common import transforms as T
     dev = torch.device("cuda", 0)
     ro.load()
@@ -129,7 +124,7 @@ def test_ro_settle_picks_records_and_rewards(N, obs_stride):
     within 2^-23 relative of the fp64 host value of (-1.0) * (1.0 / N) * sum(w^2) (one fp32 rounding of the result plus
     the reordering of an fp64 sum of at most 1024 non-negative terms, which is below 2^-43)."""
     from pdecontrol.mbrl import rollout_hip as ro
-    from pdecontrol.mbrl.policy_phase import field_map
+    from pdecontrol.mbrl.recognition import field_map
     from pdegym.common import transforms as T
     dev = torch.device("cuda", 0)
     ro.load()

@@ -147,7 +147,7 @@ def test_the_controllers_stack_is_recognised(M):
 
 def test_unrecognised_stacks_name_their_reason(M):
     from pdecontrol.mbrl import imagination_phase as ip
-    from pdecontrol.mbrl.policy_phase import Unrecognized
+    from pdecontrol.mbrl.recognition import Unrecognized
     T = M.T
     s = sc.build(M, world_kwargs=DEVICE_REWARD)
     tf, world = s.transforms, s.world

@@ -105,7 +105,8 @@ def test_cpu_phase_with_zero_updates_does_nothing():
 def test_header_binding_and_library_agree():
     """(that the header declares exactly the bound names and the library exports them: tests/test_capi_symbols.py)"""
     from pdecontrol.mbrl import replay_hip
-    assert sorted(n for n, _, _ in replay_hip.SYMBOLS) == ["rp_gather", "rp_last_error", "rp_supported"]
+    assert sorted(n for n, _, _ in replay_hip.SYMBOLS) == ["rp_append", "rp_episode_returns", "rp_gather", "rp_last_error",
+                                                           "rp_supported"]
     header = open(os.path.join(ROOT, "include", "replay_hip.h")).read()
     for macro, value in (("RP_MAX_SOURCES", replay_hip.MAX_SOURCES), ("RP_MAX_OBS_DIM", replay_hip.MAX_OBS_DIM),
                          ("RP_MAX_ACT_DIM", replay_hip.MAX_ACT_DIM)):
@@ -204,6 +205,7 @@ def test_sensor_before_scaling_and_inverse_connectors_are_recognised():
 
 def test_other_transforms_are_reported_unrecognised():
     from pdecontrol.mbrl import policy_phase as pp
+    from pdecontrol.mbrl.recognition import Unrecognized
     from pdegym.common.transforms import (BatchTransform, FuncTransform, GaussianForcing, Normalize, ScaleTransform,
                                           SensorTransform, SampleTransform)
     scale = ScaleTransform(bounds=(-1.0, 1.0), frozen=True)
@@ -215,7 +217,7 @@ def test_other_transforms_are_reported_unrecognised():
             ("two scalings", SampleTransform(otransf=[scale, SensorTransform(1), BatchTransform(scale)])),
             ("inverse of a SensorTransform", SampleTransform(otransf=SensorTransform(2)).Inverse),
             ("float", lambda sample: sample)):
-        with pytest.raises(pp.Unrecognized) as e:
+        with pytest.raises(Unrecognized) as e:
             pp.recognize(stransf, 64, 4)
         assert str(e.value), what
         if what in ("Normalize", "FuncTransform", "GaussianForcing", "two scalings"):
