@@ -169,6 +169,26 @@ int ks_sync(ks_handle* h);
 int ks_reward_rows_device(ks_handle* h, int objective, const float* d_obs, const float* d_phi, int n_rows,
                           double* d_reward);
 
+/* Replaces: KSBatchedVecEnv._finish_step + Sample.split + ExperienceReplay.add (pdecontrol/mbrl/types.py,
+ * pdecontrol/mbrl/replay.py) for the T * num_envs transitions of T consecutive steps without a truncation, read where
+ * ks_step_device left its outputs and written as rows of a device-resident replay.  ks_record is a HOST struct of DEVICE
+ * pointers, the seven slabs: obs / nxtobs fp32 [rows, N], actions fp32 [rows, A], rewards fp32 [rows], terminated /
+ * truncated bytes [rows], steps int [rows].  Transition (t, e) writes row d_dst[t][e] (a negative entry writes nothing):
+ * obs = traj[t][e], nxtobs = traj[t + 1][e], the action and steps of (t, e), terminated = truncated = 0 and
+ * rewards = (float)((c * ssq[t][e]) / (double)n_substeps), c = -1.0 * (1.0 / (double)N): numpy's
+ * (-1.0) * (1 / N) * ssq / cfg_steps cast to fp32, bit for bit.  dst_host is d_dst on the host: every refusal (NULL
+ * pointers, T < 1, A outside 1 ... 16, n_substeps < 1, slabs without rows, an entry >= rows, a row named twice) is made
+ * from it before any HIP call.  Enqueued on the handle's stream; it does not synchronise and does not allocate device
+ * memory.  On the CPU twin host pointers, synchronous. */
+typedef struct ks_record {
+    float* obs; float* actions; float* nxtobs; float* rewards;
+    unsigned char* terminated; unsigned char* truncated; int* steps; long rows;
+} ks_record;
+
+int ks_record_device(ks_handle* h, const float* d_traj /* [T+1][E][N] */, const float* d_actions /* [T][E][A] */, int A,
+                     const double* d_ssq /* [T][E] */, const int* d_steps /* [T][E] */, int T, long n_substeps,
+                     const long* d_dst /* [T][E] */, const long* dst_host, const ks_record* out);
+
 /* ---- test hooks -------------------------------------------------------------------------- */
 
 /* Replaces: KuramotoSivashinskyEnv.rhs (kuramoto.py:118-129) on a batch, in the reference's

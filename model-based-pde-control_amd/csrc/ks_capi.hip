@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "../../include/kspde.h"
 #include "capi_error.h"
@@ -664,6 +665,62 @@ int ks_reward_rows_device(ks_handle* h, int objective, const float* d_obs, const
     }
     DeviceGuard g(h->device);
     KS_HIP(ks::launch_reward_rows(objective, d_obs, d_phi, n_rows, h->N, h->dx, d_reward, h->stream));
+    return KS_OK;
+}
+
+int ks_record_device(ks_handle* h, const float* d_traj, const float* d_actions, int A, const double* d_ssq,
+                     const int* d_steps, int T, long n_substeps, const long* d_dst, const long* dst_host,
+                     const ks_record* out) {
+    // everything is refused here, before any HIP call
+    if (!h) return fail(KS_ERR_INVALID, "ks_record_device: NULL handle");
+    if (!d_traj || !d_actions || !d_ssq || !d_steps || !d_dst || !dst_host || !out)
+        return fail(KS_ERR_INVALID, "ks_record_device: NULL traj, actions, ssq, steps, dst, dst_host or out");
+    if (!out->obs || !out->actions || !out->nxtobs || !out->rewards || !out->terminated || !out->truncated || !out->steps)
+        return fail(KS_ERR_INVALID, "ks_record_device: the slabs have a NULL field pointer");
+    if (T < 1) return fail(KS_ERR_INVALID, "ks_record_device: %d steps (at least 1)", T);
+    if (A < 1 || A > 16) return fail(KS_ERR_INVALID, "ks_record_device: action width %d (1 ... 16 are supported)", A);
+    if (n_substeps < 1) return fail(KS_ERR_INVALID, "ks_record_device: n_substeps %ld (at least 1)", n_substeps);
+    if (out->rows < 1) return fail(KS_ERR_INVALID, "ks_record_device: slabs of %ld rows (at least 1)", out->rows);
+    if (h->pending) return fail(KS_ERR_INVALID, "ks_record_device: a step is in flight (ks_step_begin without ks_step_end)");
+    const long n = (long)T * h->E;
+    std::vector<bool> seen(static_cast<size_t>(out->rows), false);
+    for (long i = 0; i < n; ++i) {
+        const long r = dst_host[i];
+        if (r < 0) continue;
+        if (r >= out->rows)
+            return fail(KS_ERR_INVALID, "ks_record_device: dst[%ld] = %ld is beyond the slabs' %ld rows", i, r, out->rows);
+        if (seen[r]) return fail(KS_ERR_INVALID, "ks_record_device: row %ld is named twice (again at dst[%ld])", r, i);
+        seen[r] = true;
+    }
+    const double scale = -1.0 * (1.0 / (double)h->N);
+    if (h->cpu) {
+        kscpu::record(h->E, h->N, A, n, d_traj, d_actions, d_ssq, d_steps, d_dst, scale, (double)n_substeps, out->obs,
+                      out->actions, out->nxtobs, out->rewards, out->terminated, out->truncated, out->steps);
+        return KS_OK;
+    }
+    ks::RecordArgs a = {};
+    a.traj = d_traj;
+    a.actions = d_actions;
+    a.ssq = d_ssq;
+    a.steps = d_steps;
+    a.dst = d_dst;
+    a.obs = out->obs;
+    a.act = out->actions;
+    a.nxtobs = out->nxtobs;
+    a.rewards = out->rewards;
+    a.terminated = out->terminated;
+    a.truncated = out->truncated;
+    a.out_steps = out->steps;
+    a.rows = out->rows;
+    a.n = n;
+    a.E = h->E;
+    a.N = h->N;
+    a.A = A;
+    a.scale = scale;
+    a.substeps = (double)n_substeps;
+    DeviceGuard g(h->device);
+    const hipError_t e = ks::launch_record(a, h->stream);
+    if (e != hipSuccess) return fail(KS_ERR_HIP, "ks_record_device: launch failed: %s", hipGetErrorString(e));
     return KS_OK;
 }
 

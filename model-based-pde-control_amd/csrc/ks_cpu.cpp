@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <cstdlib>
 #include <thread>
 #include <vector>
@@ -317,6 +318,21 @@ void reward_rows(int N, double dx, int objective, const float* obs, const float*
             for (int i = 0; i < N; ++i) sup += uu[i] * uu[i];
             out[r] = (-1.0) * (1.0 / N) * sup;
         }
+    }
+}
+
+void record(int E, int N, int A, long n, const float* traj, const float* actions, const double* ssq, const int* steps,
+            const long* dst, double scale, double substeps, float* obs, float* act, float* nxtobs, float* rewards,
+            unsigned char* terminated, unsigned char* truncated, int* out_steps) {
+    for (long w = 0; w < n; ++w) {
+        const long r = dst[w];
+        if (r < 0) continue;
+        std::memcpy(obs + r * N, traj + w * N, sizeof(float) * N);
+        std::memcpy(nxtobs + r * N, traj + (w + E) * N, sizeof(float) * N);
+        std::memcpy(act + r * A, actions + w * A, sizeof(float) * A);
+        rewards[r] = (float)((scale * ssq[w]) / substeps);
+        out_steps[r] = steps[w];
+        terminated[r] = truncated[r] = 0;
     }
 }
 

@@ -34,6 +34,12 @@ void rhs(int N, double dx, double dx2, double dx4, const double* u, const float*
 // Per-row reward of fp32 obs [n_rows, N] with fp32 phi (nullptr = 0) -> out [n_rows] (ks_reward_rows_device).
 void reward_rows(int N, double dx, int objective, const float* obs, const float* phi, int n_rows, double* out);
 
+// ks_record_device on host memory: transition w = t * E + e of [T][E] goes to row dst[w] of the seven slabs (a negative
+// dst writes nothing); reward (float)((scale * ssq[w]) / substeps).
+void record(int E, int N, int A, long n, const float* traj, const float* actions, const double* ssq, const int* steps,
+            const long* dst, double scale, double substeps, float* obs, float* act, float* nxtobs, float* rewards,
+            unsigned char* terminated, unsigned char* truncated, int* out_steps);
+
 // Host threads the twin uses by default: the affinity mask, capped by KSPDE_CPU_THREADS.
 int default_threads();
 

@@ -47,6 +47,27 @@ hipError_t launch_step(const Layout& lay, int mode, int objective, const StepArg
 // per-row reward of fp32 obs [n,N] with fp32 phi [n,N] (phi may be null) -> fp64 out [n] (device pointers)
 hipError_t launch_reward_rows(int objective, const float* obs, const float* phi, int n_rows, int N, double dx,
                               double* out, hipStream_t stream);
+// ks_record_device: transition w = t * E + e of a segment goes to replay row dst[w] (device pointers; `scale` is
+// -1.0 * (1.0 / N), formed on the host)
+struct RecordArgs {
+    const float* traj;      // [T + 1][E][N]
+    const float* actions;   // [T][E][A]
+    const double* ssq;      // [T][E]
+    const int* steps;       // [T][E]
+    const long* dst;        // [T][E]
+    float* obs;
+    float* act;
+    float* nxtobs;
+    float* rewards;
+    unsigned char* terminated;
+    unsigned char* truncated;
+    int* out_steps;
+    long rows, n;           // slab rows; T * E
+    int E, N, A;
+    int vec_obs, vec_act;
+    double scale, substeps;
+};
+hipError_t launch_record(const RecordArgs& a, hipStream_t stream);
 // rhs test hook: u [n,N], phi [n,N] -> outputs [n,N] (device pointers; ux/uxx/uxxxx may be null)
 hipError_t launch_rhs(const double* u, const float* phi, int n_rows, int N, double dx, double dx2,
                       double dx4, double* rhs, double* ux, double* uxx, double* uxxxx,

@@ -27,6 +27,14 @@ VARIANT_NAME = {v: k for k, v in VARIANT.items()}
 _c = ctypes
 _H = _c.c_void_p
 _dp, _fp, _ip = _c.POINTER(_c.c_double), _c.POINTER(_c.c_float), _c.POINTER(_c.c_int)
+
+
+class ks_record(_c.Structure):
+    """``ks_record``: a host struct of the seven slab pointers of a device-resident replay and their rows."""
+    _fields_ = [("obs", _c.c_void_p), ("actions", _c.c_void_p), ("nxtobs", _c.c_void_p), ("rewards", _c.c_void_p),
+                ("terminated", _c.c_void_p), ("truncated", _c.c_void_p), ("steps", _c.c_void_p), ("rows", _c.c_long)]
+
+
 SYMBOLS = (
     ("ks_create", _c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.POINTER(_H)]),
     ("ks_destroy", _c.c_int, [_H]),
@@ -50,6 +58,8 @@ SYMBOLS = (
                                   _c.c_void_p, _c.c_void_p]),
     ("ks_sync", _c.c_int, [_H]),
     ("ks_reward_rows_device", _c.c_int, [_H, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    ("ks_record_device", _c.c_int, [_H, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_long,
+                                    _c.c_void_p, _c.c_void_p, _c.POINTER(ks_record)]),
     ("ks_rhs", _c.c_int, [_H, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                           _c.c_void_p]),
     ("ks_selftest", _c.c_int, [_H, _c.POINTER(_c.c_uint)]),
@@ -230,6 +240,18 @@ class KSStepper:
         vp = lambda x: ctypes.c_void_p(int(x)) if x else None
         _check(self._lib.ks_reward_rows_device(self._h, OBJECTIVE[objective], vp(d_obs), vp(d_phi), int(n_rows),
                                                vp(d_reward)))
+
+    def record_device(self, d_traj, d_actions, A, d_ssq, d_steps, T, n_substeps, d_dst, dst_host, slabs):
+        """The T * num_envs transitions of T steps without a truncation into replay rows; see ks_record_device.  Raw
+        device pointers (ints; host pointers on the CPU twin), ``dst_host`` a C-contiguous int64 array [T, num_envs],
+        ``slabs`` a ``ks_record``.  Enqueued on the handle's stream."""
+        vp = lambda x: ctypes.c_void_p(int(x)) if x else None
+        if dst_host is not None:
+            assert dst_host.dtype == np.int64 and dst_host.flags["C_CONTIGUOUS"] and dst_host.size == int(T) * self.num_envs, \
+                (dst_host.dtype, dst_host.shape, T, self.num_envs)
+        _check(self._lib.ks_record_device(self._h, vp(d_traj), vp(d_actions), int(A), vp(d_ssq), vp(d_steps), int(T),
+                                          int(n_substeps), vp(d_dst), _ptr(dst_host),
+                                          None if slabs is None else ctypes.byref(slabs)))
 
     def sync(self):
         _check(self._lib.ks_sync(self._h))

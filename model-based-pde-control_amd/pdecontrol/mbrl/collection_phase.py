@@ -28,6 +28,14 @@ In both tiers everything the loop mutates ends where the loop leaves it: the wor
 scaling's bounds, ``env.timestep``, the stepper's state, the env's MT19937 streams, numpy's and torch's generators, and
 the calls to ``callback.on_rollout_end``.  The worker is not reset between calls: consecutive ``collect`` calls continue
 the running episodes as consecutive ``rollout`` calls do.
+
+``collect(..., sink=replay)`` (``replay`` a ``DeviceExperienceReplay``) returns a ``StagedRollout`` that
+``replay.extend(staged)`` commits, in place of the host ``ExperienceReplay``.  On the kernel tier a segment's transitions
+go from the block into the sink's slabs with one ``ks_record_device`` launch (csrc/ks_record.hip) after its T steps, on the
+same stream: the rewards are formed on the device, only what the write-back needs comes back to the host (the last
+observation row, the last action row, the policy's observation, the bounds and the status), and no host replay is built.
+A truncation step's ``Sample`` is packed, uploaded and placed like a host replay's rows.  On the loop tier the loop's host
+replay is staged through ``_stage_host``.
 """
 import gc
 from collections import deque
@@ -38,6 +46,7 @@ from typing import Any, List, Optional
 import numpy as np
 import torch
 
+from pdecontrol.mbrl.device_replay import _DTYPES, _Episode, _carve, _rows_of, _same_device
 from pdecontrol.mbrl.recognition import (FieldMap, Unrecognized, action_store, field_map, flatten, is_forcing, notice,
                                          observation_store, one_channel_each, same_device, updates_statistics)
 from pdecontrol.mbrl.replay import ExperienceReplay
@@ -338,6 +347,7 @@ class _Buffers:
         self.coef = f32(4, self.A)
         self.block = self.block_host = None
         self.capacity = 0
+        self.index = self.index_host = None               # a sink's [dst int64 TE | steps int32 TE], grown on demand
 
     def matches(self, agent, geo):
         env = geo.env
@@ -371,6 +381,77 @@ class _Buffers:
         return cut(self.block), cut(self.block_host), int(off[-1])
 
 
+    def index_views(self, T):
+        """(device, pinned host) pairs of a segment's ``dst`` (int64 [T, E]) and ``steps`` (int32 [T, E]): one block, so
+        that one copy uploads both."""
+        n = T * self.E
+        words = n + (n + 1) // 2
+        if self.index is None or self.index.numel() < words:
+            self.index = torch.empty(words, dtype=torch.int64, device=self.device)
+            self.index_host = torch.empty(words, dtype=torch.int64).pin_memory()
+        cut = lambda block: (block[:n].view(T, self.E), block[n:words].view(torch.int32)[:n].view(T, self.E))
+        return cut(self.index), cut(self.index_host), words
+
+
+class _SinkPhase:
+    """The ``StagedRollout`` one ``collect(..., sink=)`` call fills on the kernel tier: ``_build_replay``'s keys and
+    ``vindex`` (its ``slot()`` rule, an env moving to the next free key the moment its sample truncates) over rows
+    reserved in the sink's slabs."""
+
+    def __init__(self, sink, E, N, A, expect):
+        self.sink, self.E = sink, E
+        self.staged = sink.stage(E, N, A, expect=expect)
+        self.free = 0
+
+    def _episode(self, e):
+        vindex, eps = self.staged.vindex, self.staged._eps
+        key = vindex.get(e)
+        if key is None:
+            key = vindex[e] = self.free
+            self.free += 1
+        ep = eps.get(key)
+        if ep is None:
+            ep = eps[key] = _Episode()
+        return ep
+
+    def reserve(self, T):
+        """Rows of one segment: int64 ``dst`` [T, E]; env e's T rows are consecutive and join its current episode."""
+        extents = self.sink._reserve(T * self.E)
+        for e, piece in enumerate(_carve(extents, T, self.E)):
+            ep = self._episode(e)
+            ep.extents += piece
+            ep.length += T
+            ep.stopped = False
+        return np.ascontiguousarray(_rows_of(extents).reshape(self.E, T).T)
+
+    def slabs(self):
+        """``ks_record`` of the sink's slabs as they stand (after the segment's reservation: a reservation may grow them)."""
+        import kspde
+        t = self.sink.tensors
+        return kspde.ks_record(*(x.data_ptr() for x in t), self.sink.rows)
+
+    def host_step(self, sample):
+        """One host step's ``Sample`` of E rows, packed, uploaded and placed with ``index_copy_`` (``_stage_host``'s
+        way); an env whose row ends its episode moves to the next free key."""
+        sink, E = self.sink, self.E
+        rows = _rows_of(sink._reserve(E))
+        index = torch.from_numpy(rows).to(sink.device)
+        packed = [np.asarray(field, dtype=dt).reshape((E,) + tuple(slab.shape[1:]))
+                  for field, dt, slab in zip(sample, _DTYPES, sink.tensors)]
+        for slab, block in zip(sink.tensors, packed):
+            slab.index_copy_(0, index, torch.from_numpy(block).to(sink.device))
+        terminated, truncated = packed[4], packed[5]
+        for e in range(E):
+            ep = self._episode(e)
+            ep.extents.append((int(rows[e]), 1))
+            ep.length += 1
+            ep.stopped = bool(truncated[e])
+            if terminated[e] or truncated[e]:
+                ep.done = True
+                self.staged.vindex[e] = self.free
+                self.free += 1
+
+
 def _host_step(worker, agent, deterministic):
     """One pass of the loop body of ``Worker.rollout``: the ``Sample`` of ``[E, ...]`` arrays it hands to ``split``."""
     envs, ostore, astore = worker.stack.envs, worker.stack.ostore, worker.stack.astore
@@ -387,8 +468,9 @@ def _host_step(worker, agent, deterministic):
     return Sample(obs, actions, nxtobs, rewards, terminated, truncated, infos["step"])
 
 
-def _run_segment(worker, agent, fused, geo, buf, T, steps):
-    """``T`` steps without a truncation in HBM, from the state the worker and the stack hold, written back to them."""
+def _run_segment(worker, agent, fused, geo, buf, T, steps, phase=None):
+    """``T`` steps without a truncation in HBM, from the state the worker and the stack hold, written back to them.
+    Returns the segment's replay piece, or, with a ``_SinkPhase``, records the transitions in the sink and returns None."""
     from pdecontrol.mbrl import collect_hip as co
     env, scaling = geo.env, geo.scaling
     E, N = buf.E, buf.N
@@ -427,6 +509,24 @@ def _run_segment(worker, agent, fused, geo, buf, T, steps):
         env.stepper.step_device(d_actions=d_env_action, n_substeps=substeps, d_obs=slot + (t + 1) * row,
                                 d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)
         co.observe(stream, geometry, obs_args, t)
+    if phase is not None:
+        A = buf.A
+        dst = phase.reserve(T)
+        (d_dst, d_steps), (h_dst, h_steps), words = buf.index_views(T)
+        h_dst.copy_(torch.from_numpy(dst))
+        h_steps.copy_(torch.from_numpy(np.asarray(steps, dtype=np.int32)))
+        buf.index[:words].copy_(buf.index_host[:words], non_blocking=True)
+        env.stepper.record_device(traj.data_ptr(), actions.data_ptr(), A, d_ssq, d_steps.data_ptr(), T, substeps,
+                                  d_dst.data_ptr(), dst, phase.slabs())
+        # what the write-back needs, nothing else: the last observation row, the last action row, the policy's
+        # observation with the bounds behind it, the status
+        off = buf.layout(T)
+        for a, b in ((off[0] + T * E * N, off[1]), (off[1] + (T - 1) * E * A, off[2]), (off[2], off[4]), (off[6], off[7])):
+            buf.block_host[int(a):int(b)].copy_(buf.block[int(a):int(b)], non_blocking=True)
+        current.synchronize()                             # the segment's one synchronisation
+        _restore(worker, geo, T, h_traj[T].numpy(), h_actions[T - 1].numpy(), h_pobs.numpy(), h_bounds.numpy(),
+                 h_status.numpy())
+        return None
     buf.block_host[:used].copy_(buf.block[:used], non_blocking=True)
     current.synchronize()                                 # the segment's one synchronisation
     return _write_back(worker, geo, T, h_traj.numpy(), h_actions.numpy(), h_pobs.numpy(), h_bounds.numpy(), h_ssq.numpy(),
@@ -436,16 +536,24 @@ def _run_segment(worker, agent, fused, geo, buf, T, steps):
 def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, steps):
     """A segment's host block (views of the pinned staging: copied here) into the state the loop would hold after these
     ``T`` steps -- stores, bounds, ``env.timestep``, the worker's two observations -- and the segment's replay piece."""
+    env = geo.env
+    _restore(worker, geo, T, traj[T], actions[T - 1], policy_obs, bounds, status)
+    traj, actions = traj.copy(), actions.copy()
+    rewards = (-1.0) * (1 / env.N) * ssq / env.cfg_steps  # ``KSBatchedVecEnv._finish_step``, every step at once
+    return traj, actions, rewards, steps
+
+
+def _restore(worker, geo, T, last_obs, last_actions, policy_obs, bounds, status):
+    """The state the loop would hold after these ``T`` steps, from views of the pinned staging (copied here): ``last_obs``
+    [E, N] the observations the last step ends with, ``last_actions`` [E, A] its recorded actions."""
     env, scaling = geo.env, geo.scaling
     ostore, astore = worker.stack.ostore, worker.stack.astore
     bad = np.nonzero(status.any(axis=1))[0]
     if bad.size:
         env._raise_on(status[bad[0]])                     # the first step that shows an overflow, as the loop raises it
-    traj, actions = traj.copy(), actions.copy()
-    rewards = (-1.0) * (1 / env.N) * ssq / env.cfg_steps  # ``KSBatchedVecEnv._finish_step``, every step at once
-    ostore.obs[:, -1] = traj[T][:, None, :]
+    ostore.obs[:, -1] = last_obs[:, None, :]
     ostore.mask[:, -1] = True
-    astore.actions[:, -1] = actions[T - 1][:, None, :]
+    astore.actions[:, -1] = last_actions[:, None, :]
     astore.mask[:, -1] = True
     if geo.update:
         cell = 2 * (T & 1)                                # step T - 1 wrote cell T & 1
@@ -454,20 +562,42 @@ def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, 
     env.timestep += T
     worker._last_obs = policy_obs.copy()
     worker._last_stored_obs = _stored(ostore, ostore.obs)
-    return traj, actions, rewards, steps
 
 
-def collect(worker, agent, stop, deterministic=False):
+def _check_sink(sink, agent, kernel):
+    """The sink is a ``DeviceExperienceReplay`` on the agent's device, or (loop tier only) on the CPU."""
+    from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
+    if not isinstance(sink, DeviceExperienceReplay):
+        raise ValueError(f"collect() takes a DeviceExperienceReplay as its sink, not a {type(sink).__name__}")
+    device = getattr(agent, "device", None)
+    if kernel:
+        if not _same_device(sink.device, device):
+            raise ValueError(f"the sink is on {sink.device} and the agent on {device}: the kernels write the agent's device")
+    elif sink.device.type != "cpu" and device is not None and not _same_device(sink.device, device):
+        raise ValueError(f"the sink is on {sink.device} and the agent on {device}: a sink is on the agent's device or on "
+                         f"the CPU")
+
+
+def collect(worker, agent, stop, deterministic=False, sink=None):
     """The ``ExperienceReplay`` ``worker.rollout(agent, stop, deterministic)`` returns, with everything the loop mutates
     left where the loop leaves it (module docstring).  The result carries ``tier`` ("loop" or "kernel"), ``tier_reason``
     (why the loop ran; None on the kernel tier) and ``host_steps`` (steps that went through the stack on the host: all of
     them on the loop tier, the truncation steps on the kernel tier).  ``deterministic`` reaches ``agent.select_action``,
-    which a ``SAC`` ignores as the reference's does: both tiers sample."""
+    which a ``SAC`` ignores as the reference's does: both tiers sample.
+
+    ``sink``: a ``DeviceExperienceReplay`` on the agent's device (or on the CPU, for the loop tier).  The result is then,
+    on either tier, a ``StagedRollout`` whose rows are in the sink's slabs and which ``sink.extend(result)`` commits
+    (``result.to_host()`` is the host replay); the worker's callbacks receive ``result.to_host()``.  A step that
+    overflows discards the staged rows before it raises."""
     geo, fused, reason = _kernel_tier(worker, agent)
+    if sink is not None:
+        _check_sink(sink, agent, kernel=geo is not None)
     if geo is None:
         replay = worker.rollout(agent, stop, deterministic)
-        replay.tier, replay.tier_reason, replay.host_steps = "loop", reason, replay.ntimesteps // max(len(replay.vindex), 1)
-        return replay
+        result = replay if sink is None else sink._stage_host(replay)
+        result.tier, result.tier_reason = "loop", reason
+        result.host_steps = replay.ntimesteps // max(len(replay.vindex), 1)
+        return result
     env = geo.env
     E = env.num_envs
     with torch.cuda.device(env.stepper.device):
@@ -479,15 +609,29 @@ def collect(worker, agent, stop, deterministic=False):
         if buf is None or not buf.matches(agent, geo):
             buf = worker._collect_buffers = _Buffers(agent, geo)
         pieces, host_steps = [], 0
-        for kind, first, n in segments(plan, segment_steps(E, env.N, buf.A)):
-            if kind == "host":
-                pieces.append(_host_step(worker, agent, deterministic))
-                host_steps += 1
-            else:
-                pieces.append(_run_segment(worker, agent, fused, geo, buf, n, plan.steps[first:first + n]))
+        phase = None if sink is None else _SinkPhase(sink, E, env.N, buf.A, plan.K * E)
+        try:
+            for kind, first, n in segments(plan, segment_steps(E, env.N, buf.A)):
+                if kind == "host":
+                    sample = _host_step(worker, agent, deterministic)
+                    host_steps += 1
+                    if phase is None:
+                        pieces.append(sample)
+                    else:
+                        phase.host_step(sample)
+                else:
+                    piece = _run_segment(worker, agent, fused, geo, buf, n, plan.steps[first:first + n], phase)
+                    if phase is None:
+                        pieces.append(piece)
+        except BaseException:
+            if phase is not None and phase.staged.state == "open":
+                sink.discard(phase.staged)                # the rows of a phase that raised are never committed
+            raise
         assert np.array_equal(env.timestep, plan.timestep), "the env counters left the plan"
-    replay = build_replay(pieces, E)
-    replay.tier, replay.tier_reason, replay.host_steps = "kernel", None, host_steps
-    for callback in worker.callbacks:
-        callback.on_rollout_end(replay)
-    return replay
+    result = build_replay(pieces, E) if phase is None else phase.staged
+    result.tier, result.tier_reason, result.host_steps = "kernel", None, host_steps
+    if worker.callbacks:
+        seen = result if phase is None else result.to_host()
+        for callback in worker.callbacks:
+            callback.on_rollout_end(seen)
+    return result

@@ -12,6 +12,21 @@
                              stands in the policy-update phase (pdecontrol/mbrl/policy_phase.py), which reads the slab in
                              place through the item -> physical-row map instead of packing the replay.
 
+
+The same class is the controller's real replay: ``collect(..., sink=)`` writes its segments into the slabs
+with ``ks_record_device`` and every later phase reads them in place:
+
+``replay.data``              a ``Sample`` of seven read-only mappings from episode key to a lazy column: lengths are metadata,
+                             iterating a column fetches it from the slab once.  ``SubSeqDataset``, ``StartingStateDataset``
+                             and ``train_test_split(replay.episodes)`` are built from it unchanged.
+``replay.window_store()``    ``DeviceSubSeqStore``'s surface over the slabs: windows of any length are gathered through a
+                             device map from the packed ("logical") row order to physical rows.
+``replay.transitions()``     what ``ExperienceReplay.dataset()`` returns, as device tensors.
+
+Pack equality: ``DeviceSubSeqStore(host_replay.data, device).tensors`` after the same calls equals the slabs read in logical
+order, field for field and bit for bit (the host deques hold fp64 rewards and int64 steps; every reader casts through
+``_DTYPES``, which is what the slabs hold).
+
 ``device="cpu"`` keeps the same metadata over torch CPU tensors.
 """
 import bisect
@@ -149,6 +164,125 @@ class _SlabStore:
         return stransf(sample) if stransf is not None else sample
 
 
+def _same_device(a, b):
+    a, b = torch.device(a), torch.device(b)
+    if a.type != b.type:
+        return False
+    if a.type != "cuda":
+        return True
+    index = lambda d: torch.cuda.current_device() if d.index is None else d.index
+    return index(a) == index(b)
+
+
+def _stale():
+    return RuntimeError("the replay changed after this snapshot of it was taken: take a new one")
+
+
+class _Column:
+    """One field of one episode of a ``DeviceExperienceReplay``: ``len`` is metadata, iterating (or indexing, or
+    ``np.asarray``) fetches the column from the slab once and yields the items ``to_host()`` holds."""
+    __slots__ = ("_replay", "_field", "_episode", "_version", "_values")
+
+    def __init__(self, replay, field, episode):
+        self._replay, self._field, self._episode = replay, field, episode
+        self._version, self._values = replay._version, None
+
+    def __len__(self):
+        return self._episode.length
+
+    def _fetch(self):
+        if self._values is None:
+            if self._version != self._replay._version:
+                raise _stale()
+            self._values = self._replay._fetch_field(self._field, _rows_of(self._episode.extents))
+        return self._values
+
+    def __iter__(self):
+        return iter(self._fetch())
+
+    def __getitem__(self, i):
+        return self._fetch()[i]
+
+    def __array__(self, dtype=None, copy=None):
+        values = self._fetch()
+        return values if dtype is None else values.astype(dtype, copy=False)
+
+
+class _Columns(defaultdict):
+    """Episode key -> ``_Column`` of one field, in insertion order; read-only, a missing key raises.  (A ``defaultdict``
+    because that is how ``SubSeqDataset`` tells a replay's field from a plain array.)"""
+
+    def __init__(self, replay, field):
+        super().__init__(None)
+        self._replay, self._version = replay, replay._version
+        for key, ep in replay._eps.items():
+            dict.__setitem__(self, key, _Column(replay, field, ep))
+
+    def _read_only(self, *args, **kwargs):
+        raise TypeError("the fields of a DeviceExperienceReplay are read-only: it is filled by extend()")
+
+    __setitem__ = __delitem__ = pop = popitem = clear = update = setdefault = _read_only
+
+    def window_store(self, device):
+        """The replay's ``window_store()`` when ``device`` is where its slabs are, else None (the caller packs)."""
+        if self._version != self._replay._version:
+            raise _stale()
+        if self._replay.tensors is None or not _same_device(device, self._replay.device):
+            return None
+        return self._replay.window_store()
+
+
+class _WindowStore:
+    """``DeviceSubSeqStore``'s surface over the slabs of a ``DeviceExperienceReplay``: ``starts`` and ``total`` of the
+    packed ("logical") row order -- episodes in key-insertion order -- and ``rowmap``, a device int64 map from logical
+    to physical row.  A snapshot: using it after the replay changed raises."""
+
+    def __init__(self, replay):
+        self.replay, self.device, self._version = replay, replay.device, replay._version
+        self.starts, off = {}, 0
+        for key, ep in replay._eps.items():
+            self.starts[key] = off
+            off += ep.length
+        self.total = off
+        self.rowmap = torch.from_numpy(_rows_of([e for ep in replay._eps.values() for e in ep.extents])).to(self.device)
+        self._tensors = self._steps_host = None
+
+    def _fresh(self):
+        if self._version != self.replay._version:
+            raise _stale()
+
+    def gather(self, logical_rows):
+        """The seven fields of these logical rows (a device int64 tensor): two ``index_select``s."""
+        self._fresh()
+        rows = self.rowmap.index_select(0, logical_rows)
+        return [t.index_select(0, rows) for t in self.replay.tensors]
+
+    @property
+    def tensors(self):
+        """The slabs in logical order -- ``DeviceSubSeqStore.tensors`` of the host replay -- gathered on the device
+        once, for readers that want the pack itself."""
+        if self._tensors is None:
+            self._tensors = tuple(self.gather(torch.arange(self.total, device=self.device)))
+        self._fresh()
+        return self._tensors
+
+    @property
+    def steps_host(self):
+        """The steps column on the host, in logical order (synchronises, once)."""
+        if self._steps_host is None:
+            self._fresh()
+            self._steps_host = self.replay.tensors[6].index_select(0, self.rowmap).cpu().numpy()
+        return self._steps_host
+
+    def batch(self, dataset, indices, stransf=None):
+        keys, starts = dataset.locate_many(indices)
+        first = np.asarray([self.starts[k] for k in keys], dtype=np.int64) + starts
+        rows = torch.from_numpy((first[:, None] + np.arange(dataset.length)[None, :]).reshape(-1)).to(self.device)
+        shape = (len(keys), dataset.length)
+        sample = Sample(*(t.reshape(shape + tuple(t.shape[1:])) for t in self.gather(rows)))
+        return stransf(sample) if stransf is not None else sample
+
+
 class StagedRollout:
     """Episodes whose rows are reserved (and written, or about to be, in stream order) in ``sink``'s slabs but not yet part
     of it.  It answers what ``ExperienceReplay.extend`` asks of a rollout: ``episodes`` and ``len(vindex)``."""
@@ -254,6 +388,7 @@ class DeviceExperienceReplay:
         self.obs_width = self.act_width = None
         self._live = self._staged = 0
         self._version = 0
+        self._window_store = None
 
     # -- the slabs -------------------------------------------------------------------------------------------------
     def _set_widths(self, obs_width, act_width):
@@ -422,6 +557,33 @@ class DeviceExperienceReplay:
             return [np.empty((0,), dtype=dt) for dt in _DTYPES]
         index = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(self.device)
         return [t.index_select(0, index).cpu().numpy() for t in self.tensors]
+
+    def _fetch_field(self, field, rows):
+        """One field of these rows as a numpy array (synchronises)."""
+        index = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(self.device)
+        return self.tensors[field].index_select(0, index).cpu().numpy()
+
+    @property
+    def data(self):
+        """``ExperienceReplay.data`` of the replay as it stands: a ``Sample`` of seven read-only mappings from episode
+        key to a lazy column (module docstring).  A snapshot: fetching from it after the replay changed raises."""
+        return Sample(*(_Columns(self, field) for field in range(len(_FIELDS))))
+
+    def window_store(self):
+        """The ``_WindowStore`` of the replay as it stands (one per state of the replay: its readers share it)."""
+        if self.tensors is None:
+            raise ValueError("an empty replay has no rows to gather")
+        if self._window_store is None or self._window_store._version != self._version:
+            self._window_store = _WindowStore(self)
+        return self._window_store
+
+    def transitions(self):
+        """The ``Sample`` ``ExperienceReplay.dataset()`` returns -- all live rows in insertion order, every field fp32
+        -- as tensors on the replay's device (for ``update_delta_transform``)."""
+        if self.tensors is None:
+            return Sample(*(torch.empty(0, dtype=torch.float32, device=self.device) for _ in _FIELDS))
+        rows = torch.from_numpy(_rows_of([e for ep in self._eps.values() for e in ep.extents])).to(self.device)
+        return Sample(*(t.index_select(0, rows).to(torch.float32) for t in self.tensors))
 
     def sample(self, index=None, stransf=None):
         index = np.random.choice(self.episodes) if index is None else index

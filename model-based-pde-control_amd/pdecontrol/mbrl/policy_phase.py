@@ -32,7 +32,7 @@ import torch
 from pdecontrol.mbrl.recognition import FieldMap, Unrecognized, field_map, notice
 from pdecontrol.mbrl.types import Sample
 from pdecontrol.surrogates import ops
-from pdecontrol.surrogates.common.dataset import DeviceSubSeqStore
+from pdecontrol.surrogates.common.dataset import DeviceSubSeqStore, device_store
 from pdegym.common import transforms as tr
 
 
@@ -45,8 +45,9 @@ def _is_view(dataset):
 
 
 def _store(dataset, device):
-    """The tensors the batches of ``dataset`` are gathered from: one pack of its replay, or a view's slabs as they stand."""
-    return dataset.slab_store(device) if _is_view(dataset) else DeviceSubSeqStore(dataset.fields, device)
+    """The tensors the batches of ``dataset`` are gathered from: a view's slabs as they stand, else ``device_store``'s
+    answer (one pack of a host replay; a device-resident replay's rows gathered into packed order on the device)."""
+    return dataset.slab_store(device) if _is_view(dataset) else device_store(dataset.fields, device, DeviceSubSeqStore)
 
 
 class PolicyBatchPlan:

@@ -31,7 +31,7 @@ from torch.utils.data import Dataset, RandomSampler
 
 from pdegym._gym import gym
 from pdecontrol.mbrl.types import ModelRollout, Sample
-from pdecontrol.surrogates.common.dataset import DeviceSubSeqStore, PDEDataLoader
+from pdecontrol.surrogates.common.dataset import PDEDataLoader, device_store
 
 try:  # real gym
     from gym.vector.utils.spaces import batch_space  # type: ignore
@@ -232,8 +232,8 @@ class _DeviceStartingStates:
         self.ds = starting
         first = starting.datasets[0]
         self.length = first.length
-        self.store = DeviceSubSeqStore(first.fields, device)
-        self.steps_host = self.store.tensors[6].cpu().numpy()
+        self.store = device_store(first.fields, device)
+        self.steps_host = self.store.steps_host
         self.stransf = first.stransf
         self.device = device
         sampler = RandomSampler(starting, replacement=True, num_samples=int(1e10))
@@ -259,7 +259,7 @@ class _DeviceStartingStates:
             rows[sel] = first[:, None] + pos[None, :]
         flat = torch.from_numpy(rows.reshape(-1)).to(self.device)
         shape = (len(idx), L)
-        out = [t.index_select(0, flat).reshape(shape + tuple(t.shape[1:])) for t in self.store.tensors]
+        out = [t.reshape(shape + tuple(t.shape[1:])) for t in self.store.gather(flat)]
         out[6] = out[6].to(torch.int32)
         sample = Sample(*out)
         if self.stransf is not None:

@@ -10,7 +10,7 @@ import os
 from typing import List
 
 from pdecontrol._compat.lightning import pl
-from pdecontrol.surrogates.common.dataset import DeviceBatchLoader, DeviceSubSeqStore, PDEDataLoader, SubSeqDataset
+from pdecontrol.surrogates.common.dataset import DeviceBatchLoader, PDEDataLoader, SubSeqDataset, device_store
 from pdecontrol.surrogates.common.schedulers import FuncScheduler, Scheduler
 
 
@@ -38,7 +38,7 @@ class PDEDataModule(pl.LightningDataModule):
                                 bootstrapping=bootstrapping, stransf=self.stransf)
         if self.device_data is not None:
             if self._store is None:
-                self._store = DeviceSubSeqStore(self.data, self.device_data)      # the whole replay, packed once
+                self._store = device_store(self.data, self.device_data)     # the whole replay: packed once, or its slabs
             return DeviceBatchLoader(dataset, self._store, self.batch_size)
         return PDEDataLoader(dataset, batch_size=self.batch_size, shuffle=False, num_workers=0,
                              collate_fn=PDEDataLoader.sample_collate)

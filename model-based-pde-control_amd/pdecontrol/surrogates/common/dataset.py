@@ -177,16 +177,38 @@ class DeviceSubSeqStore:
             np.concatenate([np.asarray(store[k], dtype=dt).reshape(len(store[k]), *np.shape(store[k][0])) for k in keys])
         ).to(self.device)
         self.tensors = tuple(pack(store, dt) for store, dt in zip(fields, _DTYPES))
+        self._steps_host = None
+
+    def gather(self, rows):
+        """The seven fields of these packed rows (a device int64 tensor): one ``index_select`` per field."""
+        return [t.index_select(0, rows) for t in self.tensors]
+
+    @property
+    def steps_host(self):
+        """The steps column on the host, in packed order."""
+        if self._steps_host is None:
+            self._steps_host = self.tensors[6].cpu().numpy()
+        return self._steps_host
 
     def batch(self, dataset: SubSeqDataset, indices, stransf=None):
         keys, starts = dataset.locate_many(indices)
         first = np.asarray([self.starts[k] for k in keys], dtype=np.int64) + starts
         rows = torch.from_numpy((first[:, None] + np.arange(dataset.length)[None, :]).reshape(-1)).to(self.device)
         shape = (len(keys), dataset.length)
-        out = [t.index_select(0, rows).reshape(shape + tuple(t.shape[1:])) for t in self.tensors]
+        out = [t.reshape(shape + tuple(t.shape[1:])) for t in self.gather(rows)]
         out[6] = out[6].to(torch.int32)
         sample = Sample(*out)
         return stransf(sample) if stransf is not None else sample
+
+
+def device_store(fields, device, pack=None):
+    """Where the windows of a replay's ``fields`` are gathered from on ``device``: the replay's own slabs when the fields
+    are the lazy mappings of a device-resident replay that lives there (``DeviceExperienceReplay.data``: nothing is
+    packed or uploaded), else one pack of the host replay (``pack``: ``DeviceSubSeqStore`` or a subclass of it)."""
+    fields = tuple(fields)
+    in_place = getattr(fields[0], "window_store", None)
+    store = in_place(device) if in_place is not None else None
+    return (pack or DeviceSubSeqStore)(fields, device) if store is None else store
 
 
 class DeviceBatchLoader:
