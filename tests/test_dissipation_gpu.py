@@ -1,6 +1,8 @@
-"""The dissipation objective on the MI355X: every instantiated fused layout (and the LDS kernel) against the reference's
-rhs outputs in the fixture and the oracle's trajectory (the pins of test_dissipation_host.py), GPU exact against the CPU
-twin, the env layers, and the world model's per-row reward kernel."""
+"""The dissipation objective on the MI355X: the fused layouts that the four KS_CONFIGS sizes reach (17 of the 40
+instantiated ones: row16 at P = 3, 4, 8, 16, half32 at P = 2, 4, 8, wave64 at P = 1, 2, 4) and the LDS kernel against the
+reference's rhs outputs in the fixture and the oracle's trajectory (the pins of test_dissipation_host.py), GPU exact against
+the CPU twin, the env layers, and the world model's per-row reward kernel.  All 40 layouts, every block size and the
+reward kernel's other lane-group widths run against the oracle in test_ks_geometry_gpu.py."""
 import os
 import sys
 
@@ -13,21 +15,13 @@ from oracle import ks_oracle as ko
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_dissipation_host import DT, _trajectory_sums  # noqa: E402
+from _ks_geometry import supported as _supported  # noqa: E402  (the table of instantiated layouts)
 
 pytestmark = pytest.mark.gpu
 
 FUSED = ["row16_dpp", "row16_bperm", "wave64_dpp", "wave64_bperm", "half32_bperm", "lds"]
 HYBRID = ["wave64_hybrid", "wave64_hybrid1"]
 KS_ERR_UNSUPPORTED = -4
-
-
-def _supported(variant, N):
-    if variant.startswith("wave64_hybrid"):
-        return N == 64
-    P = {"row16": 16, "wave64": 64, "half32": 32}.get(variant.split("_")[0])
-    if P is None:
-        return 9 <= N <= 2048
-    return N % P == 0 and (N // P) in (1, 2, 3, 4, 6, 8, 12, 16)
 
 
 @pytest.fixture(scope="module")

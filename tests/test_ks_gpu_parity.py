@@ -9,19 +9,11 @@ import numpy as np
 import pytest
 
 from conftest import KS_CONFIGS
+from _ks_geometry import supported as _supported      # the table of instantiated layouts
 
 pytestmark = pytest.mark.gpu
 
 FUSED = ["row16_dpp", "row16_bperm", "wave64_dpp", "wave64_bperm", "half32_bperm", "lds", "wave64_hybrid", "wave64_hybrid1"]
-
-
-def _supported(variant, N):
-    if variant.startswith("wave64_hybrid"):
-        return N == 64
-    P = {"row16": 16, "wave64": 64, "half32": 32}.get(variant.split("_")[0])
-    if P is None:
-        return 9 <= N <= 2048
-    return N % P == 0 and (N // P) in (1, 2, 3, 4, 6, 8, 12, 16)
 
 
 @pytest.fixture(scope="module")
