@@ -219,6 +219,27 @@ int sur_tbptt_delta_loss(void* stream, const float* states, long states_bstride,
                          float stdv, float* deltas, float* dd_all, float* hsteploss, float* loss, float* stats,
                          double* partial, unsigned int* ticket);
 
+/* The loss section of validation_step in one launch (reference: pdecontrol/surrogates/training.py:132-174), for the rollout
+ * of sur_chunk_forward.  With decoded[t] = states[:, 0] for t = 0 and out_all[t-1] otherwise (the IC-augmented prediction):
+ *   deltas[b,t]  = ((states[b,t+1] - states[b,t]) / delta - mean) / stdv                     t < T-1, written if non-NULL
+ *   scalars[1]   = delta loss:  mean over (b, t < T-1, i) of (d_all[t,b,i] - deltas[b,t,i])^2
+ *   scalars[0]   = scaled loss: mean over (b, t, i) of (decoded - states)^2
+ *   loss         = unscaled loss: the same mean of (affine(decoded) - affine(states))^2, hsteploss[t] its mean per time
+ *                  step (hsteploss[0] is exactly 0); `decoded` [B,T,1,N] receives affine(decoded) if non-NULL
+ * affine is the inverse observation scaling, inv_coef [4][N] = (a, b - a, d - c, c) per column applied in four separately
+ * rounded fp32 steps (the kernel keeps its multiply and add uncontracted: `decoded` has the bits of the host transform,
+ * and both sides of step 0 go through the same map on the same value, hence hsteploss[0] = 0), or NULL for the identity.  states [B,T,1,N] with element strides as in sur_tbptt_delta_loss; out_all,
+ * d_all [T,B,1,N] time-major as sur_chunk_forward writes them (row T-1 of either is not read); hsteploss [T]; loss [1];
+ * scalars [2]; partial: scratch of 24*T doubles; ticket: one zero-initialised unsigned the kernel leaves at zero.  Squared
+ * errors are fp32, their sums fp64, reduced in a fixed order by the workgroup that arrives last (deterministic).  That
+ * workgroup also ADDS the batch's sums to the caller's epoch accumulator accum [3 + T] doubles (may be NULL): accum[0..2] +=
+ * the unscaled, scaled and delta error sums, accum[3 + t] += the unscaled error sum of step t -- an epoch's metrics are
+ * one copy to the host and a division by counts the host knows.  -1: a bad argument; -2: the launch failed. */
+int sur_val_loss(void* stream, const float* states, long states_bstride, long states_tstride, const float* out_all,
+                 const float* d_all, int b, int t, int n, float delta, float mean, float stdv, const float* inv_coef,
+                 float* deltas, float* decoded, float* hsteploss, float* loss, float* scalars, double* accum, double* partial,
+                 unsigned int* ticket);
+
 /* The integration pass of sur_chunk_forward on its own (out_k = base_k + delta * (d_k * mul + add), surrogate.py:108-117):
  * sur_chunk_forward skips it when called with out_all = NULL, so a caller that needs the integrated predictions of a chunk
  * only for reporting (the last TBPTT chunk: nothing is rolled out from them) can queue it off its critical path. */
@@ -251,6 +272,49 @@ int sur_tbptt_delta_loss_range(void* stream, const float* states, long states_bs
                                int b, int t, int n, float delta, float mean, float stdv, float* deltas, float* dd_all,
                                float* hsteploss, float* loss, float* stats, double* partial, unsigned int* ticket, int t_begin,
                                int t_end);
+
+/* The window gather of the surrogate-update phase: ONE launch assembles the `states` and `actions` of one TBPTT batch from
+ * the packed replay, through the controller's replay-to-world connector (reference: pdecontrol/mbrl/mbrl.py:182-185 applied
+ * per item by SubSeqDataset.__getitem__, common/dataset.py:75-81).  For window b < B and step t < L the source row is
+ * first[b] + t in logical (packed) order, mapped through rowmap[] when rowmap is non-NULL (the slabs of a device-resident
+ * replay) and used as is otherwise:
+ *   states[b][t][j]  = affine(obs[row][obs_start + j * obs_stride], obs_coef[:, j])                       j < No
+ *   actions[b][t][j] = affine(chain(i), act_out_coef[:, j]),  i = act_start + j * act_stride              j < Na
+ *   chain(i)         = acc = a[0] * F[0][i];  acc = fmaf(a[k], F[k][i], acc)  for k = 1 ... A-1,  a[k] = affine(action[row][k],
+ *                      act_in_coef[:, k]) -- or, with forcing == NULL, chain(i) = action[row][i] (act_in_coef is not read)
+ * with No / Na the columns the sensors keep of obs_width / of forcing_width (of act_width without forcing), and
+ * affine(v, (a, b - a, d - c, c)) = ((v - a) / (b - a)) * (d - c) + c in four separately rounded fp32 steps; a NULL coefficient
+ * table ([4][columns]) is the identity.  Outputs are fp32 with element strides (bstride, tstride) between windows / steps,
+ * so one launch fills a contiguous [B, L, 1, N] tensor (L*N, N) or time-major storage (N, B*N).  A logical row outside
+ * [0, total), or a mapped row outside [0, rows), writes NaN to that output row of both outputs and reads nothing.  `first`
+ * is a DEVICE pointer (int64); the launch is enqueued on `stream` without synchronisation or allocation.  float4 loads and
+ * stores are used per output when its sensor has stride 1, start and widths are multiples of four and every base and
+ * stride is 16-byte aligned; the scalar path otherwise. */
+typedef struct sur_window_source {
+    const float* obs;           /* [rows][obs_width]                                                     */
+    const float* actions;       /* [rows][act_width]                                                     */
+    const long* rowmap;         /* [total] logical -> physical row, or NULL (then rows is not read)      */
+    long total;                 /* logical rows                                                          */
+    long rows;                  /* physical rows of obs / actions behind a rowmap                        */
+    int obs_width, obs_start, obs_stride;
+    const float* obs_coef;      /* [4][No] or NULL                                                       */
+    int act_width;              /* A                                                                     */
+    const float* act_in_coef;   /* [4][A] or NULL                                                        */
+    const float* forcing;       /* [A][forcing_width] or NULL                                            */
+    int forcing_width;
+    int act_start, act_stride;
+    const float* act_out_coef;  /* [4][Na] or NULL                                                       */
+} sur_window_source;
+/* Refused on the host before any HIP call, with a message that starts "sur_gather_windows:":
+ *   -1 a NULL src, obs, actions, first, states or actions pointer     -2 B < 1 or L < 1
+ *   -3 obs_width outside 1 ... 1024                                    -4 act_width outside 1 ... 16
+ *   -5 a sensor stride < 1                                             -6 a sensor start outside its row
+ *   -7 states_width / actions_width is not what the sensor yields      -8 forcing_width < 1 (with a forcing)
+ *   -9 total < 1, or rows < 1 behind a rowmap                          -10 an output stride smaller than its row
+ *   -20 the launch failed */
+int sur_gather_windows(void* stream, const sur_window_source* src, const long* first, int b, int l, float* states,
+                       int states_width, long states_bstride, long states_tstride, float* actions, int actions_width,
+                       long actions_bstride, long actions_tstride);
 
 const char* sur_last_error(void);
 

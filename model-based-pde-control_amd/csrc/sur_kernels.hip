@@ -25,11 +25,13 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
 #include "../../include/surrogate_hip.h"
 #include "capi_error.h"
+#include "sur_windows.h"
 
 // Diagnostic build only (-DSUR_STAMP): shader-clock stamps per phase for workgroup 0 of each launch,
 // accumulated in a __device__ buffer nothing else reads (guide section 7, In-kernel stamps).
@@ -1872,6 +1874,108 @@ delta_loss_finalize_kernel(int B, int T, int N, int nsplit, float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The loss section of validation_step as one launch (reference: pdecontrol/surrogates/training.py:132-174; ~15 torch
+// ops per batch): the IC-augmented prediction decoded[t] = states[0] (t = 0) / out_all[t-1], the true deltas through the
+// undscaling forward, the delta loss, the scaled loss, the inverse observation scaling of both sides (the affine map in
+// its four separately rounded steps: val_affine below) and the unscaled loss with its per-step means.
+//   grid = T x nsplit workgroups, row t = time step t of all samples; three fp64 partial sums per workgroup, reduced in a
+//   fixed order by the workgroup that arrives last (ticket counter), which is also the single writer of the caller's
+//   epoch accumulator: accum[0..2] += the batch's (unscaled, scaled, delta) error sums, accum[3 + t] += step t's.
+// ---------------------------------------------------------------------------------------------
+constexpr int VAL_NSUM = 3;   // squared errors: unscaled, scaled, delta
+
+// ScaleTransform._affine's  ((v - a) / (b - a)) * (d - c) + c  in four separately rounded fp32 steps.  This file is built
+// with the compiler's default contraction, under which the _rn intrinsics (plain operators of the compiler's own headers)
+// fuse once inlined; the operators below are written out under a contract(off) of their own, so the multiply and the add
+// stay two roundings and `decoded` has the bits of the host transform.
+__device__ __forceinline__ float val_affine(const float* __restrict__ coef, int n, int i, float v) {
+#pragma clang fp contract(off)
+    if (!coef) return v;
+    const float q = (v - coef[i]) / coef[n + i];
+    const float m = q * coef[2 * n + i];
+    return m + coef[3 * n + i];
+}
+
+__global__ void __launch_bounds__(TPB)
+val_loss_kernel(const float* __restrict__ states, long sb, long st, const float* __restrict__ out_all,
+                const float* __restrict__ d_all, int B, int T, int N, float delta, float mean, float stdv,
+                const float* __restrict__ inv_coef, float* __restrict__ deltas, float* __restrict__ decoded,
+                float* __restrict__ hsteploss, float* __restrict__ loss, float* __restrict__ scalars,
+                double* __restrict__ accum, double* __restrict__ partial, unsigned int* __restrict__ ticket) {
+    __shared__ double red[TPB / 64][VAL_NSUM];
+    __shared__ bool last;
+    const int t = blockIdx.x, per_t = B * N, nsplit = gridDim.y;
+    double acc[VAL_NSUM] = {0.0, 0.0, 0.0};
+    for (int e = blockIdx.y * TPB + threadIdx.x; e < per_t; e += nsplit * TPB) {
+        const int b = e / N, i = e - b * N;
+        const size_t sidx = (size_t)b * sb + (size_t)t * st + i;           // states[b, t] (any batch / time strides)
+        const float s0 = states[sidx];
+        const float dec = t == 0 ? s0 : out_all[((size_t)(t - 1) * B + b) * N + i];
+        const float es = __fsub_rn(dec, s0);
+        const float ud = val_affine(inv_coef, N, i, dec);
+        const float eu = __fsub_rn(ud, val_affine(inv_coef, N, i, s0));
+        if (decoded) decoded[((size_t)b * T + t) * N + i] = ud;
+        acc[0] += (double)__fmul_rn(eu, eu);
+        acc[1] += (double)__fmul_rn(es, es);
+        if (t < T - 1) {
+            const float dl = __fdiv_rn(__fsub_rn(__fdiv_rn(__fsub_rn(states[sidx + st], s0), delta), mean), stdv);
+            if (deltas) deltas[((size_t)b * (T - 1) + t) * N + i] = dl;
+            const float ed = __fsub_rn(d_all[((size_t)t * B + b) * N + i], dl);
+            acc[2] += (double)__fmul_rn(ed, ed);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < VAL_NSUM; ++j) {
+        const double w = wave_sum(acc[j]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < VAL_NSUM) {
+        double v = 0.0;
+        for (int w = 0; w < TPB / 64; ++w) v += red[w][threadIdx.x];
+        partial[((size_t)t * nsplit + blockIdx.y) * VAL_NSUM + threadIdx.x] = v;
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = (atomicAdd(ticket, 1u) == (unsigned)(T * nsplit - 1));
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+
+    // the last workgroup: per-step sums by one thread per step (fixed order over the slices), then the three totals by
+    // threads 0..2 in step order.  The partials are fetched with relaxed device-scope atomic loads (see delta_loss_finish).
+    auto peek = [&](size_t i) { return __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    __shared__ double stage[VAL_NSUM][TPB];
+    double tot = 0.0;
+    for (int t0 = 0; t0 < T; t0 += TPB) {
+        const int tt = t0 + threadIdx.x;
+        double sums[VAL_NSUM] = {0.0, 0.0, 0.0};
+        if (tt < T) {
+            for (int y = 0; y < nsplit; ++y)
+#pragma unroll
+                for (int j = 0; j < VAL_NSUM; ++j) sums[j] += peek(((size_t)tt * nsplit + y) * VAL_NSUM + j);
+            hsteploss[tt] = (float)(sums[0] / per_t);
+            if (accum) accum[VAL_NSUM + tt] += sums[0];
+        }
+#pragma unroll
+        for (int j = 0; j < VAL_NSUM; ++j) stage[j][threadIdx.x] = sums[j];
+        __syncthreads();
+        if (threadIdx.x < VAL_NSUM) {
+            const int lim = T - t0 < TPB ? T - t0 : TPB;
+            for (int i = 0; i < lim; ++i) tot += stage[threadIdx.x][i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < VAL_NSUM) {
+        const double count = (double)per_t * (threadIdx.x == 2 ? T - 1 : T);
+        if (threadIdx.x == 0) *loss = (float)(tot / count);
+        else scalars[threadIdx.x - 1] = (float)(tot / count);
+        if (accum) accum[threadIdx.x] += tot;
+    }
+    if (threadIdx.x == 0) *ticket = 0u;   // ready for the next launch
+}
+
+// ---------------------------------------------------------------------------------------------
 // TBPTT chunk: K x (ConvLSTM cell + decoder + integration), time loop inside the kernel
 // ---------------------------------------------------------------------------------------------
 struct StepLayout {
@@ -3114,6 +3218,60 @@ extern "C" {
 
 const char* sur_last_error(void) { return g_err; }
 
+// ---- the window gather of the surrogate-update phase: validation here, kernel and launcher in sur_windows.hip --------
+static bool win_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }   // NULL counts as aligned
+static int win_width(int n, int start, int stride) { return (n - start + stride - 1) / stride; }
+
+int sur_gather_windows(void* stream, const sur_window_source* src, const long* first, int b, int l, float* states,
+                       int states_width, long states_bstride, long states_tstride, float* actions, int actions_width,
+                       long actions_bstride, long actions_tstride) {
+    if (!src || !first || !states || !actions) return fail(-1, "sur_gather_windows: NULL source, first, states or actions pointer");
+    if (!src->obs || !src->actions) return fail(-1, "sur_gather_windows: the source has a NULL obs or actions pointer");
+    if (b < 1 || l < 1) return fail(-2, "sur_gather_windows: %d windows of %d steps (at least 1 each)", b, l);
+    if (src->obs_width < 1 || src->obs_width > 1024)
+        return fail(-3, "sur_gather_windows: observation width %d (1 ... 1024 are supported)", src->obs_width);
+    if (src->act_width < 1 || src->act_width > 16)
+        return fail(-4, "sur_gather_windows: action width %d (1 ... 16 are supported)", src->act_width);
+    if (src->obs_stride < 1 || src->act_stride < 1)
+        return fail(-5, "sur_gather_windows: sensor strides %d (observations) and %d (actions) (at least 1)", src->obs_stride,
+                    src->act_stride);
+    if (src->forcing && src->forcing_width < 1)
+        return fail(-8, "sur_gather_windows: forcing width %d (at least 1)", src->forcing_width);
+    const int act_row = src->forcing ? src->forcing_width : src->act_width;
+    if (src->obs_start < 0 || src->obs_start >= src->obs_width)
+        return fail(-6, "sur_gather_windows: the observation sensor starts at column %d of %d", src->obs_start, src->obs_width);
+    if (src->act_start < 0 || src->act_start >= act_row)
+        return fail(-6, "sur_gather_windows: the action sensor starts at column %d of %d", src->act_start, act_row);
+    if (src->total < 1 || (src->rowmap && src->rows < 1))
+        return fail(-9, "sur_gather_windows: a replay of %ld logical and %ld physical rows (at least 1)", src->total, src->rows);
+    const int no = win_width(src->obs_width, src->obs_start, src->obs_stride);
+    const int na = win_width(act_row, src->act_start, src->act_stride);
+    if (states_width != no)
+        return fail(-7, "sur_gather_windows: states of %d columns, the observation sensor yields %d", states_width, no);
+    if (actions_width != na)
+        return fail(-7, "sur_gather_windows: actions of %d columns, the action sensor yields %d", actions_width, na);
+    if ((b > 1 && (states_bstride < no || actions_bstride < na)) || (l > 1 && (states_tstride < no || actions_tstride < na)))
+        return fail(-10, "sur_gather_windows: output strides (%ld, %ld) / (%ld, %ld) for rows of %d / %d columns", states_bstride,
+                    states_tstride, actions_bstride, actions_tstride, no, na);
+    SurWindowsArgs k = {};
+    k.obs = src->obs; k.actions = src->actions; k.rowmap = src->rowmap; k.first = first;
+    k.total = src->total; k.rows = src->rowmap ? src->rows : src->total;
+    k.obs_coef = src->obs_coef; k.act_in_coef = src->act_in_coef; k.forcing = src->forcing; k.act_out_coef = src->act_out_coef;
+    k.states = states; k.actions_out = actions;
+    k.s_bstride = states_bstride; k.s_tstride = states_tstride; k.a_bstride = actions_bstride; k.a_tstride = actions_tstride;
+    k.B = b; k.L = l;
+    k.obs_width = src->obs_width; k.obs_start = src->obs_start; k.obs_stride = src->obs_stride; k.No = no;
+    k.A = src->act_width; k.Lf = act_row; k.act_start = src->act_start; k.act_stride = src->act_stride; k.Na = na;
+    k.vec_obs = src->obs_stride == 1 && src->obs_start % 4 == 0 && src->obs_width % 4 == 0 && no % 4 == 0 &&
+                states_bstride % 4 == 0 && states_tstride % 4 == 0 && win_aligned16(src->obs) && win_aligned16(src->obs_coef) &&
+                win_aligned16(states);
+    k.vec_act = src->forcing && src->act_stride == 1 && src->act_start % 4 == 0 && act_row % 4 == 0 && na % 4 == 0 &&
+                actions_bstride % 4 == 0 && actions_tstride % 4 == 0 && win_aligned16(src->forcing) &&
+                win_aligned16(src->act_out_coef) && win_aligned16(actions);
+    const int e = sur_windows_launch(stream, k);
+    return e == 0 ? 0 : fail(-20, "sur_gather_windows launch failed: %s", hipGetErrorString((hipError_t)e));
+}
+
 #ifdef SUR_STAMP
 int sur_debug_stamps(long long* out128, int reset) {
     if (out128 && hipMemcpyFromSymbol(out128, HIP_SYMBOL(sur_stamp_buf), sizeof(long long) * 128) != hipSuccess) return -2;
@@ -3750,6 +3908,22 @@ int sur_tbptt_delta_loss(void* stream, const float* states, long states_bstride,
                          double* partial, unsigned int* ticket) {
     return delta_loss_launch(stream, states, states_bstride, states_tstride, d_all, b, t, n, delta, mean, stdv, deltas, dd_all,
                              hsteploss, loss, stats, partial, ticket, 0, t, "sur_tbptt_delta_loss");
+}
+
+int sur_val_loss(void* stream, const float* states, long states_bstride, long states_tstride, const float* out_all,
+                 const float* d_all, int b, int t, int n, float delta, float mean, float stdv, const float* inv_coef,
+                 float* deltas, float* decoded, float* hsteploss, float* loss, float* scalars, double* accum, double* partial,
+                 unsigned int* ticket) {
+    if (!states || !out_all || !d_all || !hsteploss || !loss || !scalars || !partial || !ticket || b <= 0 || t < 2 || n <= 0)
+        return fail(-1, "sur_val_loss: bad argument (need B > 0, T >= 2, N > 0)");
+    if (states_bstride < n || states_tstride < n) return fail(-1, "sur_val_loss: state strides must be at least N");
+    if (!(delta != 0.0f) || !(stdv > 0.0f)) return fail(-1, "sur_val_loss: delta must be non-zero and std positive");
+    const int nsplit = loss_nsplit(b, n);
+    return launch_checked([&] {
+        hipLaunchKernelGGL(val_loss_kernel, dim3(t, nsplit), dim3(TPB), 0, (hipStream_t)stream, states, states_bstride,
+                           states_tstride, out_all, d_all, b, t, n, delta, mean, stdv, inv_coef, deltas, decoded, hsteploss, loss,
+                           scalars, accum, partial, ticket);
+    }, "val_loss");
 }
 
 int sur_tbptt_delta_loss_range(void* stream, const float* states, long states_bstride, long states_tstride, const float* d_all,

@@ -40,8 +40,8 @@ import numpy as np
 import torch
 
 from pdecontrol.mbrl.device_replay import DeviceExperienceReplay, episode_keys
-from pdecontrol.mbrl.recognition import (FieldMap, Unrecognized, action_store, field_map, is_forcing, notice, observation_store,
-                                         one_channel_each, same_device, updates_statistics)
+from pdecontrol.mbrl.recognition import (FieldMap, Unrecognized, action_maps, action_store, field_map, notice, observation_store,
+                                         one_channel_each, same_device, split_at_forcing, updates_statistics)
 from pdecontrol.mbrl.replay import ExperienceReplay
 from pdecontrol.mbrl.worker import Worker
 from pdecontrol.surrogates import ops
@@ -81,18 +81,14 @@ def recognize_stack(stack):
     env = stack.envs
     action_store(env, stack, f"a {type(env).__name__} in place of the action store on top of the stack")
     env = env.env
-    before, forcing, after = [], None, []
+    transforms = []
     while type(env) is vw.TransformActionWrapper:
         if updates_statistics(env):
             raise Unrecognized("an action transform that updates its statistics")
-        f = is_forcing(env.transform)
-        if f is not None:
-            if forcing is not None:
-                raise Unrecognized("two forcings")
-            forcing = f
-        else:
-            (before if forcing is None else after).append(env.transform)
+        transforms.append(env.transform)
+        split_at_forcing(transforms)         # a second forcing is refused where the walk meets it
         env = env.env
+    before, forcing, after = split_at_forcing(transforms)
     if forcing is None:
         raise Unrecognized("an action stack without a GaussianForcing")
     sensors = []
@@ -103,14 +99,7 @@ def recognize_stack(stack):
     if not isinstance(world, WorldVecEnv):
         raise Unrecognized(f"a {type(world).__name__} in place of the WorldVecEnv")
     N, W = one_channel_each(world, "a world")
-    matrix = forcing.forcing.detach().cpu()
-    if matrix.dtype != torch.float32 or matrix.dim() != 2:
-        raise Unrecognized("a forcing matrix that is not fp32 [A, N]")
-    A, L = (int(v) for v in matrix.shape)
-    act_in = field_map(tr.Operation(before), A)
-    if (act_in.start, act_in.stride, act_in.width) != (0, 1, A):
-        raise Unrecognized("a sensor on the agent's actions")
-    act_out = field_map(tr.Operation(after), L)
+    act_in, matrix, act_out = action_maps(before, forcing, after)
     if act_out.width != W:
         raise Unrecognized(f"an action stack that yields {act_out.width} columns for a world that takes {W}")
     agent_obs = field_map(tr.Operation(list(reversed(sensors))), N)
@@ -126,7 +115,7 @@ def recognize_stack(stack):
         raise Unrecognized("the dissipation objective")
     if owner.N != N:
         raise Unrecognized(f"a reward over {owner.N} grid points for observations of {N}")
-    return StackGeometry(world, act_in, matrix.contiguous(), act_out, agent_obs, reward)
+    return StackGeometry(world, act_in, matrix, act_out, agent_obs, reward)
 
 
 def round_length(timesteps0, horizon, max_episode_steps):

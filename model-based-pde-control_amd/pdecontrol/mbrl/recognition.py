@@ -108,6 +108,70 @@ def is_forcing(t):
     return t if type(t) is tr.GaussianForcing else None
 
 
+def split_at_forcing(transforms):
+    """(transforms before the forcing, the ``GaussianForcing`` or None, transforms after it) of a list applied left to
+    right; without a forcing everything is "before".  Raises ``Unrecognized`` on a second forcing."""
+    before, forcing, after = [], None, []
+    for t in transforms:
+        f = is_forcing(t)
+        if f is not None:
+            if forcing is not None:
+                raise Unrecognized("two forcings")
+            forcing = f
+        else:
+            (before if forcing is None else after).append(t)
+    return before, forcing, after
+
+
+def forcing_matrix(forcing):
+    """The fp32 [A, L] matrix of a ``GaussianForcing``, contiguous on the host."""
+    matrix = forcing.forcing.detach().cpu()
+    if matrix.dtype != torch.float32 or matrix.dim() != 2:
+        raise Unrecognized("a forcing matrix that is not fp32 [A, N]")
+    return matrix.contiguous()
+
+
+def action_maps(before, forcing, after):
+    """(``act_in`` FieldMap over the A action columns, the forcing matrix, ``act_out`` FieldMap over its L columns) of an
+    action chain split by ``split_at_forcing`` around a forcing."""
+    matrix = forcing_matrix(forcing)
+    A, L = (int(v) for v in matrix.shape)
+    act_in = field_map(tr.Operation(before), A)
+    if (act_in.start, act_in.stride, act_in.width) != (0, 1, A):
+        raise Unrecognized("a sensor on the agent's actions")
+    return act_in, matrix, field_map(tr.Operation(after), L)
+
+
+def _steps(t):
+    """The transforms of a chain in application order, ``Operation``s opened up."""
+    if isinstance(t, tr.Operation):
+        return [leaf for inner in t.transforms for leaf in _steps(inner)]
+    if isinstance(t, tr._OperationInverse):
+        return [leaf for inner in t.transfs for leaf in _steps(inner)]
+    return [t]
+
+
+def world_connector(stransf, obs_width, act_width):
+    """What a replay connector does to the ``obs`` and ``actions`` of a sample, as ``sur_gather_windows`` takes it:
+    (obs ``FieldMap``, (``act_in`` FieldMap with an identity sensor, the forcing matrix or None, ``act_out`` FieldMap)).
+
+    Recognised: a ``SampleTransform`` whose ``otransf`` flattens to sensors and at most one scaling and whose ``atransf``
+    flattens to at most one scaling, at most one ``GaussianForcing``, then at most one scaling and sensors -- the
+    controller's ``replay_to_world`` (mbrl.py:182-185).  Without a forcing ``act_in`` is the identity and ``act_out``
+    carries the whole action chain.  Anything else raises ``Unrecognized``."""
+    if type(stransf) is not tr.SampleTransform:
+        raise Unrecognized(f"a {type(stransf).__name__} in place of the SampleTransform")
+    obs = field_map(stransf.otransf, int(obs_width))
+    before, forcing, after = split_at_forcing(_steps(stransf.atransf))
+    A = int(act_width)
+    if forcing is None:
+        return obs, (FieldMap(0, 1, A, None), None, field_map(tr.Operation(before), A))
+    act_in, matrix, act_out = action_maps(before, forcing, after)
+    if act_in.width != A:
+        raise Unrecognized(f"a forcing over {act_in.width} actuators for actions of {A} columns")
+    return obs, (act_in, matrix, act_out)
+
+
 def updates_statistics(wrapper):
     """A ``TransformActionWrapper`` whose step changes its transform: not frozen, over a scaling that is not frozen."""
     if wrapper.frozen or is_forcing(wrapper.transform) is not None:

@@ -52,6 +52,14 @@ class ChunkSpan(ctypes.Structure):
                 ("hc_bstride", ctypes.c_int), ("dlstates_t", _fp)]
 
 
+class WindowSource(ctypes.Structure):
+    """``sur_window_source``: where ``sur_gather_windows`` reads from, and the connector it applies."""
+    _fields_ = [("obs", _fp), ("actions", _fp), ("rowmap", _fp), ("total", ctypes.c_long), ("rows", ctypes.c_long),
+                ("obs_width", ctypes.c_int), ("obs_start", ctypes.c_int), ("obs_stride", ctypes.c_int), ("obs_coef", _fp),
+                ("act_width", ctypes.c_int), ("act_in_coef", _fp), ("forcing", _fp), ("forcing_width", ctypes.c_int),
+                ("act_start", ctypes.c_int), ("act_stride", ctypes.c_int), ("act_out_coef", _fp)]
+
+
 MAX_SPANS = 4
 _EP, _CP, _i = ctypes.POINTER(EncoderParams), ctypes.POINTER(ChunkParams), ctypes.c_int
 _AP = ctypes.POINTER(AdamParams)
@@ -89,6 +97,10 @@ SYMBOLS = (
     ("sur_latent_workspace_floats", _i, [_CP, _i, _i]),
     ("sur_latent_chunk_backward", _i, [_fp, _CP, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp,
                                        _i, _i, _fp, _fp]),
+    ("sur_gather_windows", _i, [_fp, ctypes.POINTER(WindowSource), _fp, _i, _i, _fp, _i, ctypes.c_long, ctypes.c_long, _fp, _i,
+                                ctypes.c_long, ctypes.c_long]),
+    ("sur_val_loss", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                          ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     ("sur_last_error", ctypes.c_char_p, []),
 )
 _lib = None
@@ -833,6 +845,31 @@ def fused_delta_loss(surrogate, d_all, states, delta, mean, stdv):
     return _DeltaLossFn.apply(d_all, states, float(delta), float(mean), float(stdv), scratch)
 
 
+def fused_val_loss(surrogate, states, out_all, d_all, delta, mean, stdv, inv_coef, accum=None, outputs=True):
+    """The loss section of ``validation_step`` in one launch (``sur_val_loss``).  states [B,T,1,N] (rows dense, any batch /
+    time strides); out_all, d_all: the rollout's time-major [T,B,1,N] predictions and deltas; inv_coef: the inverse
+    observation scaling as [4, N] device coefficients or None.  ``accum``: a caller-owned device double[3 + T] epoch
+    accumulator the launch adds the batch's error sums to.  Returns (loss, hsteploss [T], scalars [2] = scaled loss and
+    delta loss, true deltas [B,T-1,1,N], unscaled decoded [B,T,1,N]); the last two are None without ``outputs``."""
+    t, b, _, n = d_all.shape
+    dev = d_all.device
+    owner = getattr(surrogate, "_fused_packs", None)
+    cache = owner.loss_scratch if owner is not None else surrogate.__dict__.setdefault("_loss_scratch", {})
+    scratch = cache.get(("val", t, dev))
+    if scratch is None:
+        scratch = cache[("val", t, dev)] = (torch.empty(24 * t, device=dev, dtype=torch.float64),
+                                            torch.zeros(1, device=dev, dtype=torch.int32))
+    if states.stride(3) != 1:
+        states = states.contiguous()
+    new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+    deltas, decoded = (new(b, t - 1, 1, n), new(b, t, 1, n)) if outputs else (None, None)
+    hstep, loss, scalars = new(t), new(), new(2)
+    _check(load().sur_val_loss(_stream(), _ptr(states), states.stride(0), states.stride(1), _ptr(out_all), _ptr(d_all), b, t, n,
+                               delta, mean, stdv, _ptr(inv_coef), _ptr(deltas), _ptr(decoded), _ptr(hstep), _ptr(loss),
+                               _ptr(scalars), _ptr(accum), _ptr(scratch[0]), _ptr(scratch[1])))
+    return loss, hstep, scalars, deltas, decoded
+
+
 def _encoder_forward_multi(lib, jobs):
     """jobs: one or two (pack, x_ptr, m, z_ptr, saved_ptr) tuples (raw device addresses) -> block-per-launch forward."""
     n = len(jobs)
@@ -1447,3 +1484,46 @@ def fused_tbptt_backward(st, accumulate=False):
     _tbptt_backward(st.owner, st.bounds, (st.b, st.t_total, st.n, st.nchunks), saved, (st.h_all_u, st.c_all_u, st.saved_u),
                     st.dd_all if dd is None else dd)
     st.owner.flush_into_flat(accumulate)
+
+
+# ---------------------------------------------------------------------------------------------
+# the window gather of the surrogate-update phase
+# ---------------------------------------------------------------------------------------------
+class WindowGather:
+    """``sur_gather_windows`` over one packed replay and one recognised connector (``recognition.world_connector``): the
+    coefficients, the forcing matrix and the row map are uploaded here, once; a call is one launch.
+
+    ``obs`` [rows, ..., No_src] and ``actions`` [rows, ..., A] are the packed fields on the device (fp32, contiguous),
+    ``rowmap`` the device int64 map from logical to physical row or None, ``total`` the number of logical rows."""
+
+    def __init__(self, obs, actions, rowmap, total, obs_map, act_maps):
+        act_in, forcing, act_out = act_maps
+        device = obs.device
+        if obs.dtype != torch.float32 or actions.dtype != torch.float32 or not obs.is_contiguous() or not actions.is_contiguous():
+            raise SurrogateHipError("sur_gather_windows reads contiguous fp32 fields")
+        up = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
+        self.obs, self.actions, self.rowmap, self.device = obs, actions, rowmap, device
+        self.coefs = (up(obs_map.coef), up(act_in.coef), up(forcing), up(act_out.coef))
+        self.states_width, self.actions_width = int(obs_map.width), int(act_out.width)
+        rows = int(obs.shape[0])
+        self.source = WindowSource(
+            _ptr(obs), _ptr(actions), _ptr(rowmap), int(total), rows, int(obs[0].numel()) if rows else 0, int(obs_map.start),
+            int(obs_map.stride), _ptr(self.coefs[0]), int(actions[0].numel()) if rows else 0, _ptr(self.coefs[1]),
+            _ptr(self.coefs[2]), 0 if forcing is None else int(forcing.shape[1]), int(act_out.start), int(act_out.stride),
+            _ptr(self.coefs[3]))
+
+    def refused(self):
+        """The library's reason for refusing this geometry, or None.  A host call: nothing is launched (the outputs it
+        names are never reached: one window of one step of a width no sensor yields is refused last)."""
+        lib = load()
+        probe = ctypes.c_void_p(16)
+        rc = lib.sur_gather_windows(None, ctypes.byref(self.source), probe, 1, 1, probe, -1, 0, 0, probe, -1, 0, 0)
+        return None if rc == -7 else lib.sur_last_error().decode()
+
+    def __call__(self, first, offset, b, l, states, actions):
+        """Windows ``first[offset : offset + b]`` (a device int64 tensor) of ``l`` steps into ``states`` / ``actions``:
+        fp32 [b, l, ..., width] tensors or views whose rows are contiguous (batch-major, or time-major storage)."""
+        _check(load().sur_gather_windows(
+            _stream(), ctypes.byref(self.source), ctypes.c_void_p(first.data_ptr() + 8 * int(offset)), b, l, _ptr(states),
+            self.states_width, states.stride(0), states.stride(1), _ptr(actions), self.actions_width, actions.stride(0),
+            actions.stride(1)))

@@ -256,9 +256,15 @@ class PDETrainingModule(pl.LightningModule):
         buffers (pdecontrol.surrogates.graph_step.GraphedTBPTTStep; a graph per batch shape, captured on first
         use; ONE Adam state and learning rate for all of them).  Returns training_step's dict; its tensors are
         overwritten by the next call.  CUDA only."""
-        from pdecontrol.surrogates.graph_step import GraphedTBPTTStep
         states, actions, *_ = batch
-        key = (tuple(states.shape), tuple(actions.shape))
+        return self.graphed_step_for(states.shape, actions.shape, lr=lr).step(states, actions, lr=lr)
+
+    def graphed_step_for(self, states_shape, actions_shape, lr=None):
+        """The captured step of ``fused_step`` for one batch shape (captured on first use, re-captured once it is no longer
+        ``valid()``).  A caller that fills its static ``states`` / ``actions`` itself -- the surrogate-update phase's window
+        gather -- replays it with ``step()``."""
+        from pdecontrol.surrogates.graph_step import GraphedTBPTTStep
+        key = (tuple(states_shape), tuple(actions_shape))
         cache = self.__dict__.setdefault("_graphed_steps", {})
         trained = self.__dict__.get("_graphed_trained")
         stale = key not in cache or not cache[key].valid()
@@ -278,7 +284,7 @@ class PDETrainingModule(pl.LightningModule):
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
             cache[key] = GraphedTBPTTStep(self, key[0], key[1], lr=lr, distributed=distributed)
         self.__dict__["_last_graphed_step"] = cache[key]
-        return cache[key].step(states, actions, lr=lr)
+        return cache[key]
 
     def _graphed_training_step(self, batch):
         """training_step under Lightning's manual optimization: replay the graph with the learning rate of the
@@ -311,9 +317,61 @@ class PDETrainingModule(pl.LightningModule):
                 sch.step()
 
     # -- validation / test: one un-truncated rollout ------------------------------------------
+    def _inverse_scaling(self, n, device):
+        """[4, n] device coefficients of ``stransf.otransf.Inverse`` when it is an identity sensor and at most one
+        ``ScaleTransform`` (``False`` for the identity; None for anything else, e.g. a ``Normalize``).  The host
+        coefficients are worked out on every call (a few tiny CPU ops); they go up again only when their values change."""
+        from pdecontrol.mbrl.recognition import Unrecognized, field_map
+        try:
+            fmap = field_map(self.stransf.otransf.Inverse, n)
+        except (Unrecognized, NotImplementedError):
+            return None
+        if (fmap.start, fmap.stride, fmap.width) != (0, 1, n):
+            return None
+        if fmap.coef is None:
+            return False
+        cached = self.__dict__.get("_inv_coef")
+        if cached is None or cached[0] != device or not torch.equal(cached[1], fmap.coef):
+            cached = self.__dict__["_inv_coef"] = (device, fmap.coef, fmap.coef.to(device))
+        return cached[2]
+
+    def _fused_validation_loss(self, out, states, accum=None, outputs=True):
+        """The loss section of validation_step as one HIP launch (``sur_val_loss``), on the conditions of
+        ``_fused_delta_loss`` plus a recognised ``stransf.otransf.Inverse``; None otherwise (then the torch ops run).
+        ``accum`` / ``outputs``: the epoch accumulator and the switch of ``hipops.fused_val_loss`` (the surrogate-update
+        phase keeps an epoch's sums on the device and needs neither ``deltas`` nor the decoded outputs)."""
+        from pdecontrol.surrogates import ops
+        if not (isinstance(self.surrogate, AutoRegPDESurrogate) and states.is_cuda and ops.use_fused_for(self.surrogate, states)):
+            return None
+        if self.training_mode != "delta" or not (isinstance(self.loss, torch.nn.MSELoss) and self.loss.reduction == "none"):
+            return None
+        from pdecontrol.surrogates import hipops
+        consts = hipops.undscale_constants(self.undscaling)
+        if consts is None or states.dtype != torch.float32 or states.shape[2] != 1 or states.shape[1] < 2:
+            return None
+        if tuple(out.outputs.shape) != tuple(states.shape) or tuple(out.deltas.shape) != tuple(states.shape):
+            return None
+        out_all, d_all = out.outputs.transpose(0, 1), out.deltas.transpose(0, 1)
+        if not (out_all.is_contiguous() and d_all.is_contiguous()):
+            return None             # not the time-major storage sur_chunk_forward wrote
+        inv = self._inverse_scaling(states.shape[3], states.device)
+        if inv is None:
+            return None
+        return hipops.fused_val_loss(self.surrogate, states, out_all, d_all, self.delta, *consts,
+                                     inv if inv is not False else None, accum=accum, outputs=outputs)
+
     def validation_step(self, batch, bidx):
         states, actions, *_ = batch
         out = self._full_rollout(states, actions)
+        fused = self._fused_validation_loss(out, states)
+        if fused is not None:
+            loss, hsteploss, scalars, deltas, decoded = fused
+            self.log("Val. Delta Loss", scalars[1], on_step=False, on_epoch=True)
+            self.log("Val. Scaled Loss", scalars[0], on_step=False, on_epoch=True)
+            self.log("Val. Loss", loss, on_step=False, on_epoch=True)
+            return {"loss": loss, "hsteploss": hsteploss, "outputs": decoded, "actions": actions.detach(),
+                    "states": self.stransf.otransf.Inverse(states).detach(), "outdeltas": out.deltas[:, :-1].detach(),
+                    "deltas": deltas}
         decoded = torch.cat((states[:, :1], out.outputs[:, :-1]), dim=1)  # IC-augmented prediction
         outdeltas = out.deltas[:, :-1]
         deltas = self.undscaling(torch.diff(states, dim=1) / self.delta)
