@@ -9,6 +9,10 @@
 // VGPRs; one env is one 64-lane wavefront with P = N/64 contiguous points per lane; the +-2 halo comes from the two
 // neighbouring lanes by DPP wave rotations (wave_ror:1 / wave_rol:1), which ARE the periodic boundary: no LDS, no
 // barrier, no index arithmetic.  HBM is touched once on entry and once on exit; the kernel is VALU-issue bound.
+//
+// Built with -ffp-contract=off: every device operation below is one rounded fp32 operation or one explicit fmaf, in the
+// order oracle/burgers_oracle.c restates as flat loops.  tests/test_burgers_gpu.py holds bg_step (scalar, packed and
+// pair-native forms), bg_phyloss_forward and bg_residual to that twin bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -421,7 +425,8 @@ const char* bg_last_error(void) { return g_err; }
 
 int bg_step(void* stream, float* u, const float* actions, const float* F, int n_act, int n_envs, int N, float dx, float dt,
             float nu, long n_substeps, float* obs, double* ssq_sum, int* status) {
-    if (!u || n_envs <= 0 || N <= 0 || n_substeps < 0) return fail(-1, "bg_step: bad argument");
+    if (!u || n_envs <= 0 || N <= 0) return fail(-1, "bg_step: bad argument");
+    if (n_substeps < 0) return fail(-1, "bg_step: n_substeps = %ld is negative", n_substeps);
     if (actions && (!F || n_act <= 0)) return fail(-1, "bg_step: actions need the forcing matrix F and n_act > 0");
     if (!(dx > 0.0f) || !(dt > 0.0f) || !(nu >= 0.0f)) return fail(-1, "bg_step: dx, dt must be positive, nu non-negative");
     if (N % 64) return fail(-4, "bg_step: N = %d is not a multiple of 64", N);
