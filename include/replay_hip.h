@@ -22,7 +22,8 @@
  * `rp_source` entries are HOST structs, read during the call and passed to the kernel by value; every pointer in them is
  * a DEVICE pointer.  In every entry the arguments are validated on the host before any device call and everything is
  * enqueued on `stream`: no host synchronisation, no device allocation.  Return 0 on success, negative on error
- * (rp_last_error()).  Plain vector stores, no LDS, no scratch, no atomics.
+ * (rp_last_error()).  Plain vector stores, no scratch, no atomics; LDS only in rpd_moments, where the four waves of a
+ * workgroup add up their partial sums.
  */
 #ifndef REPLAY_HIP_H
 #define REPLAY_HIP_H
@@ -93,6 +94,42 @@ int rp_append(void* stream, const float* block, int T, int T_cap, int B, int N, 
  * Refusals: -50 NULL pointer, -51 E < 1, -52 nrows < 1 or slab_rows < 1, -60 launch failure. */
 int rp_episode_returns(void* stream, const float* rewards, long slab_rows, const long* rows, long nrows, const long* offsets,
                        int E, float* returns);
+
+/* The moments of the scaled state changes of `n` transitions, read from the slabs in place (the controller's
+ * update_delta_transform, pdecontrol/mbrl/delta_phase.py).  Row i is physical row rows[i] of `obs` and `nxtobs`
+ * ([slab_rows][obs_width] fp32); rows: DEVICE int64 [n], NULL for rows 0 ... n - 1.  Output column j of obs_dim =
+ * ceil((obs_width - sensor_start) / sensor_stride) reads input column sensor_start + j * sensor_stride:
+ *   d[i][j] = (affine_j(nxtobs) - affine_j(obs)) / delta
+ * with the affine map of rp_gather (obs_coef [4][obs_dim], NULL: identity) and then one correctly rounded fp32
+ * subtraction and one correctly rounded fp32 DIVISION by `delta` (not a multiplication by its reciprocal).
+ *
+ * Sum d and sum d * d are accumulated per column in fp64.  One wave per row, four rows of a wave in flight, four waves per
+ * workgroup, lanes along the columns: float4 loads where there are more than 192 columns, sensor_stride is 1, obs_width
+ * and sensor_start are multiples of four and obs, nxtobs and obs_coef are 16-byte aligned; narrower rows keep a lane per
+ * column.  Workgroup g of G takes the rows 16 g ... 16 g + 15, 16 (g + G) ..., and writes its partial pair to row g of
+ * `workspace`.  Above 32 workgroups a middle launch adds each 32 consecutive partial rows in index order; a closing
+ * launch of one workgroup adds what is left in index order.  No floating-point atomics: at a given G the result is the
+ * same bit for bit from run to run.  G = `groups` (at most RP_MAX_DELTA_GROUPS, above which it is clamped), or for
+ * groups = 0 the default min(ceil(n / 16), RP_MAX_DELTA_GROUPS).
+ *
+ * sums:  fp64 [2][obs_dim + 1]: sum d and sum d * d per column; entry obs_dim is the total over the columns, added in
+ *        column order.
+ * stats: fp32 [2][obs_dim + 1]: mean = S / m and unbiased variance = (Q - S * S / m) / (m - 1), evaluated in fp64 and
+ *        rounded once; m = n per column and n * obs_dim for the aggregate; m < 2 gives a NaN variance.
+ * A rows entry outside [0, slab_rows) reads nothing and makes every statistic NaN.
+ * Refusals: -70 NULL obs, nxtobs, workspace, sums or stats, -71 n < 1, -72 a slab without rows, -73 sensor stride < 1,
+ * -74 sensor start outside the row, -75 more than RP_MAX_OBS_DIM output columns, -76 delta zero or not finite,
+ * -77 a negative group count, -80 launch failure.
+ *
+ * The two entries carry the prefix rpd_: they are bound by a table of their own (replay_hip.DELTA_SYMBOLS), beside the
+ * rp_ entries above and their table, and report through rp_last_error(). */
+#define RP_MAX_DELTA_GROUPS 2048
+int rpd_moments(void* stream, const float* obs, const float* nxtobs, long slab_rows, int obs_width, int sensor_start,
+                int sensor_stride, const float* obs_coef, const long* rows, long n, float delta, int groups,
+                double* workspace, double* sums, float* stats);
+
+/* Doubles of the workspace rpd_moments needs for these arguments; 0 where it would refuse them. */
+long rpd_workspace_doubles(int obs_dim, long n, int groups);
 
 const char* rp_last_error(void);
 

@@ -9,6 +9,9 @@
 //
 // The affine map is row_ops.h's, so the batch equals the host loader's bit for bit.  Plain vector stores only; nothing is
 // stored through the scalar unit.
+//
+// rpd_moments reads the same rows the other way round: nothing is copied, the scaled state changes of all rows are
+// reduced to per-column fp64 sums in two or three launches (partials per workgroup, then folds in index order).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -156,6 +159,179 @@ __global__ __launch_bounds__(NT) void rp_episode_returns_kernel(const float* __r
     returns[e] = acc;
 }
 
+// ---- the moments of the scaled state changes (update_delta_transform) -----------------------------------------------
+struct DeltaArgs {
+    const float* obs;                  // [slab_rows][obs_width]
+    const float* nxtobs;
+    const float* coef;                 // [4][obs_dim] or NULL
+    const long* rows;                  // [n] or NULL: rows 0 ... n - 1
+    long n, slab_rows;
+    int obs_width, obs_dim, start, stride;
+    float delta;
+    double* ws;                        // [groups][2][obs_dim], then the rows of the middle launch
+};
+
+constexpr int TILE = 4 * WAVE;         // columns of one blockIdx.y: four per lane
+constexpr int TURN = 4;                // rows a wave has in flight at a time
+constexpr int FOLD = 32;               // partial rows one workgroup of the middle launch folds
+
+__device__ __forceinline__ float scaled_delta(float nxt, float obs, float delta) { return __fdiv_rn(__fsub_rn(nxt, obs), delta); }
+
+// A wave owns TURN consecutive rows of the list at a time -- their loads are issued together, which is what keeps enough
+// bytes in flight -- and keeps sum d and sum d * d of its four columns of the tile in fp64 registers; the four waves'
+// pairs meet in LDS and are added in wave order.  VEC: lane l holds columns 4 l ... 4 l + 3 of the tile (one float4 per
+// field), else columns l, l + 64, l + 128, l + 192.
+template <bool VEC>
+__global__ __launch_bounds__(NT) void rpd_moments_kernel(const DeltaArgs a)
+{
+    __shared__ double part[WAVES][2][TILE];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    const int j0 = blockIdx.y * TILE;
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long i0 = ((long)blockIdx.x * WAVES + wave) * TURN; i0 < a.n; i0 += (long)gridDim.x * WAVES * TURN) {
+        long first[TURN];
+        int state[TURN];               // 0: past the list, 1: a row of the slab, 2: outside it (read nothing, poison)
+        float o[TURN][4], x[TURN][4];
+#pragma unroll
+        for (int t = 0; t < TURN; ++t) {
+            const long i = i0 + t;
+            const long r = i < a.n ? (a.rows ? a.rows[i] : i) : -1;
+            const bool inside = r >= 0 && r < a.slab_rows;
+            state[t] = i < a.n ? (inside ? 1 : 2) : 0;
+            first[t] = inside ? r * a.obs_width + a.start : 0;
+        }
+#pragma unroll
+        for (int t = 0; t < TURN; ++t) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[t][k] = x[t][k] = 0.0f;
+            if (state[t] != 1) continue;
+            if (VEC) {
+                const int j = j0 + 4 * lane;
+                if (j < a.obs_dim) {
+                    const f4 vo = *reinterpret_cast<const f4*>(a.obs + first[t] + j);
+                    const f4 vx = *reinterpret_cast<const f4*>(a.nxtobs + first[t] + j);
+                    o[t][0] = vo.x, o[t][1] = vo.y, o[t][2] = vo.z, o[t][3] = vo.w;
+                    x[t][0] = vx.x, x[t][1] = vx.y, x[t][2] = vx.z, x[t][3] = vx.w;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = j0 + lane + k * WAVE;
+                    if (j0 + k * WAVE >= a.obs_dim) break;      // wave-uniform: a narrow row costs what it holds
+                    if (j < a.obs_dim) {
+                        o[t][k] = a.obs[first[t] + (long)j * a.stride];
+                        x[t][k] = a.nxtobs[first[t] + (long)j * a.stride];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < TURN; ++t) {
+            if (state[t] == 0) continue;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = j0 + (VEC ? 4 * lane + k : lane + k * WAVE);
+                if (!VEC && j0 + k * WAVE >= a.obs_dim) break;
+                float d = 0.0f;
+                if (state[t] == 2)
+                    d = NAN;
+                else if (j < a.obs_dim)
+                    d = scaled_delta(affine_col(a.coef, a.obs_dim, j, x[t][k]), affine_col(a.coef, a.obs_dim, j, o[t][k]), a.delta);
+                const double v = (double)d;
+                s[k] += v;
+                q[k] += v * v;         // the product of two fp32 values is exact in fp64
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = VEC ? 4 * lane + k : lane + k * WAVE;
+        part[wave][0][c] = s[k];
+        part[wave][1][c] = q[k];
+    }
+    __syncthreads();
+    const int j = j0 + threadIdx.x;    // NT == TILE: a thread per column of the tile
+    if (j < a.obs_dim) {
+        double S = part[0][0][threadIdx.x], Q = part[0][1][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            S += part[w][0][threadIdx.x];
+            Q += part[w][1][threadIdx.x];
+        }
+        double* __restrict__ out = a.ws + (long)blockIdx.x * 2 * a.obs_dim;
+        out[j] = S;
+        out[a.obs_dim + j] = Q;
+    }
+}
+
+// the middle launch: workgroup b adds the partial rows FOLD b ... FOLD b + FOLD - 1 of `in` (of `groups`) in index order
+// into row b of `out`; a thread per column
+__global__ __launch_bounds__(NT) void rpd_middle_kernel(const double* __restrict__ in, int groups, int obs_dim,
+                                                             double* __restrict__ out)
+{
+    const int j = blockIdx.y * NT + threadIdx.x;
+    if (j >= obs_dim) return;
+    const int g0 = blockIdx.x * FOLD, g1 = g0 + FOLD < groups ? g0 + FOLD : groups;
+    double S = 0.0, Q = 0.0;
+#pragma unroll 8
+    for (int g = g0; g < g1; ++g) {
+        S += in[(long)g * 2 * obs_dim + j];
+        Q += in[(long)g * 2 * obs_dim + obs_dim + j];
+    }
+    out[(long)blockIdx.x * 2 * obs_dim + j] = S;
+    out[(long)blockIdx.x * 2 * obs_dim + obs_dim + j] = Q;
+}
+
+// mean and unbiased variance of m values from their fp64 sum and sum of squares, rounded once
+__device__ __forceinline__ void write_stats(double S, double Q, double m, float* __restrict__ mean, float* __restrict__ var)
+{
+    *mean = (float)(S / m);
+    *var = m < 2.0 ? NAN : (float)((Q - S * S / m) / (m - 1.0));
+}
+
+// the closing launch, one workgroup: the partial rows per column in index order, then the totals over the columns in
+// column order
+__global__ __launch_bounds__(NT) void rpd_fold_kernel(const double* __restrict__ ws, int groups, int obs_dim, long n,
+                                                           double* __restrict__ sums, float* __restrict__ stats)
+{
+    __shared__ double col[2][RP_MAX_OBS_DIM];
+    const int ld = obs_dim + 1;
+    for (int j = threadIdx.x; j < obs_dim; j += NT) {
+        double S = 0.0, Q = 0.0;
+#pragma unroll 8
+        for (int g = 0; g < groups; ++g) {
+            S += ws[(long)g * 2 * obs_dim + j];
+            Q += ws[(long)g * 2 * obs_dim + obs_dim + j];
+        }
+        col[0][j] = sums[j] = S;
+        col[1][j] = sums[ld + j] = Q;
+        write_stats(S, Q, (double)n, stats + j, stats + ld + j);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double S = 0.0, Q = 0.0;
+        for (int j = 0; j < obs_dim; ++j) {
+            S += col[0][j];
+            Q += col[1][j];
+        }
+        sums[obs_dim] = S;
+        sums[ld + obs_dim] = Q;
+        write_stats(S, Q, (double)n * obs_dim, stats + obs_dim, stats + ld + obs_dim);
+    }
+}
+
+// workgroups of rpd_moments for n rows: `groups`, or the default for 0 (a turn of rows per wave), at most
+// RP_MAX_DELTA_GROUPS
+int delta_groups(long n, int groups)
+{
+    const long most = RP_MAX_DELTA_GROUPS, per = WAVES * TURN;
+    const long g = groups > 0 ? groups : (n + per - 1) / per;
+    return (int)(g < most ? g : most);
+}
+
+// partial rows the middle launch leaves of G (0: there is no middle launch)
+int delta_middle_rows(int G) { return G > FOLD ? (G + FOLD - 1) / FOLD : 0; }
+
 int obs_dim_of(const rp_source& s) { return width_of(s.obs_width, s.sensor_start, s.sensor_stride); }
 
 }  // namespace
@@ -270,6 +446,68 @@ int rp_episode_returns(void* stream, const float* rewards, long slab_rows, const
     hipLaunchKernelGGL(rp_episode_returns_kernel, dim3((E + NT - 1) / NT), dim3(NT), 0, static_cast<hipStream_t>(stream), rewards,
                        slab_rows, rows, nrows, offsets, E, returns);
     return launch_status(-60, "rp_episode_returns");
+}
+
+long rpd_workspace_doubles(int obs_dim, long n, int groups)
+{
+    if (obs_dim < 1 || obs_dim > RP_MAX_OBS_DIM || n < 1 || groups < 0) return 0;
+    const int G = delta_groups(n, groups);
+    return (long)(G + delta_middle_rows(G)) * 2 * obs_dim;
+}
+
+int rpd_moments(void* stream, const float* obs, const float* nxtobs, long slab_rows, int obs_width, int sensor_start,
+                     int sensor_stride, const float* obs_coef, const long* rows, long n, float delta, int groups,
+                     double* workspace, double* sums, float* stats)
+{
+    if (!obs || !nxtobs || !workspace || !sums || !stats)
+        return fail(-70, "rpd_moments: NULL obs, nxtobs, workspace, sums or stats");
+    if (n < 1) return fail(-71, "rpd_moments: %ld rows (at least 1)", n);
+    if (slab_rows < 1) return fail(-72, "rpd_moments: a slab of %ld rows (at least 1)", slab_rows);
+    if (sensor_stride < 1) return fail(-73, "rpd_moments: sensor stride %d (at least 1)", sensor_stride);
+    if (obs_width < 1 || sensor_start < 0 || sensor_start >= obs_width)
+        return fail(-74, "rpd_moments: the sensor starts at column %d of %d", sensor_start, obs_width);
+    const int obs_dim = width_of(obs_width, sensor_start, sensor_stride);
+    if (obs_dim > RP_MAX_OBS_DIM)
+        return fail(-75, "rpd_moments: %d observation columns (1 ... %d are supported)", obs_dim, RP_MAX_OBS_DIM);
+    if (!(delta != 0.0f) || !std::isfinite(delta))
+        return fail(-76, "rpd_moments: a step of %g to divide by (finite and not zero)", (double)delta);
+    if (groups < 0) return fail(-77, "rpd_moments: %d workgroups (0 for the default, or at least 1)", groups);
+    DeltaArgs a = {};
+    a.obs = obs;
+    a.nxtobs = nxtobs;
+    a.coef = obs_coef;
+    a.rows = rows;
+    a.n = n;
+    a.slab_rows = slab_rows;
+    a.obs_width = obs_width;
+    a.obs_dim = obs_dim;
+    a.start = sensor_start;
+    a.stride = sensor_stride;
+    a.delta = delta;
+    a.ws = workspace;
+    const int G = delta_groups(n, groups);
+    const dim3 grid(G, (obs_dim + TILE - 1) / TILE);
+    // float4 puts four columns on a lane: worth it from 193 columns on, where a lane holds four either way; below, a
+    // lane per column keeps the lanes busy (64 columns as float4 would leave 48 of 64 lanes idle through every division)
+    const bool vec = obs_dim > 3 * WAVE && sensor_stride == 1 && obs_width % 4 == 0 && sensor_start % 4 == 0 && aligned16(obs) &&
+                     aligned16(nxtobs) && aligned16(obs_coef);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(rpd_moments_kernel<true>, grid, dim3(NT), 0, s, a);
+    else
+        hipLaunchKernelGGL(rpd_moments_kernel<false>, grid, dim3(NT), 0, s, a);
+    const int rc = launch_status(-80, "rpd_moments");
+    if (rc != 0) return rc;
+    const double* partials = workspace;
+    int left = G;
+    if (const int M = delta_middle_rows(G)) {
+        double* middle = workspace + (long)G * 2 * obs_dim;
+        hipLaunchKernelGGL(rpd_middle_kernel, dim3(M, (obs_dim + NT - 1) / NT), dim3(NT), 0, s, workspace, G, obs_dim, middle);
+        partials = middle;
+        left = M;
+    }
+    hipLaunchKernelGGL(rpd_fold_kernel, dim3(1), dim3(NT), 0, s, partials, left, obs_dim, n, sums, stats);
+    return launch_status(-80, "rpd_moments");
 }
 
 const char* rp_last_error(void) { return g_err; }

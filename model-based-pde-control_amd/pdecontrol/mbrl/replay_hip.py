@@ -36,6 +36,14 @@ SYMBOLS = (
     ("rp_episode_returns", _i, [_p, _p, _l, _p, _l, _p, _i, _p]),
     ("rp_last_error", ctypes.c_char_p, []),
 )
+# the ``rpd_*`` half of the library (the delta statistics, pdecontrol/mbrl/delta_phase.py): a table of its own, as the
+# ``fno_*`` half of libspectral_hip has; its refusals are read through ``rp_last_error`` too
+DELTA_SYMBOLS = (
+    ("rpd_moments", _i, [_p, _p, _p, _l, _i, _i, _i, _p, _p, _l, ctypes.c_float, _i, _p, _p, _p]),
+    ("rpd_workspace_doubles", _l, [_i, _l, _i]),
+)
+MAX_DELTA_GROUPS = 2048
+DELTA_LAUNCH_FAILURE = -80
 _lib = None
 
 
@@ -46,7 +54,7 @@ class ReplayHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, ReplayHipError, "The fused batch gather has no fallback.")
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + DELTA_SYMBOLS, ReplayHipError, "The fused batch gather has no fallback.")
     return _lib
 
 
@@ -88,6 +96,26 @@ def append(stream, block_ptr, T, T_cap, B, N, A, dst_ptr, dst_host, slab_struct)
     assert dst_host.dtype.kind == "i" and dst_host.dtype.itemsize == 8 and dst_host.flags.c_contiguous and dst_host.size == T * B
     _check(load().rp_append(stream, block_ptr, int(T), int(T_cap), int(B), int(N), int(A), dst_ptr, dst_host.ctypes.data,
                             ctypes.byref(slab_struct)))
+
+
+def delta_workspace_doubles(obs_dim, n, groups=0):
+    """fp64 elements of the workspace ``delta_moments`` needs; 0 where it would refuse the arguments."""
+    return int(load().rpd_workspace_doubles(int(obs_dim), int(n), int(groups)))
+
+
+def delta_moments(stream, obs, nxtobs, start, stride, coef, rows, n, delta, groups, workspace, sums, stats):
+    """``rpd_moments`` on ``stream``, two or three launches: ``obs`` and ``nxtobs`` are contiguous fp32 device tensors
+    [slab rows, (1,) obs_width], ``coef`` fp32 [4, obs_dim] or None, ``rows`` int64 [n] or None (rows 0 ... n - 1);
+    ``workspace`` fp64 of ``delta_workspace_doubles`` elements, ``sums`` fp64 and ``stats`` fp32 [2, obs_dim + 1].
+    A refusal raises ``ReplayHipError`` with the status as its ``code``; nothing was enqueued then unless the code is
+    ``DELTA_LAUNCH_FAILURE``."""
+    rc = load().rpd_moments(stream, obs.data_ptr(), nxtobs.data_ptr(), int(obs.shape[0]), int(obs.shape[-1]), int(start),
+                                 int(stride), hipbind.ptr(coef), hipbind.ptr(rows), int(n), float(delta), int(groups),
+                                 workspace.data_ptr(), sums.data_ptr(), stats.data_ptr())
+    if rc != 0:
+        error = ReplayHipError(f"libreplay_hip error {rc}: {last_error()}")
+        error.code = rc
+        raise error
 
 
 def episode_returns(stream, rewards, rows, offsets, returns):

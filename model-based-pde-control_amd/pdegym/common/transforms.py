@@ -152,11 +152,19 @@ class Normalize(Transform):
         n_new = t.shape[0]
         b_mean = torch.mean(t, dim=self.dim, keepdim=True, dtype=torch.float32)
         b_var = torch.var(t, dim=self.dim, keepdim=True)
+        self.merge(b_mean, b_var, n_new)
+
+    def merge(self, b_mean, b_var, n_new):
+        """Folds the mean and unbiased variance of a batch of ``n_new`` items into the running statistics: what
+        ``update`` does after its two reductions, for callers that have reduced the batch themselves (the fused delta
+        statistics of pdecontrol/mbrl/delta_phase.py).  The statistics move to the device of ``b_mean``."""
+        if self.frozen:
+            return
         if self.mean is None:
             self.mean = torch.zeros_like(b_mean)
         if self.var is None:
             self.var = torch.zeros_like(b_mean)
-        mean, var = _on(self.mean, t), _on(self.var, t)
+        mean, var = _on(self.mean, b_mean), _on(self.var, b_mean)
         total = self.count + n_new
         delta = b_mean - mean
         # parallel-variance merge (Chan et al.), with the batch size as the weight of both terms
