@@ -238,6 +238,47 @@ __device__ __forceinline__ double rhs_point(const double* w, const double* q, in
 }
 
 
+// ------------------------------------------------------------------------------------------
+// upwind select of the fast-mode tiles without v_cndmask:  sel = (u < 0) ? fw : bw
+// ------------------------------------------------------------------------------------------
+// A 64-bit select is two v_cndmask_b32 (there is no 64-bit form).  Instead the last FMA of the backward chain runs in
+// all lanes into R, then the last FMA of the forward chain runs into the same R with EXEC = the lanes with u < 0:
+// afterwards R is sel, with the same operations and the same bits.  Per tile: TJ + 1 scalar writes of EXEC in place
+// of 2 TJ VALU selects.  -DKS_UPWIND_CNDMASK keeps the plain ?: form (lib/libkspde_cndmask.so, the A/B partner).
+//
+// EXEC invariant: the statement leaves EXEC as the kernel was entered.  It is restored from ex0, the copy that
+// ks_rk4_fused reads once with __builtin_amdgcn_read_exec() before any control flow and hands down in an SGPR pair
+// (not from a literal -1: right as well when a caller enters with lanes off).  The sub-step loop and everything
+// between kernel entry and the tiles is wave-uniform, so EXEC at the statement is ex0.  The masks come from
+// __builtin_amdgcn_fcmp(u, 0.0, OLT): v_cmp sets bits only for active lanes, so mask is a subset of ex0, and the
+// ordered less-than leaves NaN, +0.0 and -0.0 on the backward chain exactly as the ternary does.
+//
+// Wait states (gfx9 family), per boundary of the statement:
+//   * v_cmp (compiler, before the statement) -> s_mov_b64 exec, mask: a VALU write of an SGPR read by the SALU
+//     needs no wait state.
+//   * s_mov_b64 exec -> v_fma_f64 and v_fma_f64 -> s_mov_b64 exec: a SALU write of EXEC followed by a VALU
+//     instruction needs no wait state, and a pending VALU instruction keeps the EXEC it was issued with.
+//   * last s_mov_b64 exec, ex0 -> compiler code after the statement (the DPP moves of the next build_window among
+//     it): only a VALU write of EXEC (v_cmpx) puts a 5-state hazard in front of a DPP instruction, which the compiler
+//     could not see inside the string; v_cmpx is therefore not used, every write of EXEC here is a SALU write.
+//   * v_fma_f64 writing R -> a DPP read of R needs 2 states: R is first read by the FMA that forms k, never by a DPP
+//     move, and the restoring s_mov follows the last FMA inside the string.
+#ifndef KS_UPWIND_CNDMASK
+#define KS_SEL_ASM(t) "s_mov_b64 exec, %[m" #t "]\n\tv_fma_f64 %[r" #t "], %[c], %[q" #t "], %[f" #t "]\n\t"
+#define KS_SEL_OUT(t) [r##t] "+v"(bw[t])
+#define KS_SEL_IN(t) [m##t] "s"(m[t]), [q##t] "v"(q[c0 + t + 4]), [f##t] "v"(fw[t])
+#define KS_REP2(X, SEP) X(0) SEP() X(1)
+#define KS_REP3(X, SEP) KS_REP2(X, SEP) SEP() X(2)
+#define KS_REP4(X, SEP) KS_REP3(X, SEP) SEP() X(3)
+#define KS_COMMA() ,
+#define KS_NONE()
+// REP is KS_REP<TJ>: one statement per tile, bw[t] <- fma(-0.25, q[c0 + t + 4], fw[t]) in the lanes of m[t]
+#define KS_MASKED_SELECT(REP)                                                                             \
+    asm volatile(REP(KS_SEL_ASM, KS_NONE) "s_mov_b64 exec, %[ex]"                                                \
+                 : REP(KS_SEL_OUT, KS_COMMA)                                                              \
+                 : REP(KS_SEL_IN, KS_COMMA), [c] "s"(-0.25), [ex] "s"(ex0))
+#endif
+
 // FAST-mode rhs for a tile of TJ consecutive points, written op-major ("vector across the tile") so that
 // consecutive instructions are independent: one wave per SIMD cannot hide the fp64 dependent-issue
 // latency by switching waves, the instruction stream itself has to.
@@ -247,9 +288,17 @@ __device__ __forceinline__ double rhs_point(const double* w, const double* q, in
 // caller scales once per launch).
 template <int TJ, bool DISS = false>
 __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, int c0, const double* phi,
-                                              const StepArgs& a, double* k, double* r = nullptr) {
+                                              const StepArgs& a, unsigned long long ex0, double* k, double* r = nullptr) {
     double lin[TJ], s1[TJ], s2[TJ], s3[TJ], s4[TJ], bw[TJ], fw[TJ];
     [[maybe_unused]] double lap[TJ];
+#ifndef KS_UPWIND_CNDMASK
+    // the masks of the upwind select, formed a whole tile ahead of the scalar unit reading them (KS_MASKED_SELECT)
+    [[maybe_unused]] unsigned long long m[TJ];
+    if constexpr (TJ > 1) {
+#pragma unroll
+        for (int t = 0; t < TJ; ++t) m[t] = __builtin_amdgcn_fcmp(w[c0 + t], 0.0, 4 /* ordered < */);
+    }
+#endif
 #pragma unroll
     for (int t = 0; t < TJ; ++t) s1[t] = w[c0 + t - 1] + w[c0 + t + 1];
 #pragma unroll
@@ -302,14 +351,29 @@ __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, 
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < TJ; ++t) lin[t] = __builtin_fma(a.c_lin[4], s4[t], lin[t]);
+#if defined(KS_UPWIND_CNDMASK)
+    constexpr bool MASKED = false;
+#else
+    constexpr bool MASKED = TJ > 1;   // one point: 2 selects against 2 EXEC writes, nothing to gain
+#endif
+    if constexpr (!MASKED) {
 #pragma unroll
-    for (int t = 0; t < TJ; ++t) fw[t] = __builtin_fma(-0.25, q[c0 + t + 4], fw[t]);
+        for (int t = 0; t < TJ; ++t) fw[t] = __builtin_fma(-0.25, q[c0 + t + 4], fw[t]);
+    }
 #pragma unroll
     for (int t = 0; t < TJ; ++t) bw[t] = __builtin_fma(0.25, q[c0 + t - 4], bw[t]);
     __builtin_amdgcn_sched_barrier(0);
+#ifndef KS_UPWIND_CNDMASK
+    if constexpr (MASKED) {
+        // the forward chain's last FMA lands on bw[t] in the lanes with u < 0 (see KS_MASKED_SELECT): bw[t] becomes sel
+        if constexpr (TJ == 4) KS_MASKED_SELECT(KS_REP4);
+        if constexpr (TJ == 3) KS_MASKED_SELECT(KS_REP3);
+        if constexpr (TJ == 2) KS_MASKED_SELECT(KS_REP2);
+    }
+#endif
 #pragma unroll
     for (int t = 0; t < TJ; ++t) {
-        const double sel = (w[c0 + t] < 0.0) ? fw[t] : bw[t];  // u == 0 selects the backward stencil
+        const double sel = MASKED ? bw[t] : ((w[c0 + t] < 0.0) ? fw[t] : bw[t]);  // u == 0 selects the backward stencil
         k[t] = __builtin_fma(a.mh_inv_dx, sel, lin[t]);
         if constexpr (DISS) {
             r[0] = __builtin_fma(w[c0 + t], phi[t], r[0]);
@@ -372,14 +436,14 @@ __host__ __device__ constexpr int tile_of() { return P % 4 == 0 ? 4 : (P % 3 == 
 
 template <int P, bool EXACT>
 __device__ __forceinline__ void eval_rhs(const double* w, const double* q, const double (&phi)[P],
-                                         const StepArgs& a, double (&kk)[P]) {
+                                         const StepArgs& a, unsigned long long ex0, double (&kk)[P]) {
     if constexpr (EXACT) {
 #pragma unroll
         for (int j = 0; j < P; ++j) kk[j] = rhs_point<true>(w, q, 4 + j, phi[j], a);
     } else {
         constexpr int TJ = tile_of<P>();
 #pragma unroll
-        for (int jb = 0; jb < P; jb += TJ) rhs_tile_fast<TJ>(w, q, 4 + jb, &phi[jb], a, &kk[jb]);
+        for (int jb = 0; jb < P; jb += TJ) rhs_tile_fast<TJ>(w, q, 4 + jb, &phi[jb], a, ex0, &kk[jb]);
     }
 }
 
@@ -388,7 +452,8 @@ __device__ __forceinline__ void eval_rhs(const double* w, const double* q, const
 //   FAST : r[0] += u*phi, r[1] += sel^2, r[2] += lap^2 (unscaled, see rhs_tile_fast)
 template <int P, bool EXACT>
 __device__ __forceinline__ void eval_rhs_dissipation(const double* w, const double* q, const double (&phi)[P],
-                                                     const StepArgs& a, double (&kk)[P], double (&r)[3]) {
+                                                     const StepArgs& a, unsigned long long ex0, double (&kk)[P],
+                                                     double (&r)[3]) {
     if constexpr (EXACT) {
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -399,7 +464,7 @@ __device__ __forceinline__ void eval_rhs_dissipation(const double* w, const doub
     } else {
         constexpr int TJ = tile_of<P>();
 #pragma unroll
-        for (int jb = 0; jb < P; jb += TJ) rhs_tile_fast<TJ, true>(w, q, 4 + jb, &phi[jb], a, &kk[jb], r);
+        for (int jb = 0; jb < P; jb += TJ) rhs_tile_fast<TJ, true>(w, q, 4 + jb, &phi[jb], a, ex0, &kk[jb], r);
     }
 }
 
@@ -467,6 +532,8 @@ template <int P, int G, int HALO, bool EXACT, bool DISS>
 __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
     static_assert(!(DISS && (HALO == HALO_HYBRID || HALO == HALO_HYBRID1)), "no dissipation form of the hybrid layouts");
     constexpr int EPW = 64 / G;  // envs per wavefront
+    // EXEC as the kernel was entered: what the masked upwind select of rhs_tile_fast restores (see KS_MASKED_SELECT)
+    [[maybe_unused]] const unsigned long long ex0 = __builtin_amdgcn_read_exec();
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int gl = lane & (G - 1);
@@ -514,11 +581,11 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
 #pragma unroll
             for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
             if constexpr (DISS) {
-                eval_rhs_dissipation<P, EXACT>(w, q, phi, a, kk, rd);
+                eval_rhs_dissipation<P, EXACT>(w, q, phi, a, ex0, kk, rd);
             } else {
 #pragma unroll
                 for (int j = 0; j < P; ++j) racc += q[4 + j];
-                eval_rhs<P, EXACT>(w, q, phi, a, kk);
+                eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
             }
         }
 #pragma unroll
@@ -542,7 +609,7 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
             build_window<P, G, HALO, EXACT>(halo, us, w);
 #pragma unroll
             for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
-            eval_rhs<P, EXACT>(w, q, phi, a, kk);
+            eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
         }
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -565,7 +632,7 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
             build_window<P, G, HALO, EXACT>(halo, us, w);
 #pragma unroll
             for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
-            eval_rhs<P, EXACT>(w, q, phi, a, kk);
+            eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
         }
 #pragma unroll
         for (int j = 0; j < P; ++j) {
@@ -588,7 +655,7 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
             build_window<P, G, HALO, EXACT>(halo, us, w);
 #pragma unroll
             for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
-            eval_rhs<P, EXACT>(w, q, phi, a, kk);
+            eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
         }
 #pragma unroll
         for (int j = 0; j < P; ++j) {

@@ -2,11 +2,15 @@
 """Instruction mix of one RK4 sub-step (the innermost loop body) of the fused KS stepper layouts, from the gfx950
 assembly (hipcc -S).  Every wave64 VALU instruction -- fp64 FMA, 32-bit DPP move or select alike -- holds its SIMD's
 issue port for 4 cycles, so the VALU count x 4 cycles x sub-steps is the issue floor of a launch with one wave per SIMD.
-usage: tools/ks_isa_mix.py > profiles/rNN_ks_isa_mix.txt"""
+Next to the VALU count stands the total of issued instructions of the loop (scalar, LDS-pipe and branch included): the
+bound if every issued instruction costs the lone wave a slot.  Registers, scratch and spills are the kernel's own
+metadata.  Extra arguments go to the compiler (-DKS_UPWIND_CNDMASK: the plain-select build).
+usage: tools/ks_isa_mix.py [-DNAME ...] > profiles/ks_isa_mix.txt"""
 import collections
 import os
 import re
 import subprocess
+import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,8 +25,24 @@ KERNELS = [("C2 default: 1 point/lane, DPP wave chain", "_ZN2ks12ks_rk4_fusedILi
 with tempfile.TemporaryDirectory() as tmp:
     asm = os.path.join(tmp, "ks.s")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", "-S",
-                    "--cuda-device-only", "-o", asm, SRC], check=True, capture_output=True)
+                    "--cuda-device-only", "-o", asm, SRC] + sys.argv[1:], check=True, capture_output=True)
     lines = open(asm).read().splitlines()
+
+if sys.argv[1:]:
+    print("compiler arguments:", " ".join(sys.argv[1:]))
+
+
+def resources(sym):
+    """VGPRs, scratch bytes and spilled registers of a kernel, from its .amdhsa_kernel block and metadata."""
+    i = next(i for i, l in enumerate(lines) if l.strip() == f".amdhsa_kernel {sym}")
+    blk = lines[i:next(j for j in range(i, len(lines)) if ".end_amdhsa_kernel" in lines[j])]
+    get = lambda key: next(l.split()[-1] for l in blk if l.strip().startswith(key))
+    # the metadata keys of a kernel are sorted: its spill counts follow its .name within a few lines
+    j = next(j for j, l in enumerate(lines) if l.split() == [".name:", sym])
+    meta = dict(l.split() for l in lines[j:j + 12] if len(l.split()) == 2)
+    spills = int(meta[".vgpr_spill_count:"]) + int(meta[".sgpr_spill_count:"])
+    return int(get(".amdhsa_next_free_vgpr")), int(get(".amdhsa_private_segment_fixed_size")), spills
+
 
 for title, sym, ppl in KERNELS:
     start = next(i for i, l in enumerate(lines) if l.startswith(sym + ":"))
@@ -39,12 +59,17 @@ for title, sym, ppl in KERNELS:
             continue
         ops[t.split()[0]] += 1
     valu = sum(n for k, n in ops.items() if k.startswith("v_"))
+    total = sum(ops.values())
+    vgprs, scratch, spills = resources(sym)
     lds = sum(n for k, n in ops.items() if k.startswith("ds_"))
     fp64 = sum(n for k, n in ops.items() if k.startswith("v_") and "f64" in k)
     print(f"== {title}")
     print(f"   VALU {valu} per lane and sub-step ({valu / ppl:.1f} per grid point), of which fp64 arithmetic {fp64}, "
           f"DPP moves {ops.get('v_mov_b32_dpp', 0)}, selects {ops.get('v_cndmask_b32_e32', 0)}; LDS-pipe (ds_bpermute) {lds}; "
           f"s_nop {ops.get('s_nop', 0)}, s_waitcnt {ops.get('s_waitcnt', 0)}")
-    print(f"   issue floor at one wave per SIMD: {valu} x 4 cycles = {valu * 4} cycles per sub-step per wave")
+    print(f"   all issued instructions {total} per lane and sub-step, of which EXEC writes (s_mov_b64) "
+          f"{ops.get('s_mov_b64', 0)}; VGPRs {vgprs}, scratch {scratch} bytes, spilled registers {spills}")
+    print(f"   issue floor at one wave per SIMD: {valu} x 4 cycles = {valu * 4} cycles per sub-step per wave "
+          f"({total * 4} if every issued instruction costs a slot)")
     for k, n in ops.most_common():
         print(f"      {n:5d}  {k}")
