@@ -211,3 +211,78 @@ def full_state(agent):
     out["alpha"] = torch.as_tensor(agent.alpha).detach().cpu().clone().reshape(-1).float()
     out["updates"] = torch.tensor(agent.updates)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the optimizer half: an fp64 replay of one Adam step and of the Polyak average, and the units they are judged in
+# ---------------------------------------------------------------------------------------------------------------------
+U = 2.0 ** -24             # fp32 unit roundoff
+UNIT_BOUND = 4.0           # m' sees at most 3 fp32 roundings, v' 4, target' 3, p' 8 on the step and one on the result
+#: three optimizers that share no hyper-parameter: an index into sac_config's lr[3], beta1[3], beta2[3], eps[3] that is
+#: off by one, or two betas swapped, changes a step by far more than a unit
+HYPERS = {"critic_optim": dict(lr=3e-4, betas=(0.9, 0.999), eps=1e-8),
+          "policy_optim": dict(lr=1e-4, betas=(0.8, 0.99), eps=1e-6),
+          "alpha_optim": dict(lr=1e-3, betas=(0.7, 0.95), eps=1e-7)}
+
+
+def optimizers(agent):
+    names = ("critic_optim", "policy_optim") + (("alpha_optim",) if agent.automatic_entropy_tuning else ())
+    return [(name, getattr(agent, name)) for name in names]
+
+
+def set_distinct_hypers(agent):
+    """HYPERS on ``param_groups[0]`` of the agent's optimizers (before the first fused call, or between two updates)."""
+    for name, opt in optimizers(agent):
+        opt.param_groups[0].update(HYPERS[name])
+
+
+def hypers_of(opt):
+    g = opt.param_groups[0]
+    return dict(lr=float(g["lr"]), beta1=float(g["betas"][0]), beta2=float(g["betas"][1]), eps=float(g["eps"]))
+
+
+def _f64(x):
+    return (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)).astype(np.float64)
+
+
+def adam_replay(p, m, v, g, t, lr, beta1, beta2, eps, fp32_hyper=False):
+    """One step of torch.optim.Adam (no weight decay, no amsgrad) in fp64 numpy from fp32 inputs: (p', m', v').
+    ``fp32_hyper`` rounds lr, beta1, beta2 and eps to fp32 first, which is what the C ABI hands the kernels."""
+    if fp32_hyper:
+        lr, beta1, beta2, eps = (float(np.float32(x)) for x in (lr, beta1, beta2, eps))
+    p, m, v, g = (_f64(x) for x in (p, m, v, g))
+    m1 = m + (g - m) * (1.0 - beta1)
+    v1 = beta2 * v + (1.0 - beta2) * g * g
+    p1 = p - lr / (1.0 - beta1 ** t) * (m1 / (np.sqrt(v1) / np.sqrt(1.0 - beta2 ** t) + eps))
+    return p1, m1, v1
+
+
+def polyak_replay(target, p_new, tau, fp32_hyper=True):
+    """target (1 - tau) + p_new tau in fp64 numpy from fp32 inputs (``tau`` rounded to fp32 first unless told otherwise)."""
+    tau = float(np.float32(tau)) if fp32_hyper else float(tau)
+    return _f64(target) * (1.0 - tau) + _f64(p_new) * tau
+
+
+def _worst_units(got, ref, unit):
+    """max |got - ref| / unit; an element whose unit is zero (a quantity that is exactly zero and stays so) must match."""
+    err = np.abs(_f64(got) - ref)
+    assert err.shape == unit.shape
+    assert not np.any((unit == 0) & (err != 0)), "a zero quantity moved"
+    if err.size == 0:
+        return 0.0
+    return float(np.max(np.where(unit > 0, err / np.where(unit > 0, unit, 1.0), 0.0)))
+
+
+def adam_units(p, m, v, g, got_p, got_m, got_v, ref):
+    """How far (p', m', v') = ``got_*`` sits from ``ref = adam_replay(...)``, in units: u max(|m|, |g|) for m',
+    u max(v, g^2) for v', u |p| + 16 u |p'_ref - p| for p'.  Returns {"m": .., "v": .., "p": ..} (the worst element)."""
+    p, m, v, g = (_f64(x) for x in (p, m, v, g))
+    p1, m1, v1 = ref
+    return {"m": _worst_units(got_m, m1, U * np.maximum(np.abs(m), np.abs(g))),
+            "v": _worst_units(got_v, v1, U * np.maximum(v, g * g)),
+            "p": _worst_units(got_p, p1, U * np.abs(p) + 16 * U * np.abs(p1 - p))}
+
+
+def polyak_units(target, p_new, got, ref):
+    target, p_new = _f64(target), _f64(p_new)
+    return _worst_units(got, ref, U * np.maximum(np.abs(target), np.abs(p_new)))

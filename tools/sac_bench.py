@@ -106,14 +106,16 @@ def collect_parity(path, out):
         elif isinstance(v, (int, float)):
             yield prefix, float(v)
     for r in rows:
-        for key, val in flat("", {k: v for k, v in r.items() if k not in ("case", "tol", "cap", "atol_scale", "q_gap", "first", "last")}):
+        for key, val in flat("", {k: v for k, v in r.items() if k not in ("case", "tol", "cap", "bound", "atol_scale", "q_gap", "first", "last")}):
             group = r["case"].split("-")[0] + ":" + key
             if val >= worst.get(group, {"max": -1.0})["max"]:
                 worst[group] = {"max": val, "case": r["case"]}
     rec = {"what": "deviations tests/test_sac_gpu.py observed on an MI355X: forward outputs and gradients against the CPU "
                    "module in fp64 relative to each tensor's maximum (next to the fp32 torch spelling on the CPU against the "
                    "same fp64), shares of elements whose first Adam step differs from the fp64 step by more than 0.1 lr, "
-                   "relative loss differences", "worst": worst, "cases": rows}
+                   "relative loss differences; from tests/test_sac_optimizer_gpu.py the worst distance, in units (bound 4), of every "
+                   "Adam moment, parameter, log_alpha and target element from the fp64 replay of each update", "worst": worst,
+           "cases": rows}
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
