@@ -259,8 +259,8 @@ __device__ __forceinline__ double rhs_point(const double* w, const double* q, in
 //   * s_mov_b64 exec -> v_fma_f64 and v_fma_f64 -> s_mov_b64 exec: a SALU write of EXEC followed by a VALU
 //     instruction needs no wait state, and a pending VALU instruction keeps the EXEC it was issued with.
 //   * last s_mov_b64 exec, ex0 -> compiler code after the statement (the DPP moves of the next build_window among
-//     it): only a VALU write of EXEC (v_cmpx) puts a 5-state hazard in front of a DPP instruction, which the compiler
-//     could not see inside the string; v_cmpx is therefore not used, every write of EXEC here is a SALU write.
+//     it): only a VALU write of EXEC puts a 5-state hazard in front of a DPP instruction, which the compiler could not
+//     see inside the string; a SALU write does not.
 //   * v_fma_f64 writing R -> a DPP read of R needs 2 states: R is first read by the FMA that forms k, never by a DPP
 //     move, and the restoring s_mov follows the last FMA inside the string.
 #ifndef KS_UPWIND_CNDMASK
@@ -532,6 +532,16 @@ template <int P, int G, int HALO, bool EXACT, bool DISS>
 __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
     static_assert(!(DISS && (HALO == HALO_HYBRID || HALO == HALO_HYBRID1)), "no dissipation form of the hybrid layouts");
     constexpr int EPW = 64 / G;  // envs per wavefront
+    // SLOTS: the fast-mode sub-step loop without two kinds of issue slots that are no arithmetic: the waits
+    // for the prologue's loads, issued once in front of the loop, and the 16 copies behind the stage-4 update, which is
+    // written in its three-address form.  Every floating-point operation, operand and order is the one of the loop
+    // before: -DKS_LOOP0 builds that loop (lib/libkspde_loop0.so, the A/B partner of tools/ks_select_ab.py --libs loop
+    // and tests/test_ks_loop_slots_gpu.py).  Exact mode is the same in both.
+#ifdef KS_LOOP0
+    constexpr bool SLOTS = false;
+#else
+    constexpr bool SLOTS = !EXACT;
+#endif
     // EXEC as the kernel was entered: what the masked upwind select of rhs_tile_fast restores (see KS_MASKED_SELECT)
     [[maybe_unused]] const unsigned long long ex0 = __builtin_amdgcn_read_exec();
     const int lane = threadIdx.x & 63;
@@ -567,6 +577,17 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
         for (int j = 0; j < P; ++j) phi[j] = 0.0;
     }
 
+    // The step constants of the stage updates (fetched by scalar loads that the compiler issues right in front of the loop).
+    [[maybe_unused]] double hdt = a.hdt, dt6 = a.dt6, dt3 = a.dt3, dt = a.dt;
+    if constexpr (SLOTS) {
+        // The prologue's loads are waited for HERE, once: the empty statements need u, phi and the step constants in
+        // their registers, so the s_waitcnt vmcnt / lgkmcnt land in front of the loop and not, re-issued every sub-step,
+        // inside it (3 + 1 at P = 16).
+#pragma unroll
+        for (int j = 0; j < P; ++j) asm volatile("" : "+v"(u[j]), "+v"(phi[j]));
+        asm volatile("" : "+s"(hdt), "+s"(dt6), "+s"(dt3), "+s"(dt));
+    }
+
     double racc = 0.0;
     [[maybe_unused]] double rd[3] = {0.0, 0.0, 0.0};   // dissipation partial sums (see eval_rhs_dissipation)
     for (long s = 0; s < a.n_substeps; ++s) {
@@ -595,8 +616,8 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
                 acc[j] = k;
                 usn[j] = u[j] + a.dt * k / 2.0;
             } else {
-                acc[j] = __builtin_fma(a.dt6, k, u[j]);
-                usn[j] = __builtin_fma(a.hdt, k, u[j]);
+                acc[j] = __builtin_fma(dt6, k, u[j]);
+                usn[j] = __builtin_fma(hdt, k, u[j]);
             }
         }
         // ---- stage 2 ----
@@ -618,8 +639,8 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
                 acc[j] = acc[j] + 2.0 * k;
                 usn[j] = u[j] + a.dt * k / 2.0;
             } else {
-                acc[j] = __builtin_fma(a.dt3, k, acc[j]);
-                usn[j] = __builtin_fma(a.hdt, k, u[j]);
+                acc[j] = __builtin_fma(dt3, k, acc[j]);
+                usn[j] = __builtin_fma(hdt, k, u[j]);
             }
         }
         // ---- stage 3 ----
@@ -641,8 +662,8 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
                 acc[j] = acc[j] + 2.0 * k;
                 usn[j] = u[j] + a.dt * k;
             } else {
-                acc[j] = __builtin_fma(a.dt3, k, acc[j]);
-                usn[j] = __builtin_fma(a.dt, k, u[j]);
+                acc[j] = __builtin_fma(dt3, k, acc[j]);
+                usn[j] = __builtin_fma(dt, k, u[j]);
             }
         }
         // ---- stage 4 + update ----
@@ -663,8 +684,12 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
             if constexpr (EXACT) {
                 acc[j] = acc[j] + k;
                 u[j] = u[j] + div_const(a.dt * acc[j], 6.0, 1.0 / 6.0);
+            } else if constexpr (SLOTS) {
+                // The same FMA, u = fma(dt6, k, acc), in its three-address form: the compiler ties a v_fmac to acc's
+                // registers and copies the result to u's (one v_mov_b64 per point and sub-step); this lands in u's.
+                asm("v_fma_f64 %0, %1, %2, %3" : "=v"(u[j]) : "s"(dt6), "v"(k), "v"(acc[j]));
             } else {
-                u[j] = __builtin_fma(a.dt6, k, acc[j]);
+                u[j] = __builtin_fma(dt6, k, acc[j]);
             }
         }
     }
