@@ -117,28 +117,7 @@ hipError_t copy_async(const ks_handle* h, void* dst, const void* src, size_t byt
 }
 hipError_t stream_sync(const ks_handle* h) { return h->cpu ? hipSuccess : hipStreamSynchronize(h->stream); }
 
-void fill_args(const ks_handle* h, ks::StepArgs& a) {
-    std::memset(&a, 0, sizeof(a));
-    const double dx = h->dx, dt = h->dt;
-    a.N = h->N;
-    a.n_act = h->n_act;
-    a.F = h->d_F;
-    a.dt = dt;
-    a.dx = dx;
-    a.dx2 = dx * dx;          // python: self.dx**2
-    a.dx4 = std::pow(dx, 4.0);  // python: self.dx**4
-    a.r_dx = 1.0 / a.dx;        // IEEE divisions on the host: correctly rounded reciprocals
-    a.r_dx2 = 1.0 / a.dx2;
-    a.r_dx4 = 1.0 / a.dx4;
-    // merged linear stencil  -(u_xxxx + u_xx):  c_k = -(D4_k/dx^4 + D2_k/dx^2)
-    const double d2[5] = {-49.0 / 18, 3.0 / 2, -3.0 / 20, 1.0 / 90, 0.0};
-    const double d4[5] = {91.0 / 8, -122.0 / 15, 169.0 / 60, -2.0 / 5, 7.0 / 240};
-    for (int k = 0; k < 5; ++k) a.c_lin[k] = -(d4[k] / a.dx4 + d2[k] / a.dx2);
-    a.mh_inv_dx = -0.5 / dx;
-    a.hdt = dt / 2.0;
-    a.dt6 = dt / 6.0;
-    a.dt3 = dt / 3.0;
-}
+ks::Consts consts_of(const ks_handle* h) { return ks::make_consts(h->dx, h->dt); }
 
 // Choose (variant, G, P, block, grid) for n_rows envs.
 int choose_layout(const ks_handle* h, int n_rows, ks::Layout& lay) {
@@ -199,24 +178,9 @@ int do_step(ks_handle* h, const float* d_phi, const float* d_actions, const int*
         return fail(KS_ERR_INVALID, "ks_step_actions needs ks_set_forcing first");
     const int rows = d_env_ids ? n_rows : h->E;
     if (rows < 0 || rows > h->E) return fail(KS_ERR_INVALID, "n_rows out of range");
-    ks::StepArgs a;
-    fill_args(h, a);
     if (h->cpu) {
-        kscpu::Params p{};
-        p.N = h->N;
-        p.dt = a.dt;
-        p.dx = a.dx;
-        p.dx2 = a.dx2;
-        p.dx4 = a.dx4;
-        for (int k = 0; k < 5; ++k) p.c_lin[k] = a.c_lin[k];
-        p.mh_inv_dx = a.mh_inv_dx;
-        p.hdt = a.hdt;
-        p.dt6 = a.dt6;
-        p.dt3 = a.dt3;
-        p.r_dx2 = a.r_dx2;
-        p.r_dx4 = a.r_dx4;
-        kscpu::step(p, h->mode, h->objective, h->d_u, d_phi, d_actions, h->d_F, h->n_act, d_env_ids, rows, n_substeps, d_obs, d_ssq,
-                    d_status, h->cpu_threads);
+        kscpu::step(h->N, consts_of(h), h->mode, h->objective, h->d_u, d_phi, d_actions, h->d_F, h->n_act, d_env_ids, rows,
+                    n_substeps, d_obs, d_ssq, d_status, h->cpu_threads);
         return KS_OK;
     }
     ks::Layout lay;
@@ -225,6 +189,11 @@ int do_step(ks_handle* h, const float* d_phi, const float* d_actions, const int*
     if (h->objective == KS_OBJECTIVE_DISSIPATION && d_ssq &&
         (lay.variant == KS_VARIANT_WAVE64_HYBRID || lay.variant == KS_VARIANT_WAVE64_HYBRID1))
         return fail(KS_ERR_UNSUPPORTED, "kernel variant %d has no dissipation-objective form", lay.variant);
+    ks::StepArgs a{};
+    a.k = consts_of(h);
+    a.N = h->N;
+    a.n_act = h->n_act;
+    a.F = h->d_F;
     a.u = h->d_u;
     a.phi = d_phi;
     a.actions = d_actions;
@@ -660,7 +629,7 @@ int ks_reward_rows_device(ks_handle* h, int objective, const float* d_obs, const
     if (n_rows > 0 && (!d_obs || !d_reward)) return fail(KS_ERR_INVALID, "NULL argument");
     if ((size_t)n_rows * (size_t)h->N > (size_t)1 << 31) return fail(KS_ERR_INVALID, "n_rows * N too large");
     if (h->cpu) {
-        kscpu::reward_rows(h->N, h->dx, objective, d_obs, d_phi, n_rows, d_reward);
+        kscpu::reward_rows(h->N, consts_of(h), objective, d_obs, d_phi, n_rows, d_reward);
         return KS_OK;
     }
     DeviceGuard g(h->device);
@@ -736,8 +705,7 @@ int ks_rhs(ks_handle* h, const double* u_host, const float* phi_host, int n_rows
     if (!h || !u_host || !phi_host || !rhs) return fail(KS_ERR_INVALID, "NULL argument");
     if (n_rows <= 0) return fail(KS_ERR_INVALID, "n_rows <= 0");
     if (h->cpu) {
-        const double dx = h->dx;
-        kscpu::rhs(h->N, dx, dx * dx, std::pow(dx, 4.0), u_host, phi_host, n_rows, rhs, ux, uxx, uxxxx);
+        kscpu::rhs(h->N, consts_of(h), u_host, phi_host, n_rows, rhs, ux, uxx, uxxxx);
         return KS_OK;
     }
     DeviceGuard g(h->device);

@@ -1,5 +1,6 @@
 // ks_cpu.cpp -- CPU twin of the fused KS stepper (see ks_cpu.h).  Compiled with -ffp-contract=off: the exact mode must keep
-// the reference's unfused multiply / add order; the fast mode spells its FMAs out.
+// the reference's unfused multiply / add order; the fast mode spells its FMAs out.  The per-point arithmetic and the RK4
+// stage updates are the ones of ks_internal.h, the text the GPU kernels are built from; the twin keeps the true division.
 //
 // What is computed (reference, paths relative to the reference root):
 //   pdegym/kuramoto/kuramoto.py:118-129  rhs(u, phi) with the periodic stencil tables :24-27
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace kscpu {
@@ -36,82 +38,40 @@ inline void window(const double* x, int N, double* w, double* q) {
     for (int i = 0; i < N + 8; ++i) q[i] = w[i] * w[i];
 }
 
-// reference operation order (scipy correlate1d walks the flipped kernel from the far right tap; kuramoto.py:118-129)
-inline void rhs_exact(const Params& p, const double* w, const double* q, const double* phi, int N, double* out,
-                      double* ux, double* uxx, double* uxxxx) {
-    const double dx = p.dx, dx2 = p.dx2, dx4 = p.dx4;
+// reference operation order with true divisions (ks::ref_point, kuramoto.py:118-129) over a padded row
+inline void rhs_exact(const Consts& c, const double* w, const double* q, const double* phi, int N, double* out, double* ux,
+                      double* uxx, double* uxxxx) {
     for (int i = 0; i < N; ++i) {
-        const int c = i + 4;
-        double fwd = q[c + 4] * (-1.0 / 4);
-        fwd += q[c] * (-25.0 / 12);
-        fwd += q[c + 1] * 4.0;
-        fwd += q[c + 2] * (-3.0);
-        fwd += q[c + 3] * (4.0 / 3);
-        double bwd = q[c - 4] * (1.0 / 4);
-        bwd += q[c - 3] * (-4.0 / 3);
-        bwd += q[c - 2] * 3.0;
-        bwd += q[c - 1] * (-4.0);
-        bwd += q[c] * (25.0 / 12);
-        const double f = fwd / dx, b = bwd / dx, u = w[c];
-        const double d1 = (u < 0.0 ? 1.0 : 0.0) * f + (u >= 0.0 ? 1.0 : 0.0) * b;   // u == 0 -> backward
-        double d2 = u * (-49.0 / 18);
-        d2 += (w[c - 3] + w[c + 3]) * (1.0 / 90);
-        d2 += (w[c - 2] + w[c + 2]) * (-3.0 / 20);
-        d2 += (w[c - 1] + w[c + 1]) * (3.0 / 2);
-        d2 = d2 / dx2;
-        double d4 = u * (91.0 / 8);
-        d4 += (w[c - 4] + w[c + 4]) * (7.0 / 240);
-        d4 += (w[c - 3] + w[c + 3]) * (-2.0 / 5);
-        d4 += (w[c - 2] + w[c + 2]) * (169.0 / 60);
-        d4 += (w[c - 1] + w[c + 1]) * (-122.0 / 15);
-        d4 = d4 / dx4;
-        out[i] = ((-d4 - d2) - 0.5 * d1) + phi[i];
-        if (ux) ux[i] = d1;
-        if (uxx) uxx[i] = d2;
-        if (uxxxx) uxxxx[i] = d4;
+        const ks::RefPoint p = ks::ref_point<ks::DivIeee>(w, q, i + 4, phi[i], c);
+        out[i] = p.rhs;
+        if (ux) ux[i] = p.d1;
+        if (uxx) uxx[i] = p.d2;
+        if (uxxxx) uxxxx[i] = p.d4;
     }
 }
 
-// merged linear stencil + both upwind sums sharing the centre term, FMA chains in the order of rhs_tile_fast.
-// TERMS (dissipation objective): also the unscaled reward terms of rhs_tile_fast -- sel (the selected upwind sum) and
-// lap (the 7-point u_xx stencil) per point.
-template <bool TERMS = false>
-inline void rhs_fast(const Params& p, const double* w, const double* q, const double* phi, int N, double* out,
-                     double* sel_out = nullptr, double* lap_out = nullptr) {
-    const double c0 = p.c_lin[0], c1 = p.c_lin[1], c2 = p.c_lin[2], c3 = p.c_lin[3], c4 = p.c_lin[4];
-    const double m = p.mh_inv_dx;
-    for (int i = 0; i < N; ++i) {
-        const int c = i + 4;
-        double lin = __builtin_fma(c0, w[c], phi[i]);
-        lin = __builtin_fma(c1, w[c - 1] + w[c + 1], lin);
-        lin = __builtin_fma(c2, w[c - 2] + w[c + 2], lin);
-        lin = __builtin_fma(c3, w[c - 3] + w[c + 3], lin);
-        lin = __builtin_fma(c4, w[c - 4] + w[c + 4], lin);
-        double bw = (25.0 / 12) * q[c];
-        double fw = __builtin_fma(4.0, q[c + 1], -bw);   // fw holds MINUS the forward sum
-        bw = __builtin_fma(-4.0, q[c - 1], bw);
-        fw = __builtin_fma(-3.0, q[c + 2], fw);
-        bw = __builtin_fma(3.0, q[c - 2], bw);
-        fw = __builtin_fma(4.0 / 3, q[c + 3], fw);
-        bw = __builtin_fma(-4.0 / 3, q[c - 3], bw);
-        fw = __builtin_fma(-0.25, q[c + 4], fw);
-        bw = __builtin_fma(0.25, q[c - 4], bw);
-        const double sel = (w[c] < 0.0) ? fw : bw;       // u == 0 selects the backward stencil
-        out[i] = __builtin_fma(m, sel, lin);
-        if constexpr (TERMS) {
-            double lap = (-49.0 / 18) * w[c];
-            lap = __builtin_fma(3.0 / 2, w[c - 1] + w[c + 1], lap);
-            lap = __builtin_fma(-3.0 / 20, w[c - 2] + w[c + 2], lap);
-            lap_out[i] = __builtin_fma(1.0 / 90, w[c - 3] + w[c + 3], lap);
-            sel_out[i] = sel;
+// k = rhs of one stage over a padded row.  TERMS (stage 1 of the dissipation objective): also the per-point reward terms
+// t1 / t2 -- EXACT the reference's u_x and u_xx, FAST the unscaled sel and lap of ks::fast_point.
+template <bool EXACT, bool TERMS>
+inline void rhs_row(const Consts& c, const double* w, const double* q, const double* phi, int N, double* k, double* t1,
+                    double* t2) {
+    if constexpr (EXACT) {
+        rhs_exact(c, w, q, phi, N, k, TERMS ? t1 : nullptr, TERMS ? t2 : nullptr, nullptr);
+    } else {
+        for (int i = 0; i < N; ++i) {
+            const ks::FastPoint p = ks::fast_point<TERMS>(w, q, i + 4, phi[i], c);
+            k[i] = p.k;
+            if constexpr (TERMS) {
+                t1[i] = p.sel;
+                t2[i] = p.lap;
+            }
         }
     }
 }
 
 // DISS: the reward accumulator collects the dissipation terms (kspde.h ks_objective) instead of sum u^2
 template <bool EXACT, bool DISS>
-void advance_env(const Params& p, double* u, const double* phi, long n_substeps, Scratch& s, double* ssq_out) {
-    const int N = p.N;
+void advance_env(int N, const Consts& c, double* u, const double* phi, long n_substeps, Scratch& s, double* ssq_out) {
     double* w = s.w.data();
     double* q = s.q.data();
     double* k = s.k.data();
@@ -119,87 +79,49 @@ void advance_env(const Params& p, double* u, const double* phi, long n_substeps,
     double* us = s.us.data();
     double* t1 = s.t1.data();
     double* t2 = s.t2.data();
-    const double dt = p.dt;
+    // one RK4 stage: the rhs at the stage state (stage 1's is formed with the reward terms, below), then the stage's
+    // update (ks::rk4_update; stage 4 writes the new u)
+    auto stage = [&](auto stage_no) {
+        constexpr int STAGE = decltype(stage_no)::value;
+        if constexpr (STAGE > 1) {
+            window(us, N, w, q);
+            rhs_row<EXACT, false>(c, w, q, phi, N, k, nullptr, nullptr);
+        }
+        double* next = STAGE == 4 ? u : us;
+        for (int i = 0; i < N; ++i) ks::rk4_update<EXACT, STAGE, ks::DivIeee>(k[i], u[i], acc[i], next[i], c);
+    };
     double racc = 0.0;
     double rx = 0.0, rxx = 0.0;   // fast-mode dissipation: unscaled sel^2 / lap^2 sums
     for (long step = 0; step < n_substeps; ++step) {
         // stage 1 + the reward term of this sub-step (taken BEFORE the update, kuramoto.py:84)
         window(u, N, w, q);
+        rhs_row<EXACT, DISS>(c, w, q, phi, N, k, t1, t2);
         if constexpr (!DISS) {
             double row = 0.0;
             for (int i = 0; i < N; ++i) row += q[4 + i];
             racc += row;
-        }
-        if constexpr (EXACT) {
-            if constexpr (DISS) {
-                rhs_exact(p, w, q, phi, N, k, t1, t2, nullptr);
-                double row = 0.0;
-                for (int i = 0; i < N; ++i) row += (t2[i] * t2[i] + t1[i] * t1[i]) + w[4 + i] * phi[i];
-                racc += row;
-            } else {
-                rhs_exact(p, w, q, phi, N, k, nullptr, nullptr, nullptr);
-            }
-            for (int i = 0; i < N; ++i) {
-                acc[i] = k[i];
-                us[i] = u[i] + dt * k[i] / 2.0;
-            }
-            window(us, N, w, q);
-            rhs_exact(p, w, q, phi, N, k, nullptr, nullptr, nullptr);
-            for (int i = 0; i < N; ++i) {
-                acc[i] = acc[i] + 2.0 * k[i];
-                us[i] = u[i] + dt * k[i] / 2.0;
-            }
-            window(us, N, w, q);
-            rhs_exact(p, w, q, phi, N, k, nullptr, nullptr, nullptr);
-            for (int i = 0; i < N; ++i) {
-                acc[i] = acc[i] + 2.0 * k[i];
-                us[i] = u[i] + dt * k[i];
-            }
-            window(us, N, w, q);
-            rhs_exact(p, w, q, phi, N, k, nullptr, nullptr, nullptr);
-            for (int i = 0; i < N; ++i) {
-                acc[i] = acc[i] + k[i];
-                u[i] = u[i] + dt * acc[i] / 6.0;
-            }
+        } else if constexpr (EXACT) {
+            double row = 0.0;
+            for (int i = 0; i < N; ++i) row += (t2[i] * t2[i] + t1[i] * t1[i]) + w[4 + i] * phi[i];
+            racc += row;
         } else {
-            if constexpr (DISS) {
-                rhs_fast<true>(p, w, q, phi, N, k, t1, t2);
-                for (int i = 0; i < N; ++i) {
-                    racc = __builtin_fma(w[4 + i], phi[i], racc);
-                    rx = __builtin_fma(t1[i], t1[i], rx);
-                    rxx = __builtin_fma(t2[i], t2[i], rxx);
-                }
-            } else {
-                rhs_fast(p, w, q, phi, N, k);
-            }
             for (int i = 0; i < N; ++i) {
-                acc[i] = __builtin_fma(p.dt6, k[i], u[i]);
-                us[i] = __builtin_fma(p.hdt, k[i], u[i]);
+                racc = __builtin_fma(w[4 + i], phi[i], racc);
+                rx = __builtin_fma(t1[i], t1[i], rx);
+                rxx = __builtin_fma(t2[i], t2[i], rxx);
             }
-            window(us, N, w, q);
-            rhs_fast(p, w, q, phi, N, k);
-            for (int i = 0; i < N; ++i) {
-                acc[i] = __builtin_fma(p.dt3, k[i], acc[i]);
-                us[i] = __builtin_fma(p.hdt, k[i], u[i]);
-            }
-            window(us, N, w, q);
-            rhs_fast(p, w, q, phi, N, k);
-            for (int i = 0; i < N; ++i) {
-                acc[i] = __builtin_fma(p.dt3, k[i], acc[i]);
-                us[i] = __builtin_fma(dt, k[i], u[i]);
-            }
-            window(us, N, w, q);
-            rhs_fast(p, w, q, phi, N, k);
-            for (int i = 0; i < N; ++i) u[i] = __builtin_fma(p.dt6, k[i], acc[i]);
         }
+        stage(std::integral_constant<int, 1>{});
+        stage(std::integral_constant<int, 2>{});
+        stage(std::integral_constant<int, 3>{});
+        stage(std::integral_constant<int, 4>{});
     }
-    if constexpr (DISS && !EXACT) racc = __builtin_fma(rxx, p.r_dx4, __builtin_fma(rx, p.r_dx2, racc));
+    if constexpr (DISS && !EXACT) racc = __builtin_fma(rxx, c.r_dx4, __builtin_fma(rx, c.r_dx2, racc));
     *ssq_out = racc;
 }
 
-void run_rows(const Params& p, int mode, int objective, double* u, const float* phi, const float* actions, const float* F,
+void run_rows(int N, const Consts& c, int mode, int objective, double* u, const float* phi, const float* actions, const float* F,
               int n_act, const int* env_ids, int lo, int hi, long n_substeps, float* obs, double* ssq_sum, int* status) {
-    const int N = p.N;
     Scratch s(N);
     for (int r = lo; r < hi; ++r) {
         const int env = env_ids ? env_ids[r] : r;
@@ -220,14 +142,9 @@ void run_rows(const Params& p, int mode, int objective, double* u, const float* 
         double ssq = 0.0;
         // without a reward buffer the objective is irrelevant (the GPU runs its l2control kernels then, too)
         const bool diss = objective == 1 && ssq_sum;
-        if (mode == 1 && diss)
-            advance_env<true, true>(p, ue, s.phi.data(), n_substeps, s, &ssq);
-        else if (mode == 1)
-            advance_env<true, false>(p, ue, s.phi.data(), n_substeps, s, &ssq);
-        else if (diss)
-            advance_env<false, true>(p, ue, s.phi.data(), n_substeps, s, &ssq);
-        else
-            advance_env<false, false>(p, ue, s.phi.data(), n_substeps, s, &ssq);
+        ks::with_flags(mode == 1, diss, [&](auto exact, auto dissipation) {
+            advance_env<decltype(exact)::value, decltype(dissipation)::value>(N, c, ue, s.phi.data(), n_substeps, s, &ssq);
+        });
         int bad = 0;
         for (int i = 0; i < N; ++i) bad |= !std::isfinite(ue[i]);
         if (obs)
@@ -250,14 +167,14 @@ int default_threads() {
     return n;
 }
 
-void step(const Params& p, int mode, int objective, double* u, const float* phi, const float* actions, const float* F,
+void step(int N, const Consts& c, int mode, int objective, double* u, const float* phi, const float* actions, const float* F,
           int n_act, const int* env_ids, int n_rows, long n_substeps, float* obs, double* ssq_sum, int* status, int n_threads) {
     if (n_rows <= 0) return;
     // a thread is worth starting for >= ~1e6 point-sub-steps of its own
-    const double work = (double)n_rows * (double)p.N * (double)std::max<long>(n_substeps, 1);
+    const double work = (double)n_rows * (double)N * (double)std::max<long>(n_substeps, 1);
     int T = std::max(1, std::min({n_threads, n_rows, (int)(work / 1e6) + 1}));
     if (T == 1) {
-        run_rows(p, mode, objective, u, phi, actions, F, n_act, env_ids, 0, n_rows, n_substeps, obs, ssq_sum, status);
+        run_rows(N, c, mode, objective, u, phi, actions, F, n_act, env_ids, 0, n_rows, n_substeps, obs, ssq_sum, status);
         return;
     }
     std::vector<std::thread> pool;
@@ -267,38 +184,28 @@ void step(const Params& p, int mode, int objective, double* u, const float* phi,
     for (int t = 0; t < T; ++t) {
         const int hi = lo + per + (t < extra ? 1 : 0);
         if (t + 1 < T)
-            pool.emplace_back(run_rows, std::cref(p), mode, objective, u, phi, actions, F, n_act, env_ids, lo, hi,
+            pool.emplace_back(run_rows, N, std::cref(c), mode, objective, u, phi, actions, F, n_act, env_ids, lo, hi,
                               n_substeps, obs, ssq_sum, status);
         else
-            run_rows(p, mode, objective, u, phi, actions, F, n_act, env_ids, lo, hi, n_substeps, obs, ssq_sum, status);
+            run_rows(N, c, mode, objective, u, phi, actions, F, n_act, env_ids, lo, hi, n_substeps, obs, ssq_sum, status);
         lo = hi;
     }
     for (auto& th : pool) th.join();
 }
 
-void rhs(int N, double dx, double dx2, double dx4, const double* u, const float* phi, int n_rows, double* out, double* ux,
-         double* uxx, double* uxxxx) {
-    Params p{};
-    p.N = N;
-    p.dx = dx;
-    p.dx2 = dx2;
-    p.dx4 = dx4;
+void rhs(int N, const Consts& c, const double* u, const float* phi, int n_rows, double* out, double* ux, double* uxx,
+         double* uxxxx) {
     Scratch s(N);
     for (int r = 0; r < n_rows; ++r) {
         const size_t off = (size_t)r * N;
         for (int i = 0; i < N; ++i) s.phi[i] = (double)phi[off + i];
         window(u + off, N, s.w.data(), s.q.data());
-        rhs_exact(p, s.w.data(), s.q.data(), s.phi.data(), N, out + off, ux ? ux + off : nullptr,
+        rhs_exact(c, s.w.data(), s.q.data(), s.phi.data(), N, out + off, ux ? ux + off : nullptr,
                   uxx ? uxx + off : nullptr, uxxxx ? uxxxx + off : nullptr);
     }
 }
 
-void reward_rows(int N, double dx, int objective, const float* obs, const float* phi, int n_rows, double* out) {
-    Params p{};
-    p.N = N;
-    p.dx = dx;
-    p.dx2 = dx * dx;
-    p.dx4 = std::pow(dx, 4.0);
+void reward_rows(int N, const Consts& c, int objective, const float* obs, const float* phi, int n_rows, double* out) {
     Scratch s(N);
     std::vector<double> uu(N), rhs(N), zero(N, 0.0);
     for (int r = 0; r < n_rows; ++r) {
@@ -307,7 +214,7 @@ void reward_rows(int N, double dx, int objective, const float* obs, const float*
         double sxx = 0.0, sx = 0.0, sup = 0.0;
         if (objective == 1) {
             window(uu.data(), N, s.w.data(), s.q.data());
-            rhs_exact(p, s.w.data(), s.q.data(), zero.data(), N, rhs.data(), s.t1.data(), s.t2.data(), nullptr);
+            rhs_exact(c, s.w.data(), s.q.data(), zero.data(), N, rhs.data(), s.t1.data(), s.t2.data(), nullptr);
             for (int i = 0; i < N; ++i) {
                 sxx += s.t2[i] * s.t2[i];
                 sx += s.t1[i] * s.t1[i];

@@ -154,89 +154,8 @@ struct Halo<64, HALO_HYBRID1> : Halo<64, HALO_HYBRID> {
     }
 };
 
-// x / d for a divisor d that is constant over the launch, bit-identical to the IEEE division the reference performs:
-//   q = RN(x * r),  e = x - d * q (exact in one FMA),  result = RN(q + e * r),   r = RN(1 / d) from the host
-// (Markstein's correction step: with a correctly rounded reciprocal one step from the faithful q lands on the correctly
-// rounded quotient).  3 VALU instructions instead of the ~11 of the generic fp64 division sequence (v_div_scale x 2, v_rcp,
-// 5 FMA, v_div_fmas, v_div_fixup) -- the exact mode spends 17 divisions per point and sub-step, 47 % of its instructions.
-// Checked bit for bit against x / d on 7e9 dividends incl. ones placed next to rounding boundaries
-// (tools/micro/markstein_check.c) and, end to end, by the golden tests (200 000-sub-step reset, bit-identical state).
-// Not covered: x = -0.0 (gives +0.0; unreachable -- every dividend here is a sum whose coefficients have both signs, so a
-// vanishing sum is +0.0) and non-finite x (the env raises FloatingPointError on those anyway).
-__device__ __forceinline__ double div_const(double x, double d, double r) {
-    const double q = x * r;
-    const double e = __builtin_fma(-d, q, x);
-    return __builtin_fma(e, r, q);
-}
-
-// ------------------------------------------------------------------------------------------
-// rhs at one grid point.  w[] is the lane's window of u (4 halo + P + 4 halo), q[] = w[]^2,
-// c the index of the point inside the window.
-// ------------------------------------------------------------------------------------------
-//
-// t1 / t2 (dissipation objective, may be null): EXACT -> the reference's u_x (upwind derivative of u^2) and u_xx;
-// FAST -> the same two terms unscaled: the selected upwind sum (= u_x * dx up to sign) and the 7-point u_xx stencil
-// (= u_xx * dx^2), scaled once per launch by the caller.
-template <bool EXACT>
-__device__ __forceinline__ double rhs_point(const double* w, const double* q, int c, double phi,
-                                            const StepArgs& a, double* t1 = nullptr, double* t2 = nullptr) {
-    if constexpr (EXACT) {
-        // scipy correlate1d summation order (ni_filters.c): see oracle/ks_oracle.c
-        double fwd = q[c + 4] * (-1.0 / 4);
-        fwd += q[c] * (-25.0 / 12);
-        fwd += q[c + 1] * 4.0;
-        fwd += q[c + 2] * (-3.0);
-        fwd += q[c + 3] * (4.0 / 3);
-        double bwd = q[c - 4] * (1.0 / 4);
-        bwd += q[c - 3] * (-4.0 / 3);
-        bwd += q[c - 2] * 3.0;
-        bwd += q[c - 1] * (-4.0);
-        bwd += q[c] * (25.0 / 12);
-        const double f = div_const(fwd, a.dx, a.r_dx), b = div_const(bwd, a.dx, a.r_dx);
-        const double u = w[c];
-        const double d1 = (u < 0.0 ? 1.0 : 0.0) * f + (u >= 0.0 ? 1.0 : 0.0) * b;
-        double d2 = u * (-49.0 / 18);
-        d2 += (w[c - 3] + w[c + 3]) * (1.0 / 90);
-        d2 += (w[c - 2] + w[c + 2]) * (-3.0 / 20);
-        d2 += (w[c - 1] + w[c + 1]) * (3.0 / 2);
-        d2 = div_const(d2, a.dx2, a.r_dx2);
-        double d4 = u * (91.0 / 8);
-        d4 += (w[c - 4] + w[c + 4]) * (7.0 / 240);
-        d4 += (w[c - 3] + w[c + 3]) * (-2.0 / 5);
-        d4 += (w[c - 2] + w[c + 2]) * (169.0 / 60);
-        d4 += (w[c - 1] + w[c + 1]) * (-122.0 / 15);
-        d4 = div_const(d4, a.dx4, a.r_dx4);
-        if (t1) *t1 = d1;
-        if (t2) *t2 = d2;
-        return ((-d4 - d2) - 0.5 * d1) + phi;
-    } else {
-        double lin = __builtin_fma(a.c_lin[0], w[c], phi);
-        lin = __builtin_fma(a.c_lin[1], w[c - 1] + w[c + 1], lin);
-        lin = __builtin_fma(a.c_lin[2], w[c - 2] + w[c + 2], lin);
-        lin = __builtin_fma(a.c_lin[3], w[c - 3] + w[c + 3], lin);
-        lin = __builtin_fma(a.c_lin[4], w[c - 4] + w[c + 4], lin);
-        // backward upwind table b = (25/12, -4, 3, -4/3, 1/4); forward table is its negation
-        const double t0 = (25.0 / 12) * q[c];
-        double bw = __builtin_fma(-4.0, q[c - 1], t0);
-        bw = __builtin_fma(3.0, q[c - 2], bw);
-        bw = __builtin_fma(-4.0 / 3, q[c - 3], bw);
-        bw = __builtin_fma(0.25, q[c - 4], bw);
-        double fw = __builtin_fma(-4.0, q[c + 1], t0);
-        fw = __builtin_fma(3.0, q[c + 2], fw);
-        fw = __builtin_fma(-4.0 / 3, q[c + 3], fw);
-        fw = __builtin_fma(0.25, q[c + 4], fw);
-        const double sel = (w[c] < 0.0) ? -fw : bw;  // u == 0 selects the backward stencil
-        if (t1) *t1 = sel;
-        if (t2) {
-            double lap = (-49.0 / 18) * w[c];
-            lap = __builtin_fma(3.0 / 2, w[c - 1] + w[c + 1], lap);
-            lap = __builtin_fma(-3.0 / 20, w[c - 2] + w[c + 2], lap);
-            *t2 = __builtin_fma(1.0 / 90, w[c - 3] + w[c + 3], lap);
-        }
-        return __builtin_fma(a.mh_inv_dx, sel, lin);
-    }
-}
-
+// div_const, the reference-order point function ref_point, the fast per-point form fast_point and the RK4 stage
+// updates rk4_update live in ks_internal.h: the CPU twin is built from the same text.
 
 // ------------------------------------------------------------------------------------------
 // upwind select of the fast-mode tiles without v_cndmask:  sel = (u < 0) ? fw : bw
@@ -288,7 +207,7 @@ __device__ __forceinline__ double rhs_point(const double* w, const double* q, in
 // caller scales once per launch).
 template <int TJ, bool DISS = false>
 __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, int c0, const double* phi,
-                                              const StepArgs& a, unsigned long long ex0, double* k, double* r = nullptr) {
+                                              const Consts& a, unsigned long long ex0, double* k, double* r = nullptr) {
     double lin[TJ], s1[TJ], s2[TJ], s3[TJ], s4[TJ], bw[TJ], fw[TJ];
     [[maybe_unused]] double lap[TJ];
 #ifndef KS_UPWIND_CNDMASK
@@ -387,7 +306,7 @@ __device__ __forceinline__ void rhs_tile_fast(const double* w, const double* q, 
 // distances <= 2 computed while they travel.  Same operations in the same per-accumulator order as rhs_tile_fast, so
 // the result is bit-identical to the other fast-mode layouts.
 template <int FAR>   // FAR = 2: distances 3 and 4 by ds_bpermute; FAR = 1: distance 4 only
-__device__ __forceinline__ double rhs_hybrid_fast(const Halo<64, HALO_HYBRID>& h, double u, double phi, const StepArgs& a,
+__device__ __forceinline__ double rhs_hybrid_fast(const Halo<64, HALO_HYBRID>& h, double u, double phi, const Consts& a,
                                                   double& q0) {
     double l3, r3;
     if constexpr (FAR == 2) {
@@ -436,10 +355,10 @@ __host__ __device__ constexpr int tile_of() { return P % 4 == 0 ? 4 : (P % 3 == 
 
 template <int P, bool EXACT>
 __device__ __forceinline__ void eval_rhs(const double* w, const double* q, const double (&phi)[P],
-                                         const StepArgs& a, unsigned long long ex0, double (&kk)[P]) {
+                                         const Consts& a, unsigned long long ex0, double (&kk)[P]) {
     if constexpr (EXACT) {
 #pragma unroll
-        for (int j = 0; j < P; ++j) kk[j] = rhs_point<true>(w, q, 4 + j, phi[j], a);
+        for (int j = 0; j < P; ++j) kk[j] = ref_point<DivMarkstein>(w, q, 4 + j, phi[j], a).rhs;
     } else {
         constexpr int TJ = tile_of<P>();
 #pragma unroll
@@ -448,18 +367,18 @@ __device__ __forceinline__ void eval_rhs(const double* w, const double* q, const
 }
 
 // Stage 1 under the dissipation objective: the rhs plus the reward terms of the pre-update state.
-//   EXACT: r[0] += (u_xx^2 + u_x^2) + u*phi per point, u_x / u_xx exactly as rhs_point forms them
+//   EXACT: r[0] += (u_xx^2 + u_x^2) + u*phi per point, u_x / u_xx exactly as ref_point forms them
 //   FAST : r[0] += u*phi, r[1] += sel^2, r[2] += lap^2 (unscaled, see rhs_tile_fast)
 template <int P, bool EXACT>
 __device__ __forceinline__ void eval_rhs_dissipation(const double* w, const double* q, const double (&phi)[P],
-                                                     const StepArgs& a, unsigned long long ex0, double (&kk)[P],
+                                                     const Consts& a, unsigned long long ex0, double (&kk)[P],
                                                      double (&r)[3]) {
     if constexpr (EXACT) {
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-            double ux, uxx;
-            kk[j] = rhs_point<true>(w, q, 4 + j, phi[j], a, &ux, &uxx);
-            r[0] += (uxx * uxx + ux * ux) + w[4 + j] * phi[j];
+            const RefPoint p = ref_point<DivMarkstein>(w, q, 4 + j, phi[j], a);
+            kk[j] = p.rhs;
+            r[0] += (p.d2 * p.d2 + p.d1 * p.d1) + w[4 + j] * phi[j];
         }
     } else {
         constexpr int TJ = tile_of<P>();
@@ -471,7 +390,7 @@ __device__ __forceinline__ void eval_rhs_dissipation(const double* w, const doub
 // Per-lane reward accumulator -> the launch's per-env sum of the objective's per-sub-step terms (before the cross-lane
 // reduction).  FAST dissipation scales its two derivative sums here, once.
 template <bool EXACT, bool DISS>
-__device__ __forceinline__ double reward_partial(const double (&r)[3], const StepArgs& a) {
+__device__ __forceinline__ double reward_partial(const double (&r)[3], const Consts& a) {
     if constexpr (DISS && !EXACT) return __builtin_fma(r[2], a.r_dx4, __builtin_fma(r[1], a.r_dx2, r[0]));
     return r[0];
 }
@@ -523,6 +442,22 @@ __device__ __forceinline__ void build_window(const Halo<G, HALO>& halo, const do
             if ((m + P - 1) / P == d) w[4 - m] = lc[d * P - m];
             if ((P - 1 + m) / P == d) w[P + 3 + m] = rc[(P - 1 + m) % P];
         }
+    }
+}
+
+// The rhs of RK stages 2 to 4 at the stage state us: the window, its squares and the layout's rhs form.
+template <int P, int G, int HALO, bool EXACT>
+__device__ __forceinline__ void stage_rhs(const Halo<G, HALO>& halo, const double (&us)[P], const double (&phi)[P],
+                                          const Consts& a, unsigned long long ex0, double (&kk)[P]) {
+    if constexpr ((HALO == HALO_HYBRID || HALO == HALO_HYBRID1) && !EXACT) {
+        double q0;
+        kk[0] = rhs_hybrid_fast<(HALO == HALO_HYBRID ? 2 : 1)>(halo, us[0], phi[0], a, q0);
+    } else {
+        double w[P + 8], q[P + 8];
+        build_window<P, G, HALO, EXACT>(halo, us, w);
+#pragma unroll
+        for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
+        eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
     }
 }
 
@@ -578,124 +513,73 @@ __global__ void __launch_bounds__(256) ks_rk4_fused(const StepArgs a) {
     }
 
     // The step constants of the stage updates (fetched by scalar loads that the compiler issues right in front of the loop).
-    [[maybe_unused]] double hdt = a.hdt, dt6 = a.dt6, dt3 = a.dt3, dt = a.dt;
+    // c exists for the four scalars pinned below, and only rk4_update and the stage-4 FMA read it.  The rhs functions and
+    // reward_partial read a.k, the kernel argument itself, on purpose: nothing of theirs is pinned, and this is the form
+    // whose loops were compared with the ones before (profiles/ks_refactor_isa.txt).  Do not merge the two names.
+    [[maybe_unused]] Consts c = a.k;
     if constexpr (SLOTS) {
         // The prologue's loads are waited for HERE, once: the empty statements need u, phi and the step constants in
         // their registers, so the s_waitcnt vmcnt / lgkmcnt land in front of the loop and not, re-issued every sub-step,
         // inside it (3 + 1 at P = 16).
 #pragma unroll
         for (int j = 0; j < P; ++j) asm volatile("" : "+v"(u[j]), "+v"(phi[j]));
-        asm volatile("" : "+s"(hdt), "+s"(dt6), "+s"(dt3), "+s"(dt));
+        asm volatile("" : "+s"(c.hdt), "+s"(c.dt6), "+s"(c.dt3), "+s"(c.dt));
     }
 
     double racc = 0.0;
     [[maybe_unused]] double rd[3] = {0.0, 0.0, 0.0};   // dissipation partial sums (see eval_rhs_dissipation)
     for (long s = 0; s < a.n_substeps; ++s) {
-        double acc[P], us[P], usn[P], w[P + 8], q[P + 8], kk[P];
+        double acc[P], us[P], usn[P], kk[P];
         // ---- stage 1 (k1 at u) + reward term of this sub-step ----
         if constexpr ((HALO == HALO_HYBRID || HALO == HALO_HYBRID1) && !EXACT) {
             double q0;
-            kk[0] = rhs_hybrid_fast<(HALO == HALO_HYBRID ? 2 : 1)>(halo, u[0], phi[0], a, q0);
+            kk[0] = rhs_hybrid_fast<(HALO == HALO_HYBRID ? 2 : 1)>(halo, u[0], phi[0], a.k, q0);
             racc += q0;
         } else {
+            double w[P + 8], q[P + 8];
             build_window<P, G, HALO, EXACT>(halo, u, w);
 #pragma unroll
             for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
             if constexpr (DISS) {
-                eval_rhs_dissipation<P, EXACT>(w, q, phi, a, ex0, kk, rd);
+                eval_rhs_dissipation<P, EXACT>(w, q, phi, a.k, ex0, kk, rd);
             } else {
 #pragma unroll
                 for (int j = 0; j < P; ++j) racc += q[4 + j];
-                eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
+                eval_rhs<P, EXACT>(w, q, phi, a.k, ex0, kk);
             }
         }
 #pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const double k = kk[j];
-            if constexpr (EXACT) {
-                acc[j] = k;
-                usn[j] = u[j] + a.dt * k / 2.0;
-            } else {
-                acc[j] = __builtin_fma(dt6, k, u[j]);
-                usn[j] = __builtin_fma(hdt, k, u[j]);
-            }
-        }
-        // ---- stage 2 ----
+        for (int j = 0; j < P; ++j) rk4_update<EXACT, 1>(kk[j], u[j], acc[j], usn[j], c);
+        // ---- stage 2 ----  (us is a copy of usn and not usn itself: DESIGN 4.1, the hybrid1 loop)
 #pragma unroll
         for (int j = 0; j < P; ++j) us[j] = usn[j];
-        if constexpr ((HALO == HALO_HYBRID || HALO == HALO_HYBRID1) && !EXACT) {
-            double q0;
-            kk[0] = rhs_hybrid_fast<(HALO == HALO_HYBRID ? 2 : 1)>(halo, us[0], phi[0], a, q0);
-        } else {
-            build_window<P, G, HALO, EXACT>(halo, us, w);
+        stage_rhs<P, G, HALO, EXACT>(halo, us, phi, a.k, ex0, kk);
 #pragma unroll
-            for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
-            eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
-        }
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const double k = kk[j];
-            if constexpr (EXACT) {
-                acc[j] = acc[j] + 2.0 * k;
-                usn[j] = u[j] + a.dt * k / 2.0;
-            } else {
-                acc[j] = __builtin_fma(dt3, k, acc[j]);
-                usn[j] = __builtin_fma(hdt, k, u[j]);
-            }
-        }
+        for (int j = 0; j < P; ++j) rk4_update<EXACT, 2>(kk[j], u[j], acc[j], usn[j], c);
         // ---- stage 3 ----
 #pragma unroll
         for (int j = 0; j < P; ++j) us[j] = usn[j];
-        if constexpr ((HALO == HALO_HYBRID || HALO == HALO_HYBRID1) && !EXACT) {
-            double q0;
-            kk[0] = rhs_hybrid_fast<(HALO == HALO_HYBRID ? 2 : 1)>(halo, us[0], phi[0], a, q0);
-        } else {
-            build_window<P, G, HALO, EXACT>(halo, us, w);
+        stage_rhs<P, G, HALO, EXACT>(halo, us, phi, a.k, ex0, kk);
 #pragma unroll
-            for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
-            eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
-        }
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const double k = kk[j];
-            if constexpr (EXACT) {
-                acc[j] = acc[j] + 2.0 * k;
-                usn[j] = u[j] + a.dt * k;
-            } else {
-                acc[j] = __builtin_fma(dt3, k, acc[j]);
-                usn[j] = __builtin_fma(dt, k, u[j]);
-            }
-        }
+        for (int j = 0; j < P; ++j) rk4_update<EXACT, 3>(kk[j], u[j], acc[j], usn[j], c);
         // ---- stage 4 + update ----
 #pragma unroll
         for (int j = 0; j < P; ++j) us[j] = usn[j];
-        if constexpr ((HALO == HALO_HYBRID || HALO == HALO_HYBRID1) && !EXACT) {
-            double q0;
-            kk[0] = rhs_hybrid_fast<(HALO == HALO_HYBRID ? 2 : 1)>(halo, us[0], phi[0], a, q0);
-        } else {
-            build_window<P, G, HALO, EXACT>(halo, us, w);
-#pragma unroll
-            for (int i = 0; i < P + 8; ++i) q[i] = w[i] * w[i];
-            eval_rhs<P, EXACT>(w, q, phi, a, ex0, kk);
-        }
+        stage_rhs<P, G, HALO, EXACT>(halo, us, phi, a.k, ex0, kk);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-            const double k = kk[j];
-            if constexpr (EXACT) {
-                acc[j] = acc[j] + k;
-                u[j] = u[j] + div_const(a.dt * acc[j], 6.0, 1.0 / 6.0);
-            } else if constexpr (SLOTS) {
-                // The same FMA, u = fma(dt6, k, acc), in its three-address form: the compiler ties a v_fmac to acc's
-                // registers and copies the result to u's (one v_mov_b64 per point and sub-step); this lands in u's.
-                asm("v_fma_f64 %0, %1, %2, %3" : "=v"(u[j]) : "s"(dt6), "v"(k), "v"(acc[j]));
+            if constexpr (SLOTS) {
+                // rk4_update<false, 4>'s FMA, u = fma(dt6, k, acc), in its three-address form: the compiler ties a v_fmac to
+                // acc's registers and copies the result to u's (one v_mov_b64 per point and sub-step); this lands in u's.
+                asm("v_fma_f64 %0, %1, %2, %3" : "=v"(u[j]) : "s"(c.dt6), "v"(kk[j]), "v"(acc[j]));
             } else {
-                u[j] = __builtin_fma(dt6, k, acc[j]);
+                rk4_update<EXACT, 4>(kk[j], u[j], acc[j], u[j], c);
             }
         }
     }
 
     // ---- epilogue: state, fp32 observation, reward sum, non-finite flag ----
-    if constexpr (DISS) racc = reward_partial<EXACT, DISS>(rd, a);
+    if constexpr (DISS) racc = reward_partial<EXACT, DISS>(rd, a.k);
     int bad = 0;
 #pragma unroll
     for (int j = 0; j < P; ++j) bad |= !__builtin_isfinite(u[j]);
@@ -773,30 +657,32 @@ __global__ void __launch_bounds__(256) ks_rk4_lds(const StepArgs a) {
                 if constexpr (!DISS) {
                     if (stage == 0) racc += q[4];
                 }
-                double t1 = 0.0, t2 = 0.0;   // (formed at every stage under DISS: a runtime choice of pointer spills)
-                const double k = rhs_point<EXACT>(w, q, 4, PHI[i], a, DISS ? &t1 : nullptr, DISS ? &t2 : nullptr);
-                if constexpr (DISS) {
-                    if (stage == 0) {
-                        if constexpr (EXACT) {
-                            rd[0] += (t2 * t2 + t1 * t1) + w[4] * PHI[i];
-                        } else {
+                // (the reward terms are formed at every stage under DISS and chosen by the compile-time flag: handing
+                // them out through a pointer chosen at run time spills)
+                double k;
+                if constexpr (EXACT) {
+                    const RefPoint p = ref_point<DivMarkstein>(w, q, 4, PHI[i], a.k);
+                    k = p.rhs;
+                    if constexpr (DISS) {
+                        if (stage == 0) rd[0] += (p.d2 * p.d2 + p.d1 * p.d1) + w[4] * PHI[i];
+                    }
+                } else {
+                    const FastPoint p = fast_point<DISS>(w, q, 4, PHI[i], a.k);
+                    k = p.k;
+                    if constexpr (DISS) {
+                        if (stage == 0) {
                             rd[0] = __builtin_fma(w[4], PHI[i], rd[0]);
-                            rd[1] = __builtin_fma(t1, t1, rd[1]);
-                            rd[2] = __builtin_fma(t2, t2, rd[2]);
+                            rd[1] = __builtin_fma(p.sel, p.sel, rd[1]);
+                            rd[2] = __builtin_fma(p.lap, p.lap, rd[2]);
                         }
                     }
                 }
                 const double u0 = U[i];
-                if constexpr (EXACT) {
-                    if (stage == 0) { ACC[i] = k; dst[i] = u0 + a.dt * k / 2.0; }
-                    else if (stage == 1) { ACC[i] = ACC[i] + 2.0 * k; dst[i] = u0 + a.dt * k / 2.0; }
-                    else if (stage == 2) { ACC[i] = ACC[i] + 2.0 * k; dst[i] = u0 + a.dt * k; }
-                    else { const double s4 = ACC[i] + k; dst[i] = u0 + div_const(a.dt * s4, 6.0, 1.0 / 6.0); }
-                } else {
-                    if (stage == 0) { ACC[i] = __builtin_fma(a.dt6, k, u0); dst[i] = __builtin_fma(a.hdt, k, u0); }
-                    else if (stage == 1) { ACC[i] = __builtin_fma(a.dt3, k, ACC[i]); dst[i] = __builtin_fma(a.hdt, k, u0); }
-                    else if (stage == 2) { ACC[i] = __builtin_fma(a.dt3, k, ACC[i]); dst[i] = __builtin_fma(a.dt, k, u0); }
-                    else { dst[i] = __builtin_fma(a.dt6, k, ACC[i]); }
+                switch (stage) {
+                    case 0: rk4_update<EXACT, 1>(k, u0, ACC[i], dst[i], a.k); break;
+                    case 1: rk4_update<EXACT, 2>(k, u0, ACC[i], dst[i], a.k); break;
+                    case 2: rk4_update<EXACT, 3>(k, u0, ACC[i], dst[i], a.k); break;
+                    default: rk4_update<EXACT, 4>(k, u0, ACC[i], dst[i], a.k); break;
                 }
             }
             __syncthreads();
@@ -815,7 +701,7 @@ __global__ void __launch_bounds__(256) ks_rk4_lds(const StepArgs a) {
         a.u[off + i] = v;
         if (a.obs) a.obs[off + i] = (float)v;
     }
-    if constexpr (DISS) racc = reward_partial<EXACT, DISS>(rd, a);
+    if constexpr (DISS) racc = reward_partial<EXACT, DISS>(rd, a.k);
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) racc += __shfl_xor(racc, m, 64);
     if ((tid & 63) == 0) red[tid >> 6] = racc;
@@ -848,34 +734,15 @@ __global__ void ks_rhs_kernel(const double* __restrict__ u, const float* __restr
         w[k + 4] = ur[idx];
         q[k + 4] = w[k + 4] * w[k + 4];
     }
-    const int c = 4;
-    double fwd = q[c + 4] * (-1.0 / 4);
-    fwd += q[c] * (-25.0 / 12);
-    fwd += q[c + 1] * 4.0;
-    fwd += q[c + 2] * (-3.0);
-    fwd += q[c + 3] * (4.0 / 3);
-    double bwd = q[c - 4] * (1.0 / 4);
-    bwd += q[c - 3] * (-4.0 / 3);
-    bwd += q[c - 2] * 3.0;
-    bwd += q[c - 1] * (-4.0);
-    bwd += q[c] * (25.0 / 12);
-    const double f = fwd / dx, b = bwd / dx, uc = w[c];
-    const double d1 = (uc < 0.0 ? 1.0 : 0.0) * f + (uc >= 0.0 ? 1.0 : 0.0) * b;
-    double d2 = uc * (-49.0 / 18);
-    d2 += (w[c - 3] + w[c + 3]) * (1.0 / 90);
-    d2 += (w[c - 2] + w[c + 2]) * (-3.0 / 20);
-    d2 += (w[c - 1] + w[c + 1]) * (3.0 / 2);
-    d2 = d2 / dx2;
-    double d4 = uc * (91.0 / 8);
-    d4 += (w[c - 4] + w[c + 4]) * (7.0 / 240);
-    d4 += (w[c - 3] + w[c + 3]) * (-2.0 / 5);
-    d4 += (w[c - 2] + w[c + 2]) * (169.0 / 60);
-    d4 += (w[c - 1] + w[c + 1]) * (-122.0 / 15);
-    d4 = d4 / dx4;
-    rhs[gid] = ((-d4 - d2) - 0.5 * d1) + (double)phi[gid];
-    if (ux) ux[gid] = d1;
-    if (uxx) uxx[gid] = d2;
-    if (uxxxx) uxxxx[gid] = d4;
+    Consts a{};   // DivIeee reads the three divisors and never a reciprocal: all four outputs of ref_point are valid
+    a.dx = dx;
+    a.dx2 = dx2;
+    a.dx4 = dx4;
+    const RefPoint p = ref_point<DivIeee>(w, q, 4, (double)phi[gid], a);
+    rhs[gid] = p.rhs;
+    if (ux) ux[gid] = p.d1;
+    if (uxx) uxx[gid] = p.d2;
+    if (uxxxx) uxxxx[gid] = p.d4;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -905,26 +772,10 @@ __global__ void __launch_bounds__(256) ks_reward_rows_kernel(const float* __rest
         }
         const int c = 4;
         if constexpr (DISS) {
-            double fwd = q[c + 4] * (-1.0 / 4);
-            fwd += q[c] * (-25.0 / 12);
-            fwd += q[c + 1] * 4.0;
-            fwd += q[c + 2] * (-3.0);
-            fwd += q[c + 3] * (4.0 / 3);
-            double bwd = q[c - 4] * (1.0 / 4);
-            bwd += q[c - 3] * (-4.0 / 3);
-            bwd += q[c - 2] * 3.0;
-            bwd += q[c - 1] * (-4.0);
-            bwd += q[c] * (25.0 / 12);
-            const double f = div_const(fwd, dx, r_dx), b = div_const(bwd, dx, r_dx), u = w[c];
-            const double d1 = (u < 0.0 ? 1.0 : 0.0) * f + (u >= 0.0 ? 1.0 : 0.0) * b;
-            double d2 = u * (-49.0 / 18);
-            d2 += (w[c - 3] + w[c + 3]) * (1.0 / 90);
-            d2 += (w[c - 2] + w[c + 2]) * (-3.0 / 20);
-            d2 += (w[c - 1] + w[c + 1]) * (3.0 / 2);
-            d2 = div_const(d2, dx2, r_dx2);
-            sxx += d2 * d2;
-            sx += d1 * d1;
-            if (pr) sup += u * (double)pr[i];
+            const RefTerms p = ref_terms<DivMarkstein>(w, q, c, dx, r_dx, dx2, r_dx2);
+            sxx += p.d2 * p.d2;
+            sx += p.d1 * p.d1;
+            if (pr) sup += w[c] * (double)pr[i];
         } else {
             sup += q[c];
         }
@@ -984,20 +835,15 @@ __global__ void ks_selftest_kernel(unsigned* out) {
 // ------------------------------------------------------------------------------------------
 template <int P, int G, int HALO>
 static hipError_t launch_fused(const Layout& lay, int mode, bool diss, const StepArgs& a, hipStream_t st) {
-    if constexpr (HALO == HALO_HYBRID || HALO == HALO_HYBRID1) {
-        if (diss) return hipErrorNotSupported;
-    } else if (diss) {
-        if (mode == KS_MODE_EXACT)
-            hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, true, true>), dim3(lay.grid), dim3(lay.block), 0, st, a);
-        else
-            hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, false, true>), dim3(lay.grid), dim3(lay.block), 0, st, a);
-        return hipGetLastError();
-    }
-    if (mode == KS_MODE_EXACT)
-        hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, true, false>), dim3(lay.grid), dim3(lay.block), 0, st, a);
-    else
-        hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, false, false>), dim3(lay.grid), dim3(lay.block), 0, st, a);
-    return hipGetLastError();
+    return with_flags(mode == KS_MODE_EXACT, diss, [&](auto exact, auto dissipation) {
+        constexpr bool EXACT = decltype(exact)::value, DISS = decltype(dissipation)::value;
+        if constexpr (DISS && (HALO == HALO_HYBRID || HALO == HALO_HYBRID1)) {
+            return hipErrorNotSupported;
+        } else {
+            hipLaunchKernelGGL((ks_rk4_fused<P, G, HALO, EXACT, DISS>), dim3(lay.grid), dim3(lay.block), 0, st, a);
+            return hipGetLastError();
+        }
+    });
 }
 
 #define KS_P_CASES(G_, HALO_)                                              \
@@ -1044,15 +890,11 @@ hipError_t launch_step(const Layout& lay, int mode, int objective, const StepArg
         case KS_VARIANT_WAVE64_HYBRID: return lay.P == 1 ? launch_fused<1, 64, HALO_HYBRID>(lay, mode, diss, a, st) : hipErrorInvalidValue;
         case KS_VARIANT_WAVE64_HYBRID1: return lay.P == 1 ? launch_fused<1, 64, HALO_HYBRID1>(lay, mode, diss, a, st) : hipErrorInvalidValue;
         case KS_VARIANT_LDS:
-            if (mode == KS_MODE_EXACT && !diss)
-                hipLaunchKernelGGL((ks_rk4_lds<true, false>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
-            else if (!diss)
-                hipLaunchKernelGGL((ks_rk4_lds<false, false>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
-            else if (mode == KS_MODE_EXACT)
-                hipLaunchKernelGGL((ks_rk4_lds<true, true>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
-            else
-                hipLaunchKernelGGL((ks_rk4_lds<false, true>), dim3(lay.grid), dim3(lay.block), lay.lds_bytes, st, a);
-            return hipGetLastError();
+            return with_flags(mode == KS_MODE_EXACT, diss, [&](auto exact, auto dissipation) {
+                hipLaunchKernelGGL((ks_rk4_lds<decltype(exact)::value, decltype(dissipation)::value>), dim3(lay.grid),
+                                   dim3(lay.block), lay.lds_bytes, st, a);
+                return hipGetLastError();
+            });
         default: return hipErrorInvalidValue;
     }
 }
@@ -1074,13 +916,12 @@ static hipError_t launch_reward_rows_g(bool diss, const float* obs, const float*
     const int block = 256, rows_per_block = block / G;
     const unsigned grid = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
     const double dx2 = dx * dx;   // python: self.dx**2
-    if (diss)
-        hipLaunchKernelGGL((ks_reward_rows_kernel<G, true>), dim3(grid), dim3(block), 0, st, obs, phi, n_rows, N, dx,
-                           1.0 / dx, dx2, 1.0 / dx2, out);
-    else
-        hipLaunchKernelGGL((ks_reward_rows_kernel<G, false>), dim3(grid), dim3(block), 0, st, obs, phi, n_rows, N, dx,
-                           1.0 / dx, dx2, 1.0 / dx2, out);
-    return hipGetLastError();
+    // (the reward is formed in the reference's order whatever the stepper's mode: the first flag is not read)
+    return with_flags(true, diss, [&](auto, auto dissipation) {
+        hipLaunchKernelGGL((ks_reward_rows_kernel<G, decltype(dissipation)::value>), dim3(grid), dim3(block), 0, st, obs,
+                           phi, n_rows, N, dx, 1.0 / dx, dx2, 1.0 / dx2, out);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_reward_rows(int objective, const float* obs, const float* phi, int n_rows, int N, double dx,

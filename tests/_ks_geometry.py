@@ -7,7 +7,10 @@ dissipation accumulator the oracle's rhs along the oracle's trajectory (_traject
 Tolerances are the project's contract (test_ks_gpu_parity.py, test_dissipation_gpu.py):
   exact mode  state and fp32 obs bit-equal, l2 accumulator rtol 1e-13, dissipation accumulator rtol 1e-12
   fast mode   state L_inf <= 1e-12 after one sub-step and <= 1e-11 after 20 (and after 5, the LDS range test); three
-              sub-steps get 3e-12, the per-sub-step bound added up; accumulators rtol 1e-10
+              sub-steps get 3e-12, the per-sub-step bound added up; accumulators rtol 1e-10; state and fp32 obs bit-equal
+              to the CPU twin's (device = -1): every fast-mode form runs the same IEEE fp64 operations per accumulator in
+              the same order (csrc/ks_internal.h fast_point, rhs_tile_fast, rhs_hybrid_fast), only the reward sums are
+              reduced in another order
   both        state and obs bit-identical under the two objectives, status all 0
 """
 import functools
@@ -122,6 +125,18 @@ ACC_RTOL = {("exact", "l2control"): 1e-13, ("exact", "dissipation"): 1e-12,
             ("fast", "l2control"): 1e-10, ("fast", "dissipation"): 1e-10}
 
 
+@functools.lru_cache(maxsize=None)
+def _twin(E, N, dt):
+    """The CPU twin (device = -1) at this geometry: what every layout's fast-mode state is bit-equal to."""
+    import kspde
+    return kspde.KSStepper(E, N, length_of(N), dt, device=-1, mode="fast")
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
 def _rel(got, ref):
     """max |got - ref| / |ref| (absolute where the reference is exactly 0)."""
     got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
@@ -151,6 +166,12 @@ def check_steps(s, u0, phi, ref, mode, objectives=("l2control", "dissipation"), 
                 err = float(np.abs(u - u_ref).max())
                 seen["state"] = max(seen["state"], err)
                 assert err <= FAST_STATE_TOL[n], (msg, err)
+                twin = _twin(len(u0), u0.shape[1], DT)
+                twin.set_objective(obj)
+                twin.set_state(u0)
+                obs_t, _, _ = twin.step(phi, n)
+                np.testing.assert_array_equal(_bits(u), _bits(twin.get_state()), err_msg=msg + " state bits vs the twin")
+                np.testing.assert_array_equal(_bits(obs), _bits(obs_t), err_msg=msg + " obs bits vs the twin")
             acc_ref = l2_ref if obj == "l2control" else diss_ref
             seen[obj] = max(seen.get(obj, 0.0), _rel(acc, acc_ref))
             np.testing.assert_allclose(acc, acc_ref, rtol=ACC_RTOL[mode, obj], atol=0, err_msg=msg)
@@ -225,6 +246,18 @@ def check_actions_path(s, N, E, label=""):
     np.testing.assert_array_equal(ua, s.get_state(), err_msg=label)
     np.testing.assert_array_equal(ssq_a, ssq_p, err_msg=label)
     np.testing.assert_array_equal(ua, ref, err_msg=label)
+    # fast mode: the in-kernel phi feeds the same operations as the twin's, state and fp32 obs bit for bit
+    twin = _twin(E, N, DT)
+    twin.set_objective("l2control")
+    twin.set_forcing(F)
+    twin.set_state(u0)
+    obs_t, _, _ = twin.step_actions(actions, ENTRY_SUBSTEPS)
+    s.set_mode("fast")
+    s.set_state(u0)
+    obs_f, _, st = s.step_actions(actions, ENTRY_SUBSTEPS)
+    assert not st.any(), label
+    np.testing.assert_array_equal(_bits(s.get_state()), _bits(twin.get_state()), err_msg=label + " fast state bits vs the twin")
+    np.testing.assert_array_equal(_bits(obs_f), _bits(obs_t), err_msg=label + " fast obs bits vs the twin")
 
 
 def check_step_rows(s, N, label=""):

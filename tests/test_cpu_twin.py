@@ -3,8 +3,10 @@ reference (pdegym/kuramoto/kuramoto.py:78-129) -- the same assertions the HIP pa
 BASELINE configs[0]: ``KuramotoSivashinskyEnv-v0``, L = 22, 64 grid points, one env, random-action rollout on a host
 without a GPU.
 
-The twin is product code (an independent implementation inside csrc/); the oracle (oracle/ks_oracle.c) is only the
-checker here.  ``make -C model-based-pde-control_amd/csrc asan`` builds the same sources with AddressSanitizer + UBSan;
+The twin is product code: the per-point arithmetic and the RK4 stage updates of csrc/ks_internal.h, the same source as
+the GPU kernels, built by a second compiler.  It is therefore no independent check of the kernels; the oracle
+(oracle/ks_oracle.c), which shares nothing with csrc/, alone is the independent checker, here as elsewhere.
+``make -C model-based-pde-control_amd/csrc asan`` builds the same sources with AddressSanitizer + UBSan;
 test_sanitizer_build_runs_this_file_clean runs this file against that build.
 """
 import os

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of two builds of libkspde.so on the C3 workload (4096 envs x 256 points, fast mode, 250 sub-steps per launch).
+"""A/B of two builds of libkspde.so on the C3 workload (4096 envs x 256 points, fast mode, 250 sub-steps per launch), or
+on another workload and mode of bench.py (--workload c2|c3, --mode fast|exact).
 
 --libs select (default)  lib/libkspde.so (masked FMA, KS_MASKED_SELECT in csrc/ks_kernels.hip) against
                          lib/libkspde_cndmask.so (the same sources with -DKS_UPWIND_CNDMASK: two v_cndmask per point);
@@ -14,7 +15,8 @@ limit and the driver stops at the first non-zero exit.  Writes the result file i
 --copy-to directory): every round's ms per launch, the median and the spread (max - min) per library, and the verdict:
 a gain only if the gap of the medians exceeds three times the larger spread.
 
-usage: tools/ks_select_ab.py [--libs select|loop|A.so B.so] [--out NAME.json] [--rounds 5] [--copy-to DIR ...]
+usage: tools/ks_select_ab.py [--libs select|loop|A.so B.so] [--out NAME.json] [--workload c3] [--mode fast] [--rounds 5]
+                             [--copy-to DIR ...]
 """
 import argparse
 import json
@@ -33,14 +35,14 @@ CHILD_TIMEOUT = 180
 ACTION_SETS = 64
 
 
-def child():
+def child(workload, mode):
     for p in (ROOT, PKG):
         sys.path.insert(0, p)
     import torch
     import bench
     import kspde
     dev = torch.device("cuda:0")
-    run = bench.KSRun(kspde, "c3", 0, dev, 0, ACTION_SETS, "fast")
+    run = bench.KSRun(kspde, workload, 0, dev, 0, ACTION_SETS, mode)
     step = run.one_step
     run.one_step = lambda i: step(i % ACTION_SETS)
     sync = run.stream.synchronize
@@ -59,9 +61,11 @@ def main():
     ap.add_argument("--libs", nargs="+", default=["select"], metavar="PAIR|LIB",
                     help="select, loop, or the paths of two libraries (candidate, baseline)")
     ap.add_argument("--out", default=None, metavar="NAME.json", help="file name under profiles/ (needed with two paths)")
+    ap.add_argument("--workload", choices=["c2", "c3"], default="c3")
+    ap.add_argument("--mode", choices=["fast", "exact"], default="fast")
     args = ap.parse_args()
     if args.child:
-        return child()
+        return child(args.workload, args.mode)
     if len(args.libs) == 1:
         LIBS, out_name = PAIRS[args.libs[0]]
         LIBS = tuple((n, os.path.join(PKG, "lib", f)) for n, f in LIBS)
@@ -77,7 +81,8 @@ def main():
     for r in range(args.rounds):
         for name, lib in LIBS:
             env = dict(os.environ, KSPDE_LIB=lib)
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, timeout=CHILD_TIMEOUT,
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--workload", args.workload, "--mode",
+                                args.mode], env=env, timeout=CHILD_TIMEOUT,
                                capture_output=True, text=True)
             if p.returncode != 0:
                 sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
@@ -90,7 +95,8 @@ def main():
     spread = {k: max(v) - min(v) for k, v in rounds.items()}
     gap = med[base] - med[cand]
     margin = 3.0 * max(spread.values())
-    out = {"workload": "c3: 4096 envs x 256 points, fast mode, 250 sub-steps per launch",
+    E, N = {"c2": (1024, 64), "c3": (4096, 256)}[args.workload]
+    out = {"workload": f"{args.workload}: {E} envs x {N} points, {args.mode} mode, 250 sub-steps per launch",
            "method": f"one fresh process per library and round, order A B A B; one HIP event pair around >= {SECONDS} s of "
                      f"back-to-back launches after as many warm-up launches (bench.py::KSRun.timed)",
            "libraries": dict((k, os.path.relpath(v, ROOT)) for k, v in LIBS),
