@@ -16,8 +16,8 @@
 //   backward  the same walk in reverse: gelu', the pointwise weight gradients as K = N MFMA contractions of the gradient
 //             buffer with the recomputed layer input, dx = iDFT(conj(W) . DFT(d_pre)) + Wp^T d_pre in place; the spectral
 //             weight gradient is a contraction over (step, sample) pairs of two saved spectra, done once per rollout by
-//             the caller; every other parameter gradient leaves as one row per pair (deterministic, no atomics across
-//             workgroups), summed by fno_reduce_rows.
+//             the caller; every other parameter gradient leaves as one row per pair (deterministic: no atomics, within a
+//             workgroup or across them; bit-identical run to run, tests/test_fno_kernels_gpu.py), summed by fno_reduce_rows.
 //
 // Geometry: width 32, 16 modes, N a power of two in [64, 512] (LDS: two [32][N + 4] buffers + spectra = 156 KB at N = 512).
 // fp32 throughout, v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains).
@@ -451,11 +451,14 @@ __global__ void __launch_bounds__(TPB) fno_backward_kernel(const BwdArgs a) {
     if (threadIdx.x < C) {
         L.misc[threadIdx.x] = a.w.p1_b[threadIdx.x];
         L.misc[C + threadIdx.x] = a.w.p2_w[threadIdx.x];
-        L.misc[2 * C + threadIdx.x] = 0.0f;        // dW2 accumulators
     }
     __syncthreads();
 
     // ---- project backward, position-tile local: d_z1 -> db; dW2 partial sums --------------------------------------
+    // Every wave leaves its 32 partial sums in Z (dead until the layer loop), a wave without a position tile zeros; they
+    // are added in wave order below.  (They used to meet in a float atomicAdd in LDS: the eight waves arrive in a different
+    // order from launch to launch, and the last bit of a third of the p2.weight entries moved with it --
+    // tests/test_fno_kernels_gpu.py::test_backward_is_bit_identical_run_to_run.)
     {
         float dw2[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         for (int ct = wave; ct < (N >> 4); ct += nwaves) {
@@ -486,7 +489,7 @@ __global__ void __launch_bounds__(TPB) fno_backward_kernel(const BwdArgs a) {
                 v += __shfl_xor(v, 2, 64);
                 v += __shfl_xor(v, 4, 64);
                 v += __shfl_xor(v, 8, 64);
-                if (r == 0) atomicAdd(&L.misc[2 * C + 16 * rt + 4 * q + j], v);   // LDS, 8 waves: order-insensitive to 1 ulp
+                if (r == 0) L.Z[wave * C + 16 * rt + 4 * q + j] = v;
             }
     }
     __syncthreads();
@@ -495,7 +498,11 @@ __global__ void __launch_bounds__(TPB) fno_backward_kernel(const BwdArgs a) {
     {
         const float s = row_dot(db, nullptr, N, NP);
         if ((threadIdx.x & 15) == 0 && (threadIdx.x >> 4) < C) grow[R_P1B + (threadIdx.x >> 4)] = s;
-        if (threadIdx.x < C) grow[R_P2W + threadIdx.x] = L.misc[2 * C + threadIdx.x];
+        if (threadIdx.x < C) {
+            float v = L.Z[threadIdx.x];
+            for (int w = 1; w < TPB / 64; ++w) v += L.Z[w * C + threadIdx.x];      // fixed order: deterministic
+            grow[R_P2W + threadIdx.x] = v;
+        }
         if (wave == 0) {
             float g = 0.0f;
             for (int n = lane; n < N; n += 64) g += L.gv[n];
@@ -627,9 +634,12 @@ __global__ void __launch_bounds__(TPB) fno_backward_kernel(const BwdArgs a) {
     }
     if (a.dbase) {
         for (int n = threadIdx.x; n < N; n += blockDim.x) {
-            float s = has_gout ? a.gout[(size_t)b * N + n] : 0.0f;
+            float s = 0.0f;
 #pragma unroll 8
             for (int c = 0; c < C; ++c) s = fmaf(L.misc[c], db[c * NP + n], s);
+            // gout last: it is usually far larger than the path through the network, and as the chain's start value each
+            // of the 32 steps rounded at its magnitude (measured: 2.6e-7 of the tensor's scale against 3.5e-8 for one rounding)
+            if (has_gout) s += a.gout[(size_t)b * N + n];
             a.dbase[(size_t)p * N + n] = s;
         }
     }
