@@ -115,7 +115,8 @@ int sur_encoder_backward_multi(void* stream, int njobs, const sur_encoder_params
                                const float* const* dzs, const int* ms, const int* row_bases, const int* row_counts,
                                const float* const* saveds, float* const* workspaces /* array may be NULL */);
 /* overwrite != 0 (and no Adam descriptor): g = sum of the rows instead of g += sum -- for gradient tensors that start
- * undefined (optimizer.zero_grad(set_to_none=True)), saves the zero-fill. */
+ * undefined (optimizer.zero_grad(set_to_none=True)), saves the zero-fill.  Every g[i] must be non-NULL, and with an Adam
+ * descriptor every w[i] too (the update is applied in place); -1 otherwise, before any launch. */
 int sur_flush_encoder_grads(void* stream, const sur_encoder_params* p, const sur_adam* adam /* may be NULL */, int overwrite);
 
 /* Floats per (step, sample) of the forward intermediates sur_chunk_forward saves for sur_chunk_backward (activated

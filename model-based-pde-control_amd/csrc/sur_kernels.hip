@@ -2986,10 +2986,22 @@ cell_wgrad_kernel(const sur_chunk_params p, const ChunkSpans spans, const float*
     if constexpr (GL) add_to_row(row, (const float*)gacc, psize_lstm);
 }
 
+// Adam's bias correction 1 - beta^step.  1.0f - powf(beta, step) cancels at small step counts: beta^step lies within a few
+// (1 - beta) of 1, where fp32 resolves 2^-24, so at step 2 of beta = 0.999 the difference 0.002 keeps 15 of its 24 bits
+// and the step multiplier sqrt(bc2) / bc1 is off by tens of units of its last place (measured: 3.8 of the 4 units the
+// tests allow p' at steps 2 .. 4, against 0.9 with this form).  -expm1(step log(beta)) has no subtraction.
+// (1.0 - pow((double)beta, step), the spelling of sac.hip, gives the same units in tests/test_surrogate_tail_gpu.py and a
+// flush launch 1 us longer: profiles/sur_tail_adam_ab.json.)
+__device__ __forceinline__ float adam_bias_correction(float beta, int step) {
+    return -expm1f((float)step * logf(beta));
+}
+
 // g[i][j] += sum_r partial[r][off_i + j]; the partial rows are re-zeroed.  With an Adam descriptor the reduced gradient is
 // consumed on the spot: g = sum (not accumulated), then the torch.optim.Adam update of the parameter element
-// (no weight decay, no amsgrad; same formula as torch's fused kernel) -- the optimizer costs no extra launch and the
-// gradients need no zeroing pass.
+// (no weight decay, no amsgrad): m' = beta1 m + (1 - beta1) g, v' = beta2 v + (1 - beta2) g^2,
+// p' = p - lr / bc1 * m' / (sqrt(v') / sqrt(bc2) + eps), torch's formula in fp32 with the bias corrections
+// bc = 1 - beta^step of adam_bias_correction above -- the optimizer costs no extra launch and the gradients need no
+// zeroing pass.
 #ifndef FLUSH_TPB
 #define FLUSH_TPB 1024   // the reduction over rows is a latency chain (rows / FLUSH_RG / 8 rounds of loads): 1024 threads = 32 row groups
 #endif
@@ -3027,8 +3039,8 @@ __device__ __forceinline__ void flush_grads_body(const Params& p, int psize, con
             m_old = adam.m[t];
             v_old = adam.v[t];
             w_old = *wdst;
-            bc1 = 1.0f - powf(adam.beta1, (float)step);
-            bc2 = 1.0f - powf(adam.beta2, (float)step);
+            bc1 = adam_bias_correction(adam.beta1, step);   // independent of the sum: before the row loop
+            bc2 = adam_bias_correction(adam.beta2, step);
         }
     }
     float acc = 0.0f;
@@ -3156,6 +3168,7 @@ __device__ __forceinline__ void adam_apply_body(const Params& p, int psize, cons
     const int step = *adam.step + 1;   // read before this block takes its ticket
     const float lr = *adam.lr;
     if (t < psize) {
+        const float bc1 = adam_bias_correction(adam.beta1, step), bc2 = adam_bias_correction(adam.beta2, step);
         int off = 0;
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
@@ -3165,7 +3178,6 @@ __device__ __forceinline__ void adam_apply_body(const Params& p, int psize, cons
                 const float v = adam.beta2 * adam.v[t] + (1.0f - adam.beta2) * g * g;
                 adam.m[t] = m;
                 adam.v[t] = v;
-                const float bc1 = 1.0f - powf(adam.beta1, (float)step), bc2 = 1.0f - powf(adam.beta2, (float)step);
                 const float denom = sqrtf(v) / sqrtf(bc2) + adam.eps;
                 float* w = const_cast<float*>(p.w[i]);
                 w[t - off] -= (lr / bc1) * (m / denom);
@@ -3529,6 +3541,8 @@ int sur_flush_encoder_grads(void* stream, const sur_encoder_params* p, const sur
     if (adam) {
         if (!adam->m || !adam->v || !adam->step || !adam->ticket || !adam->lr)
             return fail(-1, "flush: incomplete Adam descriptor");
+        for (int i = 0; i < SUR_ENC_NPARAM; ++i)   // the Adam branch updates the weights in place
+            if (!p->w[i]) return fail(-1, "sur_flush_encoder_grads: weight tensor %d is NULL", i);
         ad = *adam;
     }
     return launch_checked([&] {
@@ -3787,6 +3801,8 @@ int sur_flush_chunk_grads(void* stream, const sur_chunk_params* p, const sur_ada
     if (adam) {
         if (!adam->m || !adam->v || !adam->step || !adam->ticket || !adam->lr)
             return fail(-1, "flush: incomplete Adam descriptor");
+        for (int i = 0; i < SUR_ST_NPARAM; ++i)   // the Adam branch updates the weights in place
+            if (!p->w[i]) return fail(-1, "sur_flush_chunk_grads: weight tensor %d is NULL", i);
         ad = *adam;
     }
     return launch_checked([&] {
@@ -3810,6 +3826,10 @@ int sur_flush_all_grads(void* stream, const sur_encoder_params* e0, const sur_ad
                 return fail(-1, "sur_flush_all_grads: incomplete Adam descriptor %d", j);
             ad[j] = *in[j];
         }
+    for (int i = 0; i < SUR_ENC_NPARAM; ++i)   // the Adam branch updates the weights in place
+        if ((a0 && !e0->w[i]) || (a1 && !e1->w[i])) return fail(-1, "sur_flush_all_grads: encoder weight tensor %d is NULL", i);
+    for (int i = 0; i < SUR_ST_NPARAM; ++i)
+        if (a2 && !c2->w[i]) return fail(-1, "sur_flush_all_grads: chunk weight tensor %d is NULL", i);
     const int n0 = psize_of<SUR_ENC_NPARAM>(e0->size), n1 = psize_of<SUR_ENC_NPARAM>(e1->size), n2 = psize_of<SUR_ST_NPARAM>(c2->size);
     const int grid = flush_blocks(n0) + flush_blocks(n1) + flush_blocks(n2);
     return launch_checked([&] {
