@@ -16,7 +16,12 @@
 //                                  hidden state in LDS across steps, one workgroup per sample
 //   dec_fwd / dec_bwd / cell_wgrad everything of a chunk that is NOT recurrent (decoder, dx, LSTM weight gradients),
 //                                  for all (step, sample) pairs in parallel
-//   integrate, dgrad_scan, delta_loss, flush_*   prefix sums over time, the loss section, gradient reduction (+ Adam)
+//   integrate, dgrad_scan, latent_scan / _dscan   prefix sums over time
+//   delta_loss (_finalize), val_loss               the loss sections (one block reduction: loss_block_sums)
+//   flush_*, fold_rows, adam_all                   gradient reduction (+ Adam), row fold, Adam from g[]: one column sum, one
+//                                                  parameter lookup, one Adam update, one ticket epilogue between them
+// The extern "C" layer at the end validates on the host and launches; the checks and launch plans that several entry points
+// share are spelled once in front of it.
 // Conv-like layers are gather-GEMMs on v_mfma_f32_16x16x4_f32 (exact fp32).  Backward kernels do not recompute:
 // forward kernels write every intermediate to HBM and backward kernels read it back (HBM capacity and bandwidth are
 // free here, dependent-phase latency is not).  Parameter gradients are summed over space, time and the workgroup's
@@ -1754,6 +1759,33 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The end of a loss workgroup: its NSUM fp64 sums (waves first, then the waves' sums in wave order) go to `out`, the
+// workgroup's slot of the partial sums; then, unless the caller finishes the loss in a launch of its own, the workgroup takes
+// a ticket.  True for the workgroup that takes the last of `tickets`: every slot is visible to it once it has fenced.
+template <int NSUM>
+__device__ __forceinline__ bool loss_block_sums(const double (&acc)[NSUM], double* __restrict__ out, unsigned int* __restrict__ ticket,
+                                                int tickets, bool take_ticket = true) {
+    __shared__ double red[TPB / 64][NSUM];
+    __shared__ bool last;
+#pragma unroll
+    for (int j = 0; j < NSUM; ++j) {
+        const double w = wave_sum(acc[j]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < NSUM) {
+        double v = 0.0;
+        for (int w = 0; w < TPB / 64; ++w) v += red[w][threadIdx.x];
+        out[threadIdx.x] = v;
+    }
+    if (!take_ticket) return false;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = (atomicAdd(ticket, 1u) == (unsigned)(tickets - 1));
+    __syncthreads();
+    return last;
+}
+
 __device__ void delta_loss_finish(int B, int T, int N, int nsplit, float* __restrict__ hsteploss, float* __restrict__ loss,
                                   float* __restrict__ stats, double* __restrict__ partial, unsigned int* __restrict__ ticket);
 
@@ -1762,8 +1794,6 @@ delta_loss_kernel(const float* __restrict__ states, long sb, long st, const floa
                   float mean, float stdv, float* __restrict__ deltas, float* __restrict__ dd_all,
                   float* __restrict__ hsteploss, float* __restrict__ loss, float* __restrict__ stats,
                   double* __restrict__ partial, unsigned int* __restrict__ ticket, int t0, int take_ticket) {
-    __shared__ double red[TPB / 64][LOSS_NSUM];
-    __shared__ bool last;
     // blockIdx.x = time step, blockIdx.y = slice of the B*N elements of that step; LOSS_UNROLL elements per
     // thread per round with every load of the round issued before the first use
     // a launch covers the time steps [t0, t0 + gridDim.x) of the T rows; the ticket counts the workgroups of ALL T rows, so
@@ -1804,23 +1834,8 @@ delta_loss_kernel(const float* __restrict__ states, long sb, long st, const floa
     } else if (dd_all) {
         for (int e = blockIdx.y * TPB + threadIdx.x; e < per_t; e += stride) dd_all[(size_t)t * per_t + e] = 0.0f;
     }
-#pragma unroll
-    for (int j = 0; j < LOSS_NSUM; ++j) {
-        const double w = wave_sum(acc[j]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < LOSS_NSUM) {
-        double v = 0.0;
-        for (int w = 0; w < TPB / 64; ++w) v += red[w][threadIdx.x];
-        partial[((size_t)t * nsplit + blockIdx.y) * LOSS_NSUM + threadIdx.x] = v;
-    }
-    if (!take_ticket) return;   // the caller finishes the loss with delta_loss_finalize_kernel, off its critical path
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = (atomicAdd(ticket, 1u) == (unsigned)(T * nsplit - 1));
-    __syncthreads();
-    if (!last) return;
+    // without a ticket the caller finishes the loss with delta_loss_finalize_kernel, off its critical path
+    if (!loss_block_sums(acc, partial + ((size_t)t * nsplit + blockIdx.y) * LOSS_NSUM, ticket, T * nsplit, take_ticket != 0)) return;
     __threadfence();
     delta_loss_finish(B, T, N, nsplit, hsteploss, loss, stats, partial, ticket);
 }
@@ -1902,8 +1917,6 @@ val_loss_kernel(const float* __restrict__ states, long sb, long st, const float*
                 const float* __restrict__ inv_coef, float* __restrict__ deltas, float* __restrict__ decoded,
                 float* __restrict__ hsteploss, float* __restrict__ loss, float* __restrict__ scalars,
                 double* __restrict__ accum, double* __restrict__ partial, unsigned int* __restrict__ ticket) {
-    __shared__ double red[TPB / 64][VAL_NSUM];
-    __shared__ bool last;
     const int t = blockIdx.x, per_t = B * N, nsplit = gridDim.y;
     double acc[VAL_NSUM] = {0.0, 0.0, 0.0};
     for (int e = blockIdx.y * TPB + threadIdx.x; e < per_t; e += nsplit * TPB) {
@@ -1924,22 +1937,7 @@ val_loss_kernel(const float* __restrict__ states, long sb, long st, const float*
             acc[2] += (double)__fmul_rn(ed, ed);
         }
     }
-#pragma unroll
-    for (int j = 0; j < VAL_NSUM; ++j) {
-        const double w = wave_sum(acc[j]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < VAL_NSUM) {
-        double v = 0.0;
-        for (int w = 0; w < TPB / 64; ++w) v += red[w][threadIdx.x];
-        partial[((size_t)t * nsplit + blockIdx.y) * VAL_NSUM + threadIdx.x] = v;
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = (atomicAdd(ticket, 1u) == (unsigned)(T * nsplit - 1));
-    __syncthreads();
-    if (!last) return;
+    if (!loss_block_sums(acc, partial + ((size_t)t * nsplit + blockIdx.y) * VAL_NSUM, ticket, T * nsplit)) return;
     __threadfence();
 
     // the last workgroup: per-step sums by one thread per step (fixed order over the slices), then the three totals by
@@ -3008,6 +3006,76 @@ __device__ __forceinline__ float adam_bias_correction(float beta, int step) {
 constexpr int FLUSH_COLS = 32, FLUSH_RG = FLUSH_TPB / FLUSH_COLS;   // 16 columns (twice the blocks) measured slower: 34 vs 26 us
 __host__ __device__ inline int flush_blocks(int psize) { return (psize + FLUSH_COLS - 1) / FLUSH_COLS; }
 
+// The pieces the reductions and the two Adam launches share.
+//
+// One thread's share of a column of partial rows: the sum of rows rg, rg + FLUSH_RG, ... below `rows` (`stride` floats
+// apart), which are re-zeroed.  The loads of a round are all in flight before the first add / re-zero; the additions keep
+// row order.
+__device__ __forceinline__ float column_sum_rezero(float* col, int rows, int stride, int rg) {
+    constexpr int U = 8;
+    float acc = 0.0f;
+    for (int r0 = rg; r0 < rows; r0 += FLUSH_RG * U) {
+        float v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int r = r0 + FLUSH_RG * u;
+            v[u] = r < rows ? col[(size_t)r * stride] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int r = r0 + FLUSH_RG * u;
+            if (r < rows) {
+                acc += v[u];
+                col[(size_t)r * stride] = 0.0f;
+            }
+        }
+    }
+    return acc;
+}
+
+// a column's total from the row groups' sums in LDS, in row-group order
+__device__ __forceinline__ float combine_row_groups(const float (*part)[FLUSH_COLS + 1], int col) {
+    float tot = 0.0f;
+#pragma unroll
+    for (int i = 0; i < FLUSH_RG; ++i) tot += part[i][col];
+    return tot;
+}
+
+// element t of a pack's flat parameter order: where its gradient and its weight live
+template <int NP, typename Params>
+__device__ __forceinline__ void locate_param(const Params& p, int t, float*& g, float*& w) {
+    int off = 0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        if (t >= off && t < off + p.size[i]) {
+            g = p.g[i] + (t - off);
+            w = const_cast<float*>(p.w[i]) + (t - off);
+        }
+        off += p.size[i];
+    }
+}
+
+// the torch.optim.Adam update of element t from its old moments and weight: stores m', v' and p'
+__device__ __forceinline__ void adam_update(const sur_adam& adam, int t, float* w, float m_old, float v_old, float w_old, float g,
+                                            float lr, float bc1, float bc2) {
+    const float m = adam.beta1 * m_old + (1.0f - adam.beta1) * g;
+    const float v = adam.beta2 * v_old + (1.0f - adam.beta2) * g * g;
+    adam.m[t] = m;
+    adam.v[t] = v;
+    const float denom = sqrtf(v) / sqrtf(bc2) + adam.eps;
+    *w = w_old - (lr / bc1) * (m / denom);
+}
+
+// The workgroup that takes the last of a launch's nblk tickets advances the step counter and clears the ticket: like every
+// other workgroup it has read the step count before it took its ticket.
+__device__ __forceinline__ void adam_finish_step(const sur_adam& adam, int step, int nblk) {
+    __syncthreads();
+    if (threadIdx.x == 0 && atomicAdd(adam.ticket, 1u) == (unsigned)(nblk - 1)) {
+        *adam.step = step;
+        *adam.ticket = 0u;
+    }
+}
+
 template <int NP, typename Params>
 __device__ __forceinline__ void flush_grads_body(const Params& p, int psize, const sur_adam& adam, bool overwrite, int blk,
                                                  int nblk) {
@@ -3019,22 +3087,14 @@ __device__ __forceinline__ void flush_grads_body(const Params& p, int psize, con
     __shared__ float part[FLUSH_RG][FLUSH_COLS + 1];
     const int col = threadIdx.x & (FLUSH_COLS - 1), rg = threadIdx.x / FLUSH_COLS;
     const int t = blk * FLUSH_COLS + col;
-    const int step = adam.m ? *adam.step + 1 : 0;   // read before this block takes its ticket (see below)
+    const int step = adam.m ? *adam.step + 1 : 0;   // read before this block takes its ticket (adam_finish_step)
     const float lr = adam.m ? *adam.lr : 0.0f;      // device scalar: a scheduler can change it between graph replays
     const bool finisher = rg == 0 && t < psize;
     float* gdst = nullptr;
     float* wdst = nullptr;
     float m_old = 0.0f, v_old = 0.0f, w_old = 0.0f, bc1 = 1.0f, bc2 = 1.0f;
     if (finisher) {
-        int off = 0;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            if (t >= off && t < off + p.size[i]) {
-                gdst = p.g[i] + (t - off);
-                wdst = const_cast<float*>(p.w[i]) + (t - off);
-            }
-            off += p.size[i];
-        }
+        locate_param<NP>(p, t, gdst, wdst);
         if (adam.m) {
             m_old = adam.m[t];
             v_old = adam.v[t];
@@ -3043,53 +3103,20 @@ __device__ __forceinline__ void flush_grads_body(const Params& p, int psize, con
             bc2 = adam_bias_correction(adam.beta2, step);
         }
     }
-    float acc = 0.0f;
-    if (t < psize) {
-        constexpr int U = 8;   // loads of a round all in flight before the first add / re-zero (same summation order)
-        for (int r0 = rg; r0 < p.rows; r0 += FLUSH_RG * U) {
-            float v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int r = r0 + FLUSH_RG * u;
-                v[u] = r < p.rows ? p.partial[(size_t)r * psize + t] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int r = r0 + FLUSH_RG * u;
-                if (r < p.rows) {
-                    acc += v[u];
-                    p.partial[(size_t)r * psize + t] = 0.0f;
-                }
-            }
-        }
-    }
-    part[rg][col] = acc;
+    part[rg][col] = t < psize ? column_sum_rezero(p.partial + t, p.rows, psize, rg) : 0.0f;
     __syncthreads();
     if (finisher) {
-        float tot = 0.0f;
-#pragma unroll
-        for (int i = 0; i < FLUSH_RG; ++i) tot += part[i][col];
+        const float tot = combine_row_groups(part, col);
         if (adam.m) {
             *gdst = tot;
-            const float m = adam.beta1 * m_old + (1.0f - adam.beta1) * tot;
-            const float v = adam.beta2 * v_old + (1.0f - adam.beta2) * tot * tot;
-            adam.m[t] = m;
-            adam.v[t] = v;
-            const float denom = sqrtf(v) / sqrtf(bc2) + adam.eps;
-            *wdst = w_old - (lr / bc1) * (m / denom);
+            adam_update(adam, t, wdst, m_old, v_old, w_old, tot, lr, bc1, bc2);
         } else if (overwrite) {
             *gdst = tot;
         } else {
             *gdst += tot;
         }
     }
-    if (adam.m) {   // the workgroup that takes the last ticket has, like every other, already read the step count
-        __syncthreads();
-        if (threadIdx.x == 0 && atomicAdd(adam.ticket, 1u) == (unsigned)(nblk - 1)) {
-            *adam.step = step;
-            *adam.ticket = 0u;
-        }
-    }
+    if (adam.m) adam_finish_step(adam, step, nblk);
 }
 
 template <int NP, typename Params>
@@ -3120,35 +3147,9 @@ __device__ __forceinline__ void fold_rows_body(const FoldJob& j, int blk) {
     __shared__ float part[FLUSH_RG][FLUSH_COLS + 1];
     const int col = threadIdx.x & (FLUSH_COLS - 1), rg = threadIdx.x / FLUSH_COLS;
     const int t = blk * FLUSH_COLS + col;
-    float acc = 0.0f;
-    if (t < j.psize) {
-        constexpr int U = 8;
-        float* src = j.partial + (size_t)j.base * j.psize + t;
-        for (int r0 = rg; r0 < j.count; r0 += FLUSH_RG * U) {
-            float v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int r = r0 + FLUSH_RG * u;
-                v[u] = r < j.count ? src[(size_t)r * j.psize] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int r = r0 + FLUSH_RG * u;
-                if (r < j.count) {
-                    acc += v[u];
-                    src[(size_t)r * j.psize] = 0.0f;
-                }
-            }
-        }
-    }
-    part[rg][col] = acc;
+    part[rg][col] = t < j.psize ? column_sum_rezero(j.partial + (size_t)j.base * j.psize + t, j.count, j.psize, rg) : 0.0f;
     __syncthreads();
-    if (rg == 0 && t < j.psize) {
-        float tot = 0.0f;
-#pragma unroll
-        for (int i = 0; i < FLUSH_RG; ++i) tot += part[i][col];
-        j.partial[(size_t)j.dst * j.psize + t] += tot;
-    }
+    if (rg == 0 && t < j.psize) j.partial[(size_t)j.dst * j.psize + t] += combine_row_groups(part, col);
 }
 
 __global__ void __launch_bounds__(FLUSH_TPB) fold_rows_kernel(const FoldJob j0, const FoldJob j1, const FoldJob j2) {
@@ -3161,7 +3162,7 @@ __global__ void __launch_bounds__(FLUSH_TPB) fold_rows_kernel(const FoldJob j0, 
 
 // torch.optim.Adam (no weight decay / amsgrad) of a whole parameter pack from its gradient tensors: the optimizer of the
 // EAGER fused path (pdecontrol.surrogates.hipops.PackAdam) -- one launch instead of torch's per-step Python bookkeeping.
-// Same arithmetic as the Adam branch of flush_grads_body.
+// The update of the Adam branch of flush_grads_body (adam_update), fed from g[] instead of the row sum.
 template <int NP, typename Params>
 __device__ __forceinline__ void adam_apply_body(const Params& p, int psize, const sur_adam& adam, int blk, int nblk) {
     const int t = blk * TPB + threadIdx.x;
@@ -3169,27 +3170,12 @@ __device__ __forceinline__ void adam_apply_body(const Params& p, int psize, cons
     const float lr = *adam.lr;
     if (t < psize) {
         const float bc1 = adam_bias_correction(adam.beta1, step), bc2 = adam_bias_correction(adam.beta2, step);
-        int off = 0;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            if (t >= off && t < off + p.size[i]) {
-                const float g = p.g[i][t - off];
-                const float m = adam.beta1 * adam.m[t] + (1.0f - adam.beta1) * g;
-                const float v = adam.beta2 * adam.v[t] + (1.0f - adam.beta2) * g * g;
-                adam.m[t] = m;
-                adam.v[t] = v;
-                const float denom = sqrtf(v) / sqrtf(bc2) + adam.eps;
-                float* w = const_cast<float*>(p.w[i]);
-                w[t - off] -= (lr / bc1) * (m / denom);
-            }
-            off += p.size[i];
-        }
+        float* g = nullptr;
+        float* w = nullptr;
+        locate_param<NP>(p, t, g, w);
+        adam_update(adam, t, w, adam.m[t], adam.v[t], *w, *g, lr, bc1, bc2);
     }
-    __syncthreads();
-    if (threadIdx.x == 0 && atomicAdd(adam.ticket, 1u) == (unsigned)(nblk - 1)) {
-        *adam.step = step;
-        *adam.ticket = 0u;
-    }
+    adam_finish_step(adam, step, nblk);
 }
 
 __global__ void __launch_bounds__(TPB)
@@ -3222,6 +3208,120 @@ int set_lds(K kernel, size_t bytes, const char* what) {
     if (bytes > LDS_LIMIT) return fail(-4, "%s needs %zu B of LDS (> 160 KiB): N too large for the fused path", what, bytes);
     if (bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     return 0;
+}
+
+// ---- host checks and launch plans the entry points share ------------------------------------------------------------
+bool adam_complete(const sur_adam& a) { return a.m && a.v && a.step && a.ticket && a.lr; }
+
+// Every gradient tensor of a pack and, where the launch updates the weights in place (need_w), every weight tensor.  `label`
+// names the pack in a call that takes several; sur_adam_apply reads both kinds of every pack and does not name the kind.
+template <int NP, typename Params>
+int check_pack_tensors(const char* who, const char* label, const Params& p, bool need_w, bool name_kind = true) {
+    for (int i = 0; i < NP; ++i)
+        if (!p.g[i]) return fail(-1, "%s: %s%stensor %d is NULL", who, label, name_kind ? "gradient " : "", i);
+    for (int i = 0; need_w && i < NP; ++i)
+        if (!p.w[i]) return fail(-1, "%s: %s%stensor %d is NULL", who, label, name_kind ? "weight " : "", i);
+    return 0;
+}
+
+// sur_flush_encoder_grads / sur_flush_chunk_grads
+template <int NP, typename Params>
+int flush_pack(void* stream, const Params* p, const sur_adam* adam, int overwrite, const char* who, const char* what) {
+    if (!p || !p->partial) return fail(-1, "%s: bad argument", who);
+    if (adam && !adam_complete(*adam)) return fail(-1, "flush: incomplete Adam descriptor");
+    if (int rc = check_pack_tensors<NP>(who, "", *p, adam != nullptr)) return rc;   // the Adam branch updates the weights in place
+    const int psize = psize_of<NP>(p->size);
+    const sur_adam ad = adam ? *adam : sur_adam{};
+    return launch_checked([&] {
+        hipLaunchKernelGGL((flush_grads_kernel<NP, Params>), dim3(flush_blocks(psize)), dim3(FLUSH_TPB), 0, (hipStream_t)stream, *p,
+                           psize, ad, overwrite);
+    }, what);
+}
+
+// one pack of sur_adam_apply: without a descriptor it is skipped (n stays 0)
+template <int NP, typename Params>
+int adam_pack(const Params* src, const sur_adam* adam, const char* label, Params& dst, int& n) {
+    if (!adam) return 0;
+    dst = *src;
+    n = psize_of<NP>(src->size);
+    return check_pack_tensors<NP>("sur_adam_apply", label, *src, true, false);
+}
+
+// rows [base, base + count) of an encoder's partial-gradient buffer; `who` names the entry point (and the job)
+int check_partial_rows(const char* who, const sur_encoder_params& p, int base, int count) {
+    if (!p.partial || count <= 0 || base < 0 || base + count > p.rows)
+        return fail(-1, "%s: partial rows [%d, %d) outside the buffer of %d rows", who, base, base + count, p.rows);
+    return 0;
+}
+
+// LDS bytes of the whole-encoder backward (enc_bwd_kernel, enc_bwd_multi_kernel), and whether the gradient accumulators are
+// among them
+size_t enc_bwd_lds(const sur_encoder_params& p, int& grads_in_lds) {
+    const int psize = psize_of<SUR_ENC_NPARAM>(p.size);
+    const size_t base = sizeof(float) * (enc_act_floats(p, true) + psize);
+    grads_in_lds = accumulators_fit(base + sizeof(float) * psize) ? 1 : 0;
+    return base + (grads_in_lds ? sizeof(float) * psize : 0);
+}
+
+// The jobs of ONE residual block of a multi call, wide ones (MFMA kernels) and narrow ones (one wave per sample), and their
+// launches: the wide jobs' workgroups in one launch, the first narrow job's behind them in the same launch when there is a
+// wide job, every further narrow job in a launch of its own.  One instantiation serves the wide launch, so the wide jobs
+// keep their gradient accumulators in LDS all together or not at all (all_gl; the forward has none).
+inline void accumulate_in_rows(EncFwdJob&) {}
+inline void accumulate_in_rows(EncBlockJob& j) { j.grads_in_lds = 0; }
+
+template <typename Wide>
+struct BlockJobs {
+    Wide wide[3] = {};
+    NarrowJob narrow[3] = {};
+    size_t lds_w = 0;
+    int grid_w = 0, nw = 0, nn = 0;
+    bool all_gl = true;
+
+    void add_wide(Wide job, int wgs, size_t lds, bool gl = true) {
+        job.wg_begin = grid_w;
+        job.wg_count = wgs;
+        wide[nw++] = job;
+        grid_w += wgs;
+        lds_w = lds > lds_w ? lds : lds_w;
+        all_gl = all_gl && gl;
+    }
+    void add_narrow(const NarrowJob& job) { narrow[nn++] = job; }
+
+    // launch_wide(lds, grid, first workgroup of narrow[0]) launches the wide kernel; narrow_lds(job) is a narrow job's LDS
+    template <typename LaunchWide, typename NarrowLds, typename NarrowKernel>
+    int launch(void* stream, LaunchWide launch_wide, NarrowLds narrow_lds, NarrowKernel narrow_kernel, const char* narrow_name,
+               const char* narrow_what) {
+        if (nw) {
+            const bool ride = nn > 0;
+            const size_t lds = ride && narrow_lds(narrow[0]) > lds_w ? narrow_lds(narrow[0]) : lds_w;
+            const int grid = grid_w + (ride ? narrow[0].wg_count : 0);
+            if (!all_gl)
+                for (int k = 0; k < nw; ++k) accumulate_in_rows(wide[k]);
+            if (int rc = launch_wide(lds, grid, ride ? grid_w : grid)) return rc;
+        }
+        for (int k = nw ? 1 : 0; k < nn; ++k) {
+            const NarrowJob& nj = narrow[k];
+            const size_t lds_n = narrow_lds(nj);
+            if (int rc = set_lds(narrow_kernel, lds_n, narrow_name)) return rc;
+            if (int rc = launch_checked([&] {
+                    hipLaunchKernelGGL(narrow_kernel, dim3(nj.wg_count), dim3(TPB), lds_n, (hipStream_t)stream, nj);
+                }, narrow_what)) return rc;
+        }
+        return 0;
+    }
+};
+
+// the parameter floats of the ConvLSTM cell and of the decoder
+int psize_lstm(const sur_chunk_params& p) { return psize_of<ST_NLSTM>(p.size); }
+int psize_dec(const sur_chunk_params& p) { return psize_of<SUR_ST_NPARAM - ST_NLSTM>(p.size + ST_NLSTM); }
+
+// f(T) with the block size T that cell_chain_threads() picked as a compile-time constant: f names a cell chain kernel with it
+template <typename F>
+int with_chain_threads(int threads, F&& f) {
+    if (threads == TPB) return f(std::integral_constant<int, TPB>{});
+    if (threads == 2 * TPB) return f(std::integral_constant<int, 2 * TPB>{});
+    return f(std::integral_constant<int, 4 * TPB>{});
 }
 
 }  // namespace
@@ -3333,9 +3433,9 @@ int sur_encoder_saved_floats(const sur_encoder_params* p) {
 
 int sur_encoder_forward(void* stream, const sur_encoder_params* p, const float* x, int m, float* z, float* saved) {
     if (!p || !x || !z || m <= 0) return fail(-1, "sur_encoder_forward: bad argument");
+    if (int rc = enc_geometry(p, "sur_encoder_forward")) return rc;
     if (saved && sur_encoder_saved_floats(p) == 0)
         return fail(-4, "sur_encoder_forward: this geometry has no saved-activation path (pass saved = NULL)");
-    if (int rc = enc_geometry(p, "sur_encoder_forward")) return rc;
     const int psize = psize_of<SUR_ENC_NPARAM>(p->size);
     const size_t lds = sizeof(float) * (enc_act_floats(*p, false) + psize);
     if (int rc = set_lds(enc_fwd_kernel, lds, "encoder forward")) return rc;
@@ -3350,13 +3450,9 @@ int sur_encoder_backward(void* stream, const sur_encoder_params* p, const float*
     if (int rc = enc_geometry(p, "sur_encoder_backward")) return rc;
     if (saved && sur_encoder_saved_floats(p) == 0)
         return fail(-4, "sur_encoder_backward: this geometry has no saved-activation path (pass saved = NULL)");
-    if (!p->partial || row_count <= 0 || row_base < 0 || row_base + row_count > p->rows)
-        return fail(-1, "sur_encoder_backward: partial rows [%d, %d) outside the buffer of %d rows", row_base,
-                    row_base + row_count, p ? p->rows : 0);
-    const int psize = psize_of<SUR_ENC_NPARAM>(p->size);
-    const size_t base = sizeof(float) * (enc_act_floats(*p, true) + psize);
-    int grads_in_lds = accumulators_fit(base + sizeof(float) * psize) ? 1 : 0;
-    const size_t lds = base + (grads_in_lds ? sizeof(float) * psize : 0);
+    if (int rc = check_partial_rows("sur_encoder_backward", *p, row_base, row_count)) return rc;
+    int grads_in_lds = 0;
+    const size_t lds = enc_bwd_lds(*p, grads_in_lds);
     if (int rc = set_lds(enc_bwd_kernel, lds, "encoder backward")) return rc;
     const int grid = m < row_count ? m : row_count;
     return launch_checked([&] {
@@ -3369,57 +3465,43 @@ int sur_encoder_forward_multi(void* stream, int njobs, const sur_encoder_params*
                               float* const* zs, float* const* saveds, int max_workgroups) {
     if (njobs < 1 || njobs > 2 || !ps || !xs || !ms || !zs || !saveds || max_workgroups <= 0)
         return fail(-1, "sur_encoder_forward_multi: bad argument (1 or 2 jobs)");
+    for (int j = 0; j < njobs; ++j) {      // every job is checked before the first launch
+        const sur_encoder_params* p = ps[j];
+        if (!p || !xs[j] || !zs[j] || !saveds[j] || ms[j] <= 0)
+            return fail(-1, "sur_encoder_forward_multi: job %d: bad argument (the `saved` buffer is required)", j);
+        if (int rc = enc_geometry(p, "sur_encoder_forward_multi")) return rc;
+        if (sur_encoder_saved_floats(p) == 0) return fail(-4, "sur_encoder_forward_multi: job %d: geometry not float4-granular", j);
+    }
     for (int blk = 0; blk < 3; ++blk) {
-        // the jobs of this block, wide (MFMA kernels) and narrow (one wave per sample) ones in a launch each
-        EncFwdJob wide[2] = {};
-        NarrowJob narrow[2] = {};
-        size_t lds_w = 0;
-        int grid_w = 0, nw = 0, nn = 0;
+        BlockJobs<EncFwdJob> jobs;
         for (int j = 0; j < njobs; ++j) {
             const sur_encoder_params* p = ps[j];
-            if (!p || !xs[j] || !zs[j] || !saveds[j] || ms[j] <= 0)
-                return fail(-1, "sur_encoder_forward_multi: job %d: bad argument (the `saved` buffer is required)", j);
-            if (sur_encoder_saved_floats(p) == 0) return fail(-4, "sur_encoder_forward_multi: job %d: geometry not float4-granular", j);
-            if (int rc = enc_geometry(p, "sur_encoder_forward_multi")) return rc;
             const EncBlockGeom gm = enc_block_geom(*p, blk);
-            if (enc_narrow(*p)) {      // one wave per sample, a launch of its own
+            if (enc_narrow(*p)) {
                 const int per_wg = TPB / 64, passes = (ms[j] + per_wg - 1) / per_wg;
                 NarrowJob nj = narrow_job(*p, blk, ms[j]);
                 nj.x = xs[j];
                 nj.z = blk == 2 ? zs[j] : nullptr;
                 nj.saved = saveds[j];
                 nj.wg_count = passes < max_workgroups ? passes : max_workgroups;
-                narrow[nn++] = nj;
+                jobs.add_narrow(nj);
             } else {
-                const size_t need = sizeof(float) * (gm.cin * gm.hin + 7 * gm.cout * gm.hout + gm.psize_blk);
-                lds_w = need > lds_w ? need : lds_w;
-                const int wgs = ms[j] < max_workgroups ? ms[j] : max_workgroups;
-                wide[nw++] = EncFwdJob{*p, xs[j], zs[j], saveds[j], ms[j], grid_w, wgs};
-                grid_w += wgs;
+                jobs.add_wide(EncFwdJob{*p, xs[j], zs[j], saveds[j], ms[j], 0, 0}, ms[j] < max_workgroups ? ms[j] : max_workgroups,
+                              sizeof(float) * (gm.cin * gm.hin + 7 * gm.cout * gm.hout + gm.psize_blk));
             }
         }
-        // ONE launch: the wide jobs' workgroups first, the (first) narrow job's behind them; further narrow jobs on their own
+        auto launch_wide = [&](size_t lds, int grid, int narrow_begin) -> int {
+            if (int rc = set_lds(enc_block_fwd_multi_kernel, lds, "encoder block forward")) return rc;
+            return launch_checked([&] {
+                hipLaunchKernelGGL(enc_block_fwd_multi_kernel, dim3(grid), dim3(TPB), lds, (hipStream_t)stream, jobs.wide[0],
+                                   jobs.wide[1], jobs.nw, blk, jobs.narrow[0], narrow_begin);
+            }, "enc_block_fwd");
+        };
         auto narrow_lds = [](const NarrowJob& nj) {
             return sizeof(float) * ((size_t)(TPB / 64) * nr_fwd_wave_floats(nj.cin, nj.hin, nj.cout, nj.hout) + nj.psize_blk);
         };
-        if (nw) {
-            const bool ride = nn > 0;
-            const size_t lds = ride && narrow_lds(narrow[0]) > lds_w ? narrow_lds(narrow[0]) : lds_w;
-            const int grid = grid_w + (ride ? narrow[0].wg_count : 0);
-            if (int rc = set_lds(enc_block_fwd_multi_kernel, lds, "encoder block forward")) return rc;
-            if (int rc = launch_checked([&] {
-                    hipLaunchKernelGGL(enc_block_fwd_multi_kernel, dim3(grid), dim3(TPB), lds, (hipStream_t)stream, wide[0], wide[1], nw,
-                                       blk, narrow[0], ride ? grid_w : grid);
-                }, "enc_block_fwd")) return rc;
-        }
-        for (int k = nw ? 1 : 0; k < nn; ++k) {
-            const NarrowJob& nj = narrow[k];
-            const size_t lds_n = narrow_lds(nj);
-            if (int rc = set_lds(enc_narrow_fwd_kernel, lds_n, "narrow encoder block forward")) return rc;
-            if (int rc = launch_checked([&] {
-                    hipLaunchKernelGGL(enc_narrow_fwd_kernel, dim3(nj.wg_count), dim3(TPB), lds_n, (hipStream_t)stream, nj);
-                }, "enc_narrow_fwd")) return rc;
-        }
+        if (int rc = jobs.launch(stream, launch_wide, narrow_lds, enc_narrow_fwd_kernel, "narrow encoder block forward", "enc_narrow_fwd"))
+            return rc;
     }
     return 0;
 }
@@ -3434,29 +3516,30 @@ int sur_encoder_backward_multi(void* stream, int njobs, const sur_encoder_params
                                const float* const* saveds, float* const* workspaces) {
     if (njobs < 1 || njobs > 3 || !ps || !xs || !dzs || !ms || !row_bases || !row_counts || !saveds)
         return fail(-1, "sur_encoder_backward_multi: bad argument (1 to 3 jobs)");
-    for (int j = 0; j < njobs; ++j) {
-        if (!ps[j]) return fail(-1, "sur_encoder_backward_multi: job %d: no parameters", j);
+    for (int j = 0; j < njobs; ++j) {      // every job is checked before the first launch
+        char who[48];
+        snprintf(who, sizeof(who), "sur_encoder_backward_multi: job %d", j);
+        if (!ps[j]) return fail(-1, "%s: no parameters", who);
         if (int rc = enc_geometry(ps[j], "sur_encoder_backward_multi")) return rc;
+        if (!xs[j] || !dzs[j] || ms[j] <= 0) return fail(-1, "%s: bad argument", who);
+        if (int rc = check_partial_rows(who, *ps[j], row_bases[j], row_counts[j])) return rc;
     }
     bool split = workspaces != nullptr;
-    for (int j = 0; j < njobs && split; ++j) split = saveds[j] && workspaces[j] && ps[j] && sur_encoder_saved_floats(ps[j]) > 0;
+    for (int j = 0; j < njobs && split; ++j) split = saveds[j] && workspaces[j] && sur_encoder_saved_floats(ps[j]) > 0;
     if (split) {
-        // one residual block per launch, last block first; every launch carries all jobs
-        for (int blk = 2; blk >= 0; --blk) {
-            EncBlockJob wide[3] = {};
-            NarrowJob narrow[3] = {};
-            size_t lds_w = 0;
-            int grid_w = 0, nw = 0, nn = 0;
+        for (int blk = 2; blk >= 0; --blk)
             for (int j = 0; j < njobs; ++j) {
-                const sur_encoder_params* p = ps[j];
-                if (!xs[j] || !dzs[j] || ms[j] <= 0) return fail(-1, "sur_encoder_backward_multi: job %d: bad argument", j);
-                if (!p->partial || row_counts[j] <= 0 || row_bases[j] < 0 || row_bases[j] + row_counts[j] > p->rows)
-                    return fail(-1, "sur_encoder_backward_multi: job %d: partial rows [%d, %d) outside the buffer of %d rows", j,
-                                row_bases[j], row_bases[j] + row_counts[j], p->rows);
-                const EncBlockGeom gm = enc_block_geom(*p, blk);
+                const EncBlockGeom gm = enc_block_geom(*ps[j], blk);
                 if ((gm.cout * gm.hout) & 3 || ((gm.cin * gm.hin) & 3 && blk > 0))
                     return fail(-4, "sur_encoder_backward_multi: job %d: block %d is not float4-granular", j, blk);
-                if (enc_narrow(*p)) {       // one wave per sample, gradient accumulators per wave in LDS, a launch of its own
+            }
+        // one residual block per launch, last block first; every launch carries all jobs
+        for (int blk = 2; blk >= 0; --blk) {
+            BlockJobs<EncBlockJob> jobs;
+            for (int j = 0; j < njobs; ++j) {
+                const sur_encoder_params* p = ps[j];
+                const EncBlockGeom gm = enc_block_geom(*p, blk);
+                if (enc_narrow(*p)) {       // gradient accumulators per wave in LDS
                     const int per_wg = TPB / 64, passes = (ms[j] + per_wg - 1) / per_wg;
                     NarrowJob nj = narrow_job(*p, blk, ms[j]);
                     nj.x = xs[j];
@@ -3466,43 +3549,27 @@ int sur_encoder_backward_multi(void* stream, int njobs, const sur_encoder_params
                     nj.wg_count = passes < row_counts[j] ? passes : row_counts[j];
                     nj.row_stride = psize_of<SUR_ENC_NPARAM>(p->size);
                     nj.rows = p->partial + (size_t)row_bases[j] * nj.row_stride + gm.param_off;
-                    narrow[nn++] = nj;
+                    jobs.add_narrow(nj);
                 } else {
                     const size_t base = sizeof(float) * (enc_block_act_floats(gm) + gm.psize_blk);
                     const int gl = accumulators_fit(base + sizeof(float) * gm.psize_blk) ? 1 : 0;
-                    const size_t need = base + (gl ? sizeof(float) * gm.psize_blk : 0);
-                    lds_w = need > lds_w ? need : lds_w;
-                    const int wgs = ms[j] < row_counts[j] ? ms[j] : row_counts[j];
-                    wide[nw++] = EncBlockJob{*p, xs[j], dzs[j], saveds[j], workspaces[j], ms[j], row_bases[j], grid_w, wgs, gl};
-                    grid_w += wgs;
+                    jobs.add_wide(EncBlockJob{*p, xs[j], dzs[j], saveds[j], workspaces[j], ms[j], row_bases[j], 0, 0, gl},
+                                  ms[j] < row_counts[j] ? ms[j] : row_counts[j], base + (gl ? sizeof(float) * gm.psize_blk : 0), gl != 0);
                 }
             }
+            auto launch_wide = [&](size_t lds, int grid, int narrow_begin) -> int {
+                auto kernel = jobs.all_gl ? enc_block_bwd_multi_kernel<true> : enc_block_bwd_multi_kernel<false>;
+                if (int rc = set_lds(kernel, lds, "encoder block backward")) return rc;
+                return launch_checked([&] {
+                    hipLaunchKernelGGL(kernel, dim3(grid), dim3(TPB), lds, (hipStream_t)stream, jobs.wide[0], jobs.wide[1], jobs.wide[2],
+                                       jobs.nw, blk, jobs.narrow[0], narrow_begin);
+                }, "enc_block_bwd");
+            };
             auto narrow_lds = [](const NarrowJob& nj) {
                 return sizeof(float) * ((size_t)(TPB / 64) * nr_bwd_wave_floats(nj.cin, nj.hin, nj.cout, nj.hout, nj.psize_blk) + nj.psize_blk);
             };
-            if (nw) {      // ONE launch: the wide jobs' workgroups first, the (first) narrow job's behind them
-                const bool ride = nn > 0;
-                const size_t lds = ride && narrow_lds(narrow[0]) > lds_w ? narrow_lds(narrow[0]) : lds_w;
-                const int grid = grid_w + (ride ? narrow[0].wg_count : 0);
-                bool all_gl = true;       // LDS accumulators for every wide job, or for none (one instantiation serves the launch)
-                for (int k = 0; k < nw; ++k) all_gl = all_gl && wide[k].grads_in_lds;
-                if (!all_gl)
-                    for (int k = 0; k < nw; ++k) wide[k].grads_in_lds = 0;
-                auto kernel = all_gl ? enc_block_bwd_multi_kernel<true> : enc_block_bwd_multi_kernel<false>;
-                if (int rc = set_lds(kernel, lds, "encoder block backward")) return rc;
-                if (int rc = launch_checked([&] {
-                        hipLaunchKernelGGL(kernel, dim3(grid), dim3(TPB), lds, (hipStream_t)stream, wide[0], wide[1], wide[2], nw, blk, narrow[0],
-                                           ride ? grid_w : grid);
-                    }, "enc_block_bwd")) return rc;
-            }
-            for (int k = nw ? 1 : 0; k < nn; ++k) {
-                const NarrowJob& nj = narrow[k];
-                const size_t lds_n = narrow_lds(nj);
-                if (int rc = set_lds(enc_narrow_bwd_kernel, lds_n, "narrow encoder block backward")) return rc;
-                if (int rc = launch_checked([&] {
-                        hipLaunchKernelGGL(enc_narrow_bwd_kernel, dim3(nj.wg_count), dim3(TPB), lds_n, (hipStream_t)stream, nj);
-                    }, "enc_narrow_bwd")) return rc;
-            }
+            if (int rc = jobs.launch(stream, launch_wide, narrow_lds, enc_narrow_bwd_kernel, "narrow encoder block backward", "enc_narrow_bwd"))
+                return rc;
         }
         return 0;
     }
@@ -3511,16 +3578,10 @@ int sur_encoder_backward_multi(void* stream, int njobs, const sur_encoder_params
     int grid = 0;
     for (int j = 0; j < njobs; ++j) {
         const sur_encoder_params* p = ps[j];
-        if (!p || !xs[j] || !dzs[j] || ms[j] <= 0) return fail(-1, "sur_encoder_backward_multi: job %d: bad argument", j);
-        if (!p->partial || row_counts[j] <= 0 || row_bases[j] < 0 || row_bases[j] + row_counts[j] > p->rows)
-            return fail(-1, "sur_encoder_backward_multi: job %d: partial rows [%d, %d) outside the buffer of %d rows", j, row_bases[j],
-                        row_bases[j] + row_counts[j], p->rows);
         if (saveds[j] && sur_encoder_saved_floats(p) == 0)
             return fail(-4, "sur_encoder_backward_multi: job %d: this geometry has no saved-activation path", j);
-        const int psize = psize_of<SUR_ENC_NPARAM>(p->size);
-        const size_t base = sizeof(float) * (enc_act_floats(*p, true) + psize);
-        const int gl = accumulators_fit(base + sizeof(float) * psize) ? 1 : 0;
-        const size_t need = base + (gl ? sizeof(float) * psize : 0);
+        int gl = 0;
+        const size_t need = enc_bwd_lds(*p, gl);
         lds = need > lds ? need : lds;
         const int wgs = ms[j] < row_counts[j] ? ms[j] : row_counts[j];
         jobs[j] = EncBwdJob{*p, xs[j], dzs[j], saveds[j], ms[j], row_bases[j], grid, wgs, gl};
@@ -3533,22 +3594,7 @@ int sur_encoder_backward_multi(void* stream, int njobs, const sur_encoder_params
 }
 
 int sur_flush_encoder_grads(void* stream, const sur_encoder_params* p, const sur_adam* adam, int overwrite) {
-    if (!p || !p->partial) return fail(-1, "sur_flush_encoder_grads: bad argument");
-    for (int i = 0; i < SUR_ENC_NPARAM; ++i)
-        if (!p->g[i]) return fail(-1, "sur_flush_encoder_grads: gradient tensor %d is NULL", i);
-    const int psize = psize_of<SUR_ENC_NPARAM>(p->size);
-    sur_adam ad{};
-    if (adam) {
-        if (!adam->m || !adam->v || !adam->step || !adam->ticket || !adam->lr)
-            return fail(-1, "flush: incomplete Adam descriptor");
-        for (int i = 0; i < SUR_ENC_NPARAM; ++i)   // the Adam branch updates the weights in place
-            if (!p->w[i]) return fail(-1, "sur_flush_encoder_grads: weight tensor %d is NULL", i);
-        ad = *adam;
-    }
-    return launch_checked([&] {
-        hipLaunchKernelGGL((flush_grads_kernel<SUR_ENC_NPARAM, sur_encoder_params>), dim3(flush_blocks(psize)), dim3(FLUSH_TPB), 0,
-                           (hipStream_t)stream, *p, psize, ad, overwrite);
-    }, "flush_enc");
+    return flush_pack<SUR_ENC_NPARAM>(stream, p, adam, overwrite, "sur_flush_encoder_grads", "flush_enc");
 }
 
 int sur_chunk_saved_floats(const sur_chunk_params* p) {
@@ -3574,11 +3620,8 @@ static int chunk_forward_launches(void* stream, const sur_chunk_params* p, const
     if (p->hq & 15) return fail(-4, "%s: latent width N/4 = %d must be a multiple of 16", who, p->hq);
     if (saved && sur_chunk_saved_floats(p) == 0)
         return fail(-4, "%s: hq = %d, ca = %d, cs = %d: no `saved` buffer for this geometry", who, p->hq, p->ca, p->cs);
-    int psize_lstm = 0, psize_dec = 0;
-    for (int i = 0; i < ST_NLSTM; ++i) psize_lstm += p->size[i];
-    for (int i = ST_NLSTM; i < SUR_ST_NPARAM; ++i) psize_dec += p->size[i];
-    const size_t lds_cell = sizeof(float) * (cell_fwd_act_floats(*p) + psize_lstm);
-    const size_t lds_dec = sizeof(float) * (dec_act_floats(*p, false) + psize_dec);
+    const size_t lds_cell = sizeof(float) * (cell_fwd_act_floats(*p) + psize_lstm(*p));
+    const size_t lds_dec = sizeof(float) * (dec_act_floats(*p, false) + psize_dec(*p));
     if (int rc = set_lds(dec_fwd_kernel, lds_dec, "decoder forward")) return rc;
     const int m = k * b;
     const int chain_threads = cell_chain_threads(*p);
@@ -3589,9 +3632,7 @@ static int chunk_forward_launches(void* stream, const sur_chunk_params* p, const
                                hc_bstride, k, s, b, h_all, c_all, saved);
         }, "cell_fwd");
     };
-    if (int rc = chain_threads == TPB ? launch_cell_fwd(cell_fwd_kernel<TPB>)
-                                      : (chain_threads == 2 * TPB ? launch_cell_fwd(cell_fwd_kernel<2 * TPB>)
-                                                                  : launch_cell_fwd(cell_fwd_kernel<4 * TPB>)))
+    if (int rc = with_chain_threads(chain_threads, [&](auto t) { return launch_cell_fwd(cell_fwd_kernel<decltype(t)::value>); }))
         return rc;
     const float* dec_in = h_all;
     if (z_all) {
@@ -3673,9 +3714,7 @@ static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const C
                     row_base + row_count, spans.n * b);
     // decoder backward of all (step, sample) pairs in parallel, then the cell chains (one workgroup per chunk and
     // sample), then dx and the LSTM weight gradients of all pairs in parallel
-    int psize_lstm = 0, psize_dec = 0;
-    for (int i = 0; i < ST_NLSTM; ++i) psize_lstm += p->size[i];
-    for (int i = ST_NLSTM; i < SUR_ST_NPARAM; ++i) psize_dec += p->size[i];
+    const int n_lstm = psize_lstm(*p), n_dec = psize_dec(*p);
     const int m = k_total * b, n = 4 * p->hq, sl = p->cs * p->hq;
     float* dh_dec = workspace;
     float* dg_all = workspace + (size_t)m * sl;
@@ -3697,22 +3736,21 @@ static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const C
             }, "dgrad_scan")) return rc;
         ga = ga_all;
     }
-    const size_t dec_base = sizeof(float) * (dec_act_floats(*p, true) + psize_dec);
-    const int dec_gl = accumulators_fit(dec_base + sizeof(float) * psize_dec) ? 1 : 0;
-    const size_t lds_dec = dec_base + (dec_gl ? sizeof(float) * psize_dec : 0);
-    const size_t lds_cell = sizeof(float) * (cell_bwd_act_floats(*p) + psize_lstm);
+    const size_t dec_base = sizeof(float) * (dec_act_floats(*p, true) + n_dec);
+    const bool dec_gl = accumulators_fit(dec_base + sizeof(float) * n_dec);
+    const size_t lds_dec = dec_base + (dec_gl ? sizeof(float) * n_dec : 0);
+    const size_t lds_cell = sizeof(float) * (cell_bwd_act_floats(*p) + n_lstm);
     const size_t wg_base = sizeof(float) * (cell_wgrad_act_floats(*p) + p->size[SUR_ST_WXI] + p->size[SUR_ST_WXF] + p->size[SUR_ST_WXC] +
                                             p->size[SUR_ST_WXO]);      // activations + the staged Wx_g
-    const int wg_gl = accumulators_fit(wg_base + sizeof(float) * psize_lstm) ? 1 : 0;
-    const size_t lds_wg = wg_base + (wg_gl ? sizeof(float) * psize_lstm : 0);
-    if (int rc = dec_gl ? set_lds(dec_bwd_kernel<true>, lds_dec, "decoder backward") : set_lds(dec_bwd_kernel<false>, lds_dec, "decoder backward"))
-        return rc;
-    if (int rc = wg_gl ? set_lds(cell_wgrad_kernel<true>, lds_wg, "cell weight gradients") : set_lds(cell_wgrad_kernel<false>, lds_wg, "cell weight gradients"))
-        return rc;
+    const bool wg_gl = accumulators_fit(wg_base + sizeof(float) * n_lstm);
+    const size_t lds_wg = wg_base + (wg_gl ? sizeof(float) * n_lstm : 0);
+    auto dec_bwd = dec_gl ? dec_bwd_kernel<true> : dec_bwd_kernel<false>;
+    auto cell_wgrad = wg_gl ? cell_wgrad_kernel<true> : cell_wgrad_kernel<false>;
+    if (int rc = set_lds(dec_bwd, lds_dec, "decoder backward")) return rc;
+    if (int rc = set_lds(cell_wgrad, lds_wg, "cell weight gradients")) return rc;
     const int grid = m < row_count ? m : row_count;
     if (int rc = launch_checked([&] {
-            if (dec_gl) hipLaunchKernelGGL(dec_bwd_kernel<true>, dim3(grid), dim3(TPB), lds_dec, (hipStream_t)stream, *p, saved, ga, m, dh_dec, row_base);
-            else hipLaunchKernelGGL(dec_bwd_kernel<false>, dim3(grid), dim3(TPB), lds_dec, (hipStream_t)stream, *p, saved, ga, m, dh_dec, row_base);
+            hipLaunchKernelGGL(dec_bwd, dim3(grid), dim3(TPB), lds_dec, (hipStream_t)stream, *p, saved, ga, m, dh_dec, row_base);
         }, "dec_bwd")) return rc;
     float* dz0 = latent && latent->dlstates0 ? workspace + (size_t)m * (5 * sl + n) : nullptr;
     if (latent)
@@ -3728,9 +3766,7 @@ static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const C
                                dh_dec, dh_all, dc_all, b, dg_all, dh0, dc0);
         }, "cell_bwd");
     };
-    if (int rc = chain_threads == TPB ? launch_cell_bwd(cell_bwd_kernel<TPB>)
-                                      : (chain_threads == 2 * TPB ? launch_cell_bwd(cell_bwd_kernel<2 * TPB>)
-                                                                  : launch_cell_bwd(cell_bwd_kernel<4 * TPB>)))
+    if (int rc = with_chain_threads(chain_threads, [&](auto t) { return launch_cell_bwd(cell_bwd_kernel<decltype(t)::value>); }))
         return rc;
     if (dz0)   // cell_bwd has WRITTEN dlstates_t[0] (the hidden input of the first, teacher-forced step): add z_{-1}'s share
         if (int rc = launch_checked([&] {
@@ -3738,8 +3774,8 @@ static int chunks_backward_impl(void* stream, const sur_chunk_params* p, const C
                                    latent->dlstates0, dz0, b * sl);
             }, "latent_dz0")) return rc;
     return launch_checked([&] {
-        if (wg_gl) hipLaunchKernelGGL(cell_wgrad_kernel<true>, dim3(grid), dim3(TPB), lds_wg, (hipStream_t)stream, *p, spans, xlat_t, h_all, dg_all, k_total, b, dxlat_t, row_base);
-        else hipLaunchKernelGGL(cell_wgrad_kernel<false>, dim3(grid), dim3(TPB), lds_wg, (hipStream_t)stream, *p, spans, xlat_t, h_all, dg_all, k_total, b, dxlat_t, row_base);
+        hipLaunchKernelGGL(cell_wgrad, dim3(grid), dim3(TPB), lds_wg, (hipStream_t)stream, *p, spans, xlat_t, h_all, dg_all, k_total, b,
+                           dxlat_t, row_base);
     }, "cell_wgrad");
 }
 
@@ -3793,43 +3829,23 @@ int sur_chunks_backward(void* stream, const sur_chunk_params* p, int nspans, con
 }
 
 int sur_flush_chunk_grads(void* stream, const sur_chunk_params* p, const sur_adam* adam, int overwrite) {
-    if (!p || !p->partial) return fail(-1, "sur_flush_chunk_grads: bad argument");
-    for (int i = 0; i < SUR_ST_NPARAM; ++i)
-        if (!p->g[i]) return fail(-1, "sur_flush_chunk_grads: gradient tensor %d is NULL", i);
-    const int psize = psize_of<SUR_ST_NPARAM>(p->size);
-    sur_adam ad{};
-    if (adam) {
-        if (!adam->m || !adam->v || !adam->step || !adam->ticket || !adam->lr)
-            return fail(-1, "flush: incomplete Adam descriptor");
-        for (int i = 0; i < SUR_ST_NPARAM; ++i)   // the Adam branch updates the weights in place
-            if (!p->w[i]) return fail(-1, "sur_flush_chunk_grads: weight tensor %d is NULL", i);
-        ad = *adam;
-    }
-    return launch_checked([&] {
-        hipLaunchKernelGGL((flush_grads_kernel<SUR_ST_NPARAM, sur_chunk_params>), dim3(flush_blocks(psize)), dim3(FLUSH_TPB), 0,
-                           (hipStream_t)stream, *p, psize, ad, overwrite);
-    }, "flush_chunk");
+    return flush_pack<SUR_ST_NPARAM>(stream, p, adam, overwrite, "sur_flush_chunk_grads", "flush_chunk");
 }
 
 int sur_flush_all_grads(void* stream, const sur_encoder_params* e0, const sur_adam* a0, const sur_encoder_params* e1,
                         const sur_adam* a1, const sur_chunk_params* c2, const sur_adam* a2, int overwrite_mask) {
     if (!e0 || !e1 || !c2 || !e0->partial || !e1->partial || !c2->partial) return fail(-1, "sur_flush_all_grads: bad argument");
-    for (int i = 0; i < SUR_ENC_NPARAM; ++i)
-        if (!e0->g[i] || !e1->g[i]) return fail(-1, "sur_flush_all_grads: encoder gradient tensor %d is NULL", i);
-    for (int i = 0; i < SUR_ST_NPARAM; ++i)
-        if (!c2->g[i]) return fail(-1, "sur_flush_all_grads: chunk gradient tensor %d is NULL", i);
     const sur_adam* in[3] = {a0, a1, a2};
     sur_adam ad[3] = {};
     for (int j = 0; j < 3; ++j)
         if (in[j]) {
-            if (!in[j]->m || !in[j]->v || !in[j]->step || !in[j]->ticket || !in[j]->lr)
-                return fail(-1, "sur_flush_all_grads: incomplete Adam descriptor %d", j);
+            if (!adam_complete(*in[j])) return fail(-1, "sur_flush_all_grads: incomplete Adam descriptor %d", j);
             ad[j] = *in[j];
         }
-    for (int i = 0; i < SUR_ENC_NPARAM; ++i)   // the Adam branch updates the weights in place
-        if ((a0 && !e0->w[i]) || (a1 && !e1->w[i])) return fail(-1, "sur_flush_all_grads: encoder weight tensor %d is NULL", i);
-    for (int i = 0; i < SUR_ST_NPARAM; ++i)
-        if (a2 && !c2->w[i]) return fail(-1, "sur_flush_all_grads: chunk weight tensor %d is NULL", i);
+    const char* who = "sur_flush_all_grads";     // the Adam branch updates the weights in place
+    if (int rc = check_pack_tensors<SUR_ENC_NPARAM>(who, "encoder ", *e0, a0 != nullptr)) return rc;
+    if (int rc = check_pack_tensors<SUR_ENC_NPARAM>(who, "encoder ", *e1, a1 != nullptr)) return rc;
+    if (int rc = check_pack_tensors<SUR_ST_NPARAM>(who, "chunk ", *c2, a2 != nullptr)) return rc;
     const int n0 = psize_of<SUR_ENC_NPARAM>(e0->size), n1 = psize_of<SUR_ENC_NPARAM>(e1->size), n2 = psize_of<SUR_ST_NPARAM>(c2->size);
     const int grid = flush_blocks(n0) + flush_blocks(n1) + flush_blocks(n2);
     return launch_checked([&] {
@@ -3866,37 +3882,26 @@ int sur_adam_apply(void* stream, const sur_encoder_params* e0, const sur_adam* a
     sur_adam ad[3] = {};
     for (int j = 0; j < 3; ++j)
         if (in[j]) {
-            if (!in[j]->m || !in[j]->v || !in[j]->step || !in[j]->ticket || !in[j]->lr)
-                return fail(-1, "sur_adam_apply: incomplete Adam descriptor %d", j);
+            if (!adam_complete(*in[j])) return fail(-1, "sur_adam_apply: incomplete Adam descriptor %d", j);
             ad[j] = *in[j];
         }
     if ((a0 && !e0) || (a1 && !e1) || (a2 && !c2)) return fail(-1, "sur_adam_apply: descriptor without its parameter pack");
     sur_encoder_params pe0{}, pe1{};
     sur_chunk_params pc2{};
     int n0 = 0, n1 = 0, n2 = 0;
-    if (a0) {
-        pe0 = *e0;
-        n0 = psize_of<SUR_ENC_NPARAM>(e0->size);
-        for (int i = 0; i < SUR_ENC_NPARAM; ++i)
-            if (!e0->g[i] || !e0->w[i]) return fail(-1, "sur_adam_apply: encoder 0 tensor %d is NULL", i);
-    }
-    if (a1) {
-        pe1 = *e1;
-        n1 = psize_of<SUR_ENC_NPARAM>(e1->size);
-        for (int i = 0; i < SUR_ENC_NPARAM; ++i)
-            if (!e1->g[i] || !e1->w[i]) return fail(-1, "sur_adam_apply: encoder 1 tensor %d is NULL", i);
-    }
-    if (a2) {
-        pc2 = *c2;
-        n2 = psize_of<SUR_ST_NPARAM>(c2->size);
-        for (int i = 0; i < SUR_ST_NPARAM; ++i)
-            if (!c2->g[i] || !c2->w[i]) return fail(-1, "sur_adam_apply: chunk tensor %d is NULL", i);
-    }
+    if (int rc = adam_pack<SUR_ENC_NPARAM>(e0, a0, "encoder 0 ", pe0, n0)) return rc;
+    if (int rc = adam_pack<SUR_ENC_NPARAM>(e1, a1, "encoder 1 ", pe1, n1)) return rc;
+    if (int rc = adam_pack<SUR_ST_NPARAM>(c2, a2, "chunk ", pc2, n2)) return rc;
     const int grid = (n0 + TPB - 1) / TPB + (n1 + TPB - 1) / TPB + (n2 + TPB - 1) / TPB;
     if (grid == 0) return 0;
     return launch_checked([&] {
         hipLaunchKernelGGL(adam_all_kernel, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, pe0, ad[0], n0, pe1, ad[1], n1, pc2, ad[2], n2);
     }, "adam_all");
+}
+
+static int loss_nsplit(int b, int n) {
+    const int nsplit = (b * n + LOSS_UNROLL * TPB - 1) / (LOSS_UNROLL * TPB);
+    return nsplit < 1 ? 1 : (nsplit > LOSS_MAX_SPLIT ? LOSS_MAX_SPLIT : nsplit);
 }
 
 static int delta_loss_launch(void* stream, const float* states, long states_bstride, long states_tstride, const float* d_all, int b,
@@ -3908,18 +3913,12 @@ static int delta_loss_launch(void* stream, const float* states, long states_bstr
     if (t_begin < 0 || t_end > t || t_begin >= t_end) return fail(-1, "%s: time range [%d, %d) outside [0, %d)", who, t_begin, t_end, t);
     if (states_bstride < n || states_tstride < n) return fail(-1, "%s: state strides must be at least N", who);
     if (!(delta != 0.0f) || !(stdv > 0.0f)) return fail(-1, "%s: delta must be non-zero and std positive", who);
-    int nsplit = (b * n + LOSS_UNROLL * TPB - 1) / (LOSS_UNROLL * TPB);
-    nsplit = nsplit < 1 ? 1 : (nsplit > LOSS_MAX_SPLIT ? LOSS_MAX_SPLIT : nsplit);
+    const int nsplit = loss_nsplit(b, n);
     return launch_checked([&] {
         hipLaunchKernelGGL(delta_loss_kernel, dim3(t_end - t_begin, nsplit), dim3(TPB), 0, (hipStream_t)stream, states, states_bstride,
                            states_tstride, d_all, b, t, n, delta, mean,
                            stdv, deltas, dd_all, hsteploss, loss, stats, partial, ticket, t_begin, take_ticket);
     }, "delta_loss");
-}
-
-static int loss_nsplit(int b, int n) {
-    const int nsplit = (b * n + LOSS_UNROLL * TPB - 1) / (LOSS_UNROLL * TPB);
-    return nsplit < 1 ? 1 : (nsplit > LOSS_MAX_SPLIT ? LOSS_MAX_SPLIT : nsplit);
 }
 
 int sur_tbptt_delta_loss(void* stream, const float* states, long states_bstride, long states_tstride, const float* d_all, int b,

@@ -312,16 +312,16 @@ def test_adam_apply_skips_a_pack_without_a_descriptor():
     assert int(states[0].step) == 3 and int(states[1].step) == 2 and int(states[2].step) == 1
 
 
-def test_adam_spellings_from_equal_inputs_are_recorded():
-    """sur_adam_apply and the flush spelling from the same parameters, moments and (the flush's own) gradient, three
-    updates.  The source calls them the same arithmetic; under the compiler's default contraction the two sites may fuse
-    differently, so the outcome is recorded (bit-equal or the largest difference in units), not asserted."""
+def test_adam_apply_and_flush_agree_bit_for_bit_from_equal_inputs():
+    """sur_adam_apply and the flush from the same parameters, moments and (the flush's own) gradient, three updates.  Both
+    launches run the one adam_update of sur_kernels.hip, so p', m' and v' agree bit for bit on every update; the outcome
+    (and, should they ever part, the largest difference in units) is recorded as well."""
     names = ("wide", "odd", "tiny")
     a, b = _packs(names, [FLUSH_ROWS] * 3), _packs(names, [FLUSH_ROWS] * 3)
     sa = [so.AdamState(p, device=DEV, **h) for p, h in zip(a, HYPER)]
     sb = [so.AdamState(p, device=DEV, **h) for p, h in zip(b, HYPER)]
     rs = np.random.RandomState(21)
-    equal, apart = True, 0.0
+    equal, apart, parted = True, 0.0, []
     for t in (1, 2, 3):
         for p, q, s, r in zip(a, b, sa, sb):
             w0, g = so.parameter_classes(rs, p.psize), so.gradient_classes(rs, p.psize)
@@ -338,13 +338,16 @@ def test_adam_spellings_from_equal_inputs_are_recorded():
         for p, q, s, r in zip(a, b, sa, sb):
             assert int(s.step) == int(r.step) == t
             pairs = [(_host(p.get(p.wflat)), _host(q.get(q.wflat))), (_host(s.m), _host(r.m)), (_host(s.v), _host(r.v))]
-            for x, y in pairs:
+            for (x, y), what in zip(pairs, ("p'", "m'", "v'")):
                 assert not (np.isnan(x).any() or np.isnan(y).any())
-                equal = equal and np.array_equal(so.bits(x), so.bits(y))
+                same = np.array_equal(so.bits(x), so.bits(y))
+                equal = equal and same
+                parted.extend([] if same else [(t, what, p.psize)])
                 scale = np.maximum(np.abs(x), np.abs(y)).astype(np.float64)
                 diff = np.abs(x.astype(np.float64) - y)
                 apart = max(apart, float(np.max(np.where(scale > 0, diff / np.where(scale > 0, scale * so.U, 1.0), 0.0))))
     so.record(case="adam-apply-vs-flush-equal-inputs", bit_equal=bool(equal), worst_difference_in_u_of_the_value=apart)
+    assert equal and not parted, (parted, apart)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
