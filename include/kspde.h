@@ -189,6 +189,49 @@ int ks_record_device(ks_handle* h, const float* d_traj /* [T+1][E][N] */, const 
                      const double* d_ssq /* [T][E] */, const int* d_steps /* [T][E] */, int T, long n_substeps,
                      const long* d_dst /* [T][E] */, const long* dst_host, const ks_record* out);
 
+/* ---- surrogate test phase -------------------------------------------------------------------- */
+
+/* Replaces: the metric section of PDETrainingModule.test_step (pdecontrol/surrogates/training.py:195-243) for a batch of
+ * B sequences of T steps -- 2 * B * T reward_func calls, 2 * B * T env.rhs calls and some forty torch reductions -- by
+ * two launches.  Both follow ks_reward_rows_device: the handle's N and dx, not its state; enqueued on the handle's
+ * stream; on the CPU twin host pointers, synchronous, plain C++.  Every argument error is refused on the host before
+ * any HIP call, with a message that starts with the function's name. */
+#define KS_EVAL_ROW_STATS 18
+#define KS_EVAL_TABLES    25          /* per-time-step tables; + 1 scalar (MSE) */
+
+typedef struct ks_eval_batch {
+    const float* truth;  long truth_bstride, truth_tstride;   /* [B][T][N] through element strides            */
+    const float* pred;   long pred_bstride,  pred_tstride;    /* prediction rows, batch- or time-major         */
+    int pred_shift;      /* 1: predicted row of (b, 0) is truth (b, 0), of (b, t >= 1) is pred (b, t-1)       */
+    const float* phi;    /* [B][T][N] contiguous fp32 forcing field, or NULL (read under dissipation only)    */
+    int inv_kind;        /* 0 identity; 1 four-step affine, coef [4][N] = (a, b-a, d-c, c); 2 mul-add [2][N]  */
+    const float* inv_coef;
+    float* truth_out;    /* [B][T][N] contiguous: the inverse-scaled rows as the metrics read them, or NULL   */
+    float* pred_out;
+} ks_eval_batch;
+
+/* Per (b, t) row, with s the truth row and o the predicted row after stransf.otransf.Inverse (inv_kind, in separately
+ * rounded fp32 steps: kind 1 ScaleTransform._affine, kind 2 Normalize._inv with coef = (sqrt(var + epsilon), mean)) and
+ * e_i = (float)(o_i - s_i), 18 fp64 values (sums in fp64):
+ *   0-3    sum|e|, sum e^2, sum|s|, sum s^2
+ *   4, 5   the reward of s and of o as ks_reward_rows_device forms it (phi enters both under KS_OBJECTIVE_DISSIPATION and
+ *          is not read under KS_OBJECTIVE_L2CONTROL, where the reward is rounded to fp32, the reference's precision there)
+ *   6-17   for u_x, u_xx, u_xxxx of the fp64-cast rows (reference operation order, ds of s, do of o):
+ *          sum|ds - do|, sum (ds - do)^2, sum|ds|, sum ds^2
+ * With pred_shift = 1 both sides of step 0 read the same value through the same map: its error sums are exactly 0. */
+int ks_eval_rows_device(ks_handle* h, int objective, const ks_eval_batch* in, int B, int T, double* rowstats /* [B][T][18] */);
+
+/* tables[0] = MSE = sum_{b,t} sum e^2 / (B T N); tables[1 + k T + t] = table k at step t, k in the order of the dict
+ * test_step returns: l1_loss, l2_loss, l1_loss_scaled, l2_loss_scaled, nrmse (means over b of sum|e|, sqrt(sum e^2),
+ * sum|e| / sum|s|, sqrt(sum e^2) / sqrt(sum s^2), sum e^2 / sum s^2); the five *_rews (norms over the batch: sum_b|r - r^|,
+ * sqrt(sum_b (r - r^)^2), their ratios to sum_b|r| and sqrt(sum_b r^2), sum_b (r - r^)^2 / sum_b r^2); then the five
+ * row-mean tables of each derivative as l1_loss_derivs-derivative-0, -1, -2, l2_loss_derivs-..., l1_loss_scaled_derivs-...,
+ * l2_loss_scaled_derivs-..., nrms_derivs-....  One thread per value, b in index order, fp64; a zero norm divides to
+ * IEEE inf / NaN as in the reference.  accum (same shape, or NULL): accum[i] += B * tables[i] by the same thread, so the
+ * batches of an epoch on one stream sum deterministically. */
+int ks_eval_fold_device(ks_handle* h, const double* rowstats, int B, int T,
+                        double* tables /* [1 + 25*T] */, double* accum /* same shape: += B * value; or NULL */);
+
 /* ---- test hooks -------------------------------------------------------------------------- */
 
 /* Replaces: KuramotoSivashinskyEnv.rhs (kuramoto.py:118-129) on a batch, in the reference's

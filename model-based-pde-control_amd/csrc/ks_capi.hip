@@ -15,6 +15,7 @@
 #include "../../include/kspde.h"
 #include "capi_error.h"
 #include "ks_cpu.h"
+#include "ks_eval.h"
 #include "ks_internal.h"
 
 namespace {
@@ -690,6 +691,69 @@ int ks_record_device(ks_handle* h, const float* d_traj, const float* d_actions, 
     DeviceGuard g(h->device);
     const hipError_t e = ks::launch_record(a, h->stream);
     if (e != hipSuccess) return fail(KS_ERR_HIP, "ks_record_device: launch failed: %s", hipGetErrorString(e));
+    return KS_OK;
+}
+
+static_assert(KS_EVAL_ROW_STATS == ks::EVAL_ROW_STATS && KS_EVAL_TABLES == ks::EVAL_TABLES, "kspde.h and ks_eval.h disagree");
+
+int ks_eval_rows_device(ks_handle* h, int objective, const ks_eval_batch* in, int B, int T, double* rowstats) {
+    // everything is refused here, before any HIP call
+    if (!h) return fail(KS_ERR_INVALID, "ks_eval_rows_device: NULL handle");
+    if (!in || !rowstats) return fail(KS_ERR_INVALID, "ks_eval_rows_device: NULL batch or rowstats");
+    if (objective != KS_OBJECTIVE_L2CONTROL && objective != KS_OBJECTIVE_DISSIPATION)
+        return fail(KS_ERR_INVALID, "ks_eval_rows_device: unknown objective %d", objective);
+    if (B < 1 || T < 1) return fail(KS_ERR_INVALID, "ks_eval_rows_device: B = %d, T = %d (at least 1 each)", B, T);
+    if (!in->truth || !in->pred) return fail(KS_ERR_INVALID, "ks_eval_rows_device: NULL truth or pred");
+    if (in->inv_kind < 0 || in->inv_kind > 2)
+        return fail(KS_ERR_INVALID, "ks_eval_rows_device: unknown inv_kind %d (0, 1 or 2)", in->inv_kind);
+    if (in->inv_kind != 0 && !in->inv_coef)
+        return fail(KS_ERR_INVALID, "ks_eval_rows_device: inv_kind %d without coefficients", in->inv_kind);
+    if (in->pred_shift != 0 && in->pred_shift != 1)
+        return fail(KS_ERR_INVALID, "ks_eval_rows_device: pred_shift %d (0 or 1)", in->pred_shift);
+    const long strides[4] = {in->truth_bstride, in->truth_tstride, in->pred_bstride, in->pred_tstride};
+    for (long s : strides)
+        if (s < h->N) return fail(KS_ERR_INVALID, "ks_eval_rows_device: a stride of %ld elements is smaller than a row of %d", s, h->N);
+    if ((size_t)B * (size_t)T * (size_t)h->N > (size_t)1 << 31) return fail(KS_ERR_INVALID, "ks_eval_rows_device: B * T * N too large");
+    ks::EvalArgs a = {};
+    a.truth = in->truth;
+    a.truth_bs = in->truth_bstride;
+    a.truth_ts = in->truth_tstride;
+    a.pred = in->pred;
+    a.pred_bs = in->pred_bstride;
+    a.pred_ts = in->pred_tstride;
+    a.pred_shift = in->pred_shift;
+    a.phi = in->phi;
+    a.inv_kind = in->inv_kind;
+    a.inv_coef = in->inv_coef;
+    a.truth_out = in->truth_out;
+    a.pred_out = in->pred_out;
+    a.B = B;
+    a.T = T;
+    a.N = h->N;
+    a.rowstats = rowstats;
+    a.k = consts_of(h);
+    if (h->cpu) {
+        kscpu::eval_rows(objective, a);
+        return KS_OK;
+    }
+    DeviceGuard g(h->device);
+    const hipError_t e = ks::launch_eval_rows(objective, a, h->stream);
+    if (e != hipSuccess) return fail(KS_ERR_HIP, "ks_eval_rows_device: launch failed: %s", hipGetErrorString(e));
+    return KS_OK;
+}
+
+int ks_eval_fold_device(ks_handle* h, const double* rowstats, int B, int T, double* tables, double* accum) {
+    if (!h) return fail(KS_ERR_INVALID, "ks_eval_fold_device: NULL handle");
+    if (!rowstats || !tables) return fail(KS_ERR_INVALID, "ks_eval_fold_device: NULL rowstats or tables");
+    if (B < 1 || T < 1) return fail(KS_ERR_INVALID, "ks_eval_fold_device: B = %d, T = %d (at least 1 each)", B, T);
+    if ((size_t)B * (size_t)T * (size_t)h->N > (size_t)1 << 31) return fail(KS_ERR_INVALID, "ks_eval_fold_device: B * T * N too large");
+    if (h->cpu) {
+        kscpu::eval_fold(rowstats, B, T, h->N, tables, accum);
+        return KS_OK;
+    }
+    DeviceGuard g(h->device);
+    const hipError_t e = ks::launch_eval_fold(rowstats, B, T, h->N, tables, accum, h->stream);
+    if (e != hipSuccess) return fail(KS_ERR_HIP, "ks_eval_fold_device: launch failed: %s", hipGetErrorString(e));
     return KS_OK;
 }
 

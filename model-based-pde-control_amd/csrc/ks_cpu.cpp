@@ -243,4 +243,22 @@ void record(int E, int N, int A, long n, const float* traj, const float* actions
     }
 }
 
+void eval_rows(int objective, const ks::EvalArgs& a) {
+    ks::with_flags(true, objective == 1, [&](auto, auto dissipation) {
+        constexpr bool DISS = decltype(dissipation)::value;
+        for (long row = 0; row < (long)a.B * a.T; ++row) {
+            ks::EvalSums sums = {};
+            ks::eval_row_share<ks::DivIeee, DISS>(a, row, 0, 1, sums);
+            ks::eval_row_finish<DISS>(sums, a.N, a.rowstats + row * ks::EVAL_ROW_STATS);
+        }
+    });
+}
+
+void eval_fold(const double* rowstats, int B, int T, int N, double* tables, double* accum) {
+    for (int i = 0; i < 1 + ks::EVAL_TABLES * T; ++i) {
+        tables[i] = ks::eval_fold_value(rowstats, B, T, N, i);
+        if (accum) accum[i] += (double)B * tables[i];
+    }
+}
+
 }  // namespace kscpu

@@ -9,6 +9,7 @@
 #pragma once
 #include <cstddef>
 
+#include "ks_eval.h"
 #include "ks_internal.h"
 
 namespace kscpu {
@@ -36,6 +37,11 @@ void reward_rows(int N, const Consts& c, int objective, const float* obs, const 
 void record(int E, int N, int A, long n, const float* traj, const float* actions, const double* ssq, const int* steps,
             const long* dst, double scale, double substeps, float* obs, float* act, float* nxtobs, float* rewards,
             unsigned char* terminated, unsigned char* truncated, int* out_steps);
+
+// ks_eval_rows_device / ks_eval_fold_device on host memory: the arithmetic of ks_eval.h (eval_row_share,
+// eval_row_finish, eval_fold_value) row by row and value by value, with the true division.
+void eval_rows(int objective, const ks::EvalArgs& a);
+void eval_fold(const double* rowstats, int B, int T, int N, double* tables, double* accum);
 
 // Host threads the twin uses by default: the affinity mask, capped by KSPDE_CPU_THREADS.
 int default_threads();

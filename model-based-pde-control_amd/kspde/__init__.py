@@ -35,6 +35,23 @@ class ks_record(_c.Structure):
                 ("terminated", _c.c_void_p), ("truncated", _c.c_void_p), ("steps", _c.c_void_p), ("rows", _c.c_long)]
 
 
+class ks_eval_batch(_c.Structure):
+    """``ks_eval_batch``: truth and prediction rows through element strides, the forcing field, the inverse observation
+    map and the optional inverse-scaled outputs of ``ks_eval_rows_device``."""
+    _fields_ = [("truth", _c.c_void_p), ("truth_bstride", _c.c_long), ("truth_tstride", _c.c_long),
+                ("pred", _c.c_void_p), ("pred_bstride", _c.c_long), ("pred_tstride", _c.c_long),
+                ("pred_shift", _c.c_int), ("phi", _c.c_void_p), ("inv_kind", _c.c_int), ("inv_coef", _c.c_void_p),
+                ("truth_out", _c.c_void_p), ("pred_out", _c.c_void_p)]
+
+
+EVAL_ROW_STATS = 18      # KS_EVAL_ROW_STATS
+EVAL_TABLES = 25         # KS_EVAL_TABLES
+# the names of the per-step tables of ks_eval_fold_device, in its order: the keys of the dict test_step returns
+EVAL_TABLE_NAMES = (("l1_loss", "l2_loss", "l1_loss_scaled", "l2_loss_scaled", "nrmse")
+                    + ("l1_loss_rews", "l2_loss_rews", "l1_loss_scaled_rews", "l2_loss_scaled_rews", "nrmse_rews")
+                    + tuple(f"{name}-derivative-{d}" for name in ("l1_loss_derivs", "l2_loss_derivs", "l1_loss_scaled_derivs",
+                                                                  "l2_loss_scaled_derivs", "nrms_derivs") for d in range(3)))
+
 SYMBOLS = (
     ("ks_create", _c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.POINTER(_H)]),
     ("ks_destroy", _c.c_int, [_H]),
@@ -60,6 +77,8 @@ SYMBOLS = (
     ("ks_reward_rows_device", _c.c_int, [_H, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     ("ks_record_device", _c.c_int, [_H, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_long,
                                     _c.c_void_p, _c.c_void_p, _c.POINTER(ks_record)]),
+    ("ks_eval_rows_device", _c.c_int, [_H, _c.c_int, _c.POINTER(ks_eval_batch), _c.c_int, _c.c_int, _c.c_void_p]),
+    ("ks_eval_fold_device", _c.c_int, [_H, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("ks_rhs", _c.c_int, [_H, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                           _c.c_void_p]),
     ("ks_selftest", _c.c_int, [_H, _c.POINTER(_c.c_uint)]),
@@ -252,6 +271,21 @@ class KSStepper:
         _check(self._lib.ks_record_device(self._h, vp(d_traj), vp(d_actions), int(A), vp(d_ssq), vp(d_steps), int(T),
                                           int(n_substeps), vp(d_dst), _ptr(dst_host),
                                           None if slabs is None else ctypes.byref(slabs)))
+
+    def eval_rows_device(self, objective, batch, B, T, d_rowstats):
+        """The 18 fp64 sums of every (b, t) row of a test batch (``batch`` a ``ks_eval_batch`` of raw device pointers;
+        host pointers on the CPU twin) into ``d_rowstats`` [B, T, 18]; see ks_eval_rows_device.  Enqueued on the
+        handle's stream."""
+        if objective not in OBJECTIVE:
+            raise ValueError(f"objective must be one of {sorted(OBJECTIVE)}, not {objective!r}")
+        _check(self._lib.ks_eval_rows_device(self._h, OBJECTIVE[objective], None if batch is None else ctypes.byref(batch),
+                                             int(B), int(T), ctypes.c_void_p(int(d_rowstats)) if d_rowstats else None))
+
+    def eval_fold_device(self, d_rowstats, B, T, d_tables, d_accum=0):
+        """``d_rowstats`` [B, T, 18] folded into the MSE and the 25 per-step tables, ``d_tables`` [1 + 25 T], and
+        ``d_accum`` (same shape, 0 = NULL) += B * tables; see ks_eval_fold_device.  Enqueued on the handle's stream."""
+        vp = lambda x: ctypes.c_void_p(int(x)) if x else None
+        _check(self._lib.ks_eval_fold_device(self._h, vp(d_rowstats), int(B), int(T), vp(d_tables), vp(d_accum)))
 
     def sync(self):
         _check(self._lib.ks_sync(self._h))

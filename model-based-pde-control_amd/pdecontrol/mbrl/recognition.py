@@ -101,6 +101,57 @@ def field_map(chain, width):
     return FieldMap(start, stride, width, None if coef is None else coef.contiguous())
 
 
+# ---- inverse observation chains (the surrogate test phase) ------------------------------------------------------------
+def _leaves(t):
+    """The transforms of a chain in application order, ``Operation``s and ``BatchTransform``s opened up."""
+    if isinstance(t, (tr.BatchTransform, tr._BatchInverse)):
+        return _leaves(t.transform)
+    steps = _steps(t)
+    return steps if len(steps) == 1 and steps[0] is t else [leaf for step in steps for leaf in _leaves(step)]
+
+
+def _statistic(stat, width, what):
+    if stat is None:
+        raise Unrecognized(f"a Normalize without a fitted {what}")
+    stat = torch.as_tensor(stat).detach().cpu()
+    if stat.dtype != torch.float32:
+        raise Unrecognized(f"a Normalize with its {what} in {str(stat.dtype).replace('torch.', '')}")
+    if stat.numel() == 1:
+        return stat.reshape(1).expand(width)
+    if stat.shape[-1] == width and stat.numel() == width:
+        return stat.reshape(width)
+    raise Unrecognized(f"a Normalize whose {what} of shape {tuple(stat.shape)} is not one value or one per column")
+
+
+def inverse_map(chain, width):
+    """``(kind, coef)`` of an inverse observation chain (``stransf.otransf.Inverse``) over rows of ``width`` columns, as
+    ``ks_eval_rows_device`` takes it: identity sensors and at most one scaling.  Kind 0 is the identity (``coef`` None);
+    kind 1 a ``ScaleTransform`` in either direction, ``coef`` [4, width] = (a, b - a, d - c, c) as in ``FieldMap``; kind 2
+    the inverse of a ``Normalize`` with scalar or per-column statistics, ``coef`` [2, width] = (sqrt(var + epsilon), mean),
+    the square root taken in fp32 torch as ``Normalize._inv`` takes it.  Raises ``Unrecognized``."""
+    kind, coef = 0, None
+    for leaf in _leaves(chain):
+        inverse = type(leaf) is tr._InverseView
+        inner = leaf.transf if inverse else leaf
+        if inner is None or isinstance(inner, tr.Identity):
+            continue
+        if isinstance(inner, tr.SensorTransform):
+            if int(inner.stride) != 1:
+                raise Unrecognized(f"a SensorTransform of stride {inner.stride}")
+            continue
+        if kind:
+            raise Unrecognized("two scalings in a row")
+        if type(inner) is tr.ScaleTransform:
+            kind, coef = 1, field_map(leaf, width).coef
+        elif type(inner) is tr.Normalize and inverse:
+            scale = None if inner.var is None else torch.sqrt(torch.as_tensor(inner.var).detach().cpu() + inner.epsilon)
+            kind = 2
+            coef = torch.stack([_statistic(scale, width, "variance"), _statistic(inner.mean, width, "mean")]).contiguous()
+        else:
+            raise Unrecognized(f"a {type(inner).__name__}" if not inverse else f"the inverse of a {type(inner).__name__}")
+    return kind, coef
+
+
 # ---- what both stack recognisers check -------------------------------------------------------------------------------
 def is_forcing(t):
     if isinstance(t, tr.BatchTransform):

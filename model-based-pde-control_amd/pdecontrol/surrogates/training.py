@@ -388,9 +388,105 @@ class PDETrainingModule(pl.LightningModule):
                 "actions": actions.detach(), "states": states.detach(), "outdeltas": outdeltas.detach(),
                 "deltas": deltas.detach()}
 
+    # -- test: the metric section on the device (ks_eval_rows_device / ks_eval_fold_device) -------------------
+    def _test_kernel_plan(self, states, out):
+        """(kind, device coefficients or None) of ``stransf.otransf.Inverse`` when the metric section of ``test_step``
+        runs as the two HIP launches; otherwise None, with a one-time notice that says why."""
+        from pdecontrol.mbrl.recognition import Unrecognized, inverse_map, notice
+        from pdecontrol.surrogates import ops
+        from pdegym.kuramoto import KuramotoSivashinskyEnv
+        sentence = "test_step computes its metrics with torch on the host: %s"
+        if not states.is_cuda:
+            notice(sentence, "the batch is in host memory", expected=True)
+            return None
+        if not ops.fused_enabled():
+            notice(sentence, "the fused kernels are switched off", expected=True)
+            return None
+        if states.dtype != torch.float32 or states.dim() != 4 or states.shape[2] != 1:
+            notice(sentence, f"states of shape {tuple(states.shape)} in {states.dtype} are not fp32 [B, T, 1, N]")
+            return None
+        if not isinstance(self.env, KuramotoSivashinskyEnv) or self.env.N != states.shape[3]:
+            notice(sentence, f"the env is no KuramotoSivashinskyEnv on the states' grid of {states.shape[3]} points")
+            return None
+        pred = out.outputs
+        if pred.dtype != torch.float32 or not pred.is_cuda or tuple(pred.shape) != tuple(states.shape):
+            notice(sentence, f"the rollout returned {tuple(pred.shape)} in {pred.dtype} for states {tuple(states.shape)}")
+            return None
+        try:
+            kind, coef = inverse_map(self.stransf.otransf.Inverse, states.shape[3])
+        except (Unrecognized, NotImplementedError) as reason:
+            notice(sentence, f"the inverse observation transform is {reason}")
+            return None
+        if coef is None:
+            return kind, None
+        cached = self.__dict__.get("_test_inv_coef")
+        if cached is None or cached[0] != states.device or cached[1].shape != coef.shape or not torch.equal(cached[1], coef):
+            cached = self.__dict__["_test_inv_coef"] = (states.device, coef, coef.to(states.device))
+        return kind, cached[2]
+
+    @staticmethod
+    def _rows(field):
+        """``field`` [B, T, 1, N] as ks_eval_batch names it: (tensor, batch stride, time stride) with unit-stride rows
+        that do not overlap -- the tensor itself, batch- or time-major, or a contiguous copy."""
+        n = field.shape[3]
+        if field.stride(3) != 1 or field.stride(0) < n or field.stride(1) < n:
+            field = field.contiguous()
+        return field, field.stride(0), field.stride(1)
+
+    def _test_metrics_device(self, states, actions, out, plan, accum=None, keep=True):
+        """The metric section of ``test_step`` for one batch on the device: two launches on the env's reward handle
+        (torch's current stream).  Returns (tables fp64 [1 + 25 T], inverse-scaled states, IC-augmented inverse-scaled
+        outputs), the last two None without ``keep``; ``accum`` is the epoch accumulator of ``ks_eval_fold_device``."""
+        import kspde
+        kind, coef = plan
+        b, t, _, n = states.shape
+        dev = states.device
+        objective = self.env.step_objective
+        phi = None
+        if objective == "dissipation":
+            flat = actions.reshape(b * t, *actions.shape[2:])
+            phi = BatchTransform(self.env.forcing)(self.stransf.atransf.Inverse(flat))
+            phi = phi.to(torch.float32).reshape(b * t, n).contiguous()
+        truth, truth_bs, truth_ts = self._rows(states.detach())
+        pred, pred_bs, pred_ts = self._rows(out.outputs.detach())
+        truth_out = torch.empty((b, t, 1, n), dtype=torch.float32, device=dev) if keep else None
+        pred_out = torch.empty((b, t, 1, n), dtype=torch.float32, device=dev) if keep else None
+        rowstats = torch.empty((b, t, kspde.EVAL_ROW_STATS), dtype=torch.float64, device=dev)
+        tables = torch.empty(1 + kspde.EVAL_TABLES * t, dtype=torch.float64, device=dev)
+        ptr = lambda v: None if v is None else v.data_ptr()
+        # pred_shift: the prediction of step 0 is the initial condition, of step t >= 1 the rollout's output t - 1
+        desc = kspde.ks_eval_batch(ptr(truth), truth_bs, truth_ts, ptr(pred), pred_bs, pred_ts, 1, ptr(phi), kind, ptr(coef),
+                                   ptr(truth_out), ptr(pred_out))
+        handle = self.env._reward_handle(dev)
+        handle.eval_rows_device(objective, desc, b, t, rowstats.data_ptr())
+        handle.eval_fold_device(rowstats.data_ptr(), b, t, tables.data_ptr(), 0 if accum is None else accum.data_ptr())
+        return tables, truth_out, pred_out
+
+    @staticmethod
+    def _named_tables(values, steps):
+        """fp64 [1 + 25 T] host values of ``ks_eval_fold_device`` as the reference's keys."""
+        import kspde
+        named = {"MSE": values[0]}
+        for k, name in enumerate(kspde.EVAL_TABLE_NAMES):
+            named[name] = values[1 + k * steps:1 + (k + 1) * steps]
+        return named
+
     def test_step(self, batch, bidx):
         states, actions, *_ = batch
         out = self._full_rollout(states, actions)
+        plan = self._test_kernel_plan(states, out)
+        if plan is None:
+            self.last_test_tier = "torch"
+            return self._test_step_host(states, actions, out)
+        self.last_test_tier = "kernel"
+        tables, truth, pred = self._test_metrics_device(states, actions, out, plan)
+        named = self._named_tables(tables.cpu().numpy(), states.shape[1])
+        data = {name: np.asarray(value, dtype=np.float32) for name, value in named.items()}
+        data.update({"states": truth.cpu().numpy(), "outputs": pred.cpu().numpy(), "actions": actions.detach().cpu().numpy()})
+        return data
+
+    def _test_step_host(self, states, actions, out):
+        """The metric section of ``test_step`` in torch on the host, line for line the reference's."""
         outputs = torch.cat((states[:, :1], out.outputs[:, :-1]), dim=1)
         states = self.stransf.otransf.Inverse(states).detach().cpu()
         outputs = self.stransf.otransf.Inverse(outputs).detach().cpu()
