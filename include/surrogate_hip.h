@@ -317,6 +317,58 @@ int sur_gather_windows(void* stream, const sur_window_source* src, const long* f
                        int states_width, long states_bstride, long states_tstride, float* actions, int actions_width,
                        long actions_bstride, long actions_tstride);
 
+/* ---- the fully-connected LSTM baselines (KSAutoRegFullyConnectedLSTM, KSLatentLSTM): csrc/sur_fclstm.hip --------------------
+ * Whole-rollout kernels of the fixed network Linear 64 -> 32 -> 16, nn.LSTM(4, 16) on the 4 raw actuator values (gate order
+ * i, f, g, o, both biases added), Linear 16 -> 32 -> 64.  Parameters travel as ONE flat fp32 vector in the module's
+ * named_parameters() order WITHOUT the frozen H0 / C0 (sur_fc_param_count() = 6 672 floats): the caller expands those into
+ * h_in / c_in.
+ *
+ *   form  SUR_FC_AUTOREG  at a given step k < min(S, K): H = enc(states[k]) (C kept), out_k = states[k] + delta (mul dec(h') + add);
+ *                         afterwards H is the LSTM's own and out_k = out_{k-1} + delta (mul dec(h') + add).  inlatents (may
+ *                         be NULL: then the re-encoding of the predictions is skipped) is enc(states[k]), then the detached
+ *                         enc(out_{k-1}).
+ *         SUR_FC_LATENT   z_0 = enc(states[0]), z_{k+1} = z_k + delta h'_k, out_k = dec(z_{k+1}); H is replaced at the given
+ *                         steps as above; inlatents[k] is enc(states[k]), then z_k (it carries gradient).  deltas is not
+ *                         written (may be NULL); mul / add are not read.
+ *   act   SUR_FC_SILU_TANH     SiLU in the encoder and the decoder's first layer, Tanh after its last
+ *         SUR_FC_ELU_IDENTITY  ELU likewise, no activation after the last layer
+ *
+ *   sur_fc_forward   ONE launch: a wave per sample walks all K steps, weights staged in LDS once per workgroup.  `saved`
+ *                    (sur_fc_saved_floats(B, K) floats, or NULL when no backward follows) receives 256 floats per
+ *                    (sample, step).
+ *   sur_fc_backward  TWO launches: the reverse walk (gradients of states, actions, c_in; one workspace row of 304 floats
+ *                    per (sample, step)), then the weight gradients as sums of outer products in a fixed order (skipped
+ *                    when d_params is NULL).  No floating-point atomics: bit-identical from run to run.
+ *
+ * Layouts (contiguous fp32 DEVICE pointers): states [B][S][64]; actions [B][K][4], already mapped to the K internal steps;
+ * h, c [B][16]; outputs, deltas [B][K][64]; inlatents, outlatents [B][K][16].  h_in never reaches an output (the first
+ * step is always a given one), so it is not read and d_h_in receives zeros.  A NULL c_in is zero; a NULL gradient input is
+ * zero; a NULL gradient output is not written.  Everything is enqueued on `stream`: no host synchronisation, no device
+ * allocation; every argument is checked on the host before the first HIP call.  -1: a bad argument, -2: the launch
+ * failed, -4: a layout the kernels do not implement; the reason is in sur_last_error(). */
+enum { SUR_FC_AUTOREG = 0, SUR_FC_LATENT = 1 };
+enum { SUR_FC_SILU_TANH = 0, SUR_FC_ELU_IDENTITY = 1 };
+
+int sur_fc_param_count(void);
+
+/* 0 when the kernels implement this layout (pure host function) */
+int sur_fc_supported(int n, int enc_mid, int latent, int dec_mid, int actions, int form, int act, int nparams);
+
+/* floats of `saved` (256 B K) and of `work` (304 B K); 0 for a non-positive B or K */
+long sur_fc_saved_floats(int B, int K);
+long sur_fc_workspace_floats(int B, int K);
+
+int sur_fc_forward(void* stream, const float* params, int form, int act, int B, int S, int K, const float* states,
+                   const float* actions, const float* h_in, const float* c_in, float delta, float mul, float add,
+                   float* outputs, float* deltas, float* inlatents, float* outlatents, float* h_out, float* c_out,
+                   float* saved);
+
+int sur_fc_backward(void* stream, const float* params, int form, int act, int B, int S, int K, const float* states,
+                    const float* actions, const float* c_in, const float* saved, float delta, float mul,
+                    const float* d_outputs, const float* d_deltas, const float* d_inlatents, const float* d_outlatents,
+                    const float* d_h_out, const float* d_c_out, float* d_states, float* d_actions, float* d_h_in,
+                    float* d_c_in, float* d_params, float* work);
+
 const char* sur_last_error(void);
 
 #ifdef __cplusplus

@@ -101,6 +101,15 @@ SYMBOLS = (
                                 ctypes.c_long, ctypes.c_long]),
     ("sur_val_loss", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                           ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # the fully-connected LSTM baselines (csrc/sur_fclstm.hip; autograd node: pdecontrol/surrogates/fclstm_hip.py)
+    ("sur_fc_param_count", _i, []),
+    ("sur_fc_supported", _i, [_i] * 8),
+    ("sur_fc_saved_floats", ctypes.c_long, [_i, _i]),
+    ("sur_fc_workspace_floats", ctypes.c_long, [_i, _i]),
+    ("sur_fc_forward", _i, [_fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                            _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    ("sur_fc_backward", _i, [_fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp,
+                             _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     ("sur_last_error", ctypes.c_char_p, []),
 )
 _lib = None

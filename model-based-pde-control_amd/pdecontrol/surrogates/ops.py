@@ -12,6 +12,11 @@ never the other way round: a covered architecture cannot end up on torch kernels
 plain torch-on-GPU path also exists as an explicit opt-out (``enable_fused(False)``, the
 ``fused(False)`` context manager or ``PDECONTROL_FUSED=0``): it is the same-device cross-check of the
 parity tests and the "hipGraph over torch kernels" leg of the benchmark.
+
+The two fully-connected LSTM baselines (``KSAutoRegFullyConnectedLSTM``, ``KSLatentLSTM``) have whole-rollout kernels of
+their own (``fclstm_hip``, ``sur_fc_*``) behind a second, opt-in switch: ``enable_fused_fc(True)``, the ``fused_fc(True)``
+context manager or ``PDECONTROL_FUSED_FC=1``.  It is off by default -- then they run on PyTorch-ROCm kernels with the
+notice above, exactly as before -- and the opt-out above overrides it.
 """
 import logging
 import os
@@ -22,6 +27,8 @@ _LOG = logging.getLogger("pdecontrol.surrogates")
 _NOTIFIED = set()
 _DEFAULT = os.environ.get("PDECONTROL_FUSED", "1") != "0"
 _FUSED = {"enabled": _DEFAULT, "lib": None}
+_DEFAULT_FC = os.environ.get("PDECONTROL_FUSED_FC", "0") == "1"
+_FUSED_FC = {"enabled": _DEFAULT_FC}
 
 
 def enable_fused(flag=True):
@@ -33,8 +40,35 @@ def enable_fused(flag=True):
 
 
 def reset_fused():
-    """Back to the process default (fused unless PDECONTROL_FUSED=0)."""
+    """Back to the process defaults (fused unless PDECONTROL_FUSED=0; the FC-LSTM kernels off unless
+    PDECONTROL_FUSED_FC=1)."""
     _FUSED["enabled"] = _DEFAULT
+    _FUSED_FC["enabled"] = _DEFAULT_FC
+
+
+def enable_fused_fc(flag=True):
+    """Opt the fully-connected LSTM baselines in to (or out of) their whole-rollout kernels (``fclstm_hip``)."""
+    _FUSED_FC["enabled"] = bool(flag)
+
+
+def fused_fc_enabled():
+    return _FUSED_FC["enabled"]
+
+
+class fused_fc:
+    """``with ops.fused_fc(True): ...`` -- run a block with the FC-LSTM kernels switched on (or off) and restore the
+    previous choice."""
+
+    def __init__(self, flag):
+        self.flag = bool(flag)
+
+    def __enter__(self):
+        self.prev = _FUSED_FC["enabled"]
+        enable_fused_fc(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        _FUSED_FC["enabled"] = self.prev
 
 
 def fused_enabled():
@@ -71,6 +105,8 @@ def use_fused_for(surrogate, tensor):
     logged notice per class (it then runs on PyTorch-ROCm kernels, as in the reference)."""
     if is_delay(surrogate):
         return False   # its own kernels and its own notice: use_fused_delay_for
+    if _fc_layout(surrogate, tensor):
+        return False   # its own kernels and its own notice: use_fused_fc_for
     from pdecontrol.surrogates import hipops
     return _use_fused_layout(surrogate, tensor, hipops.fused_supported, "KSAutoRegConvolutionalLSTM")
 
@@ -96,8 +132,44 @@ def use_fused_latent_for(surrogate, tensor):
     """``use_fused_for`` of the latent-space rollout (LatentAutoRegPDESurrogate): True for the KSLatentConvolutionalLSTM
     layout at a supported grid width; any other latent architecture (KSLatentLSTM) runs on PyTorch-ROCm kernels, announced
     once per class."""
+    if _fc_layout(surrogate, tensor):
+        return False   # its own kernels and its own notice: use_fused_fc_for
     from pdecontrol.surrogates import hipops
     return _use_fused_layout(surrogate, tensor, hipops.fused_latent_supported, "KSLatentConvolutionalLSTM")
+
+
+def is_fc_lstm(surrogate):
+    """True for a surrogate around an LSTMTransitionModel (the two fully-connected baselines and their variants)."""
+    from pdecontrol.surrogates.transition import LSTMTransitionModel
+    return isinstance(getattr(surrogate, "transition_model", None), LSTMTransitionModel)
+
+
+def _fc_layout(surrogate, tensor):
+    """True when the FC-LSTM switch decides the path of ``surrogate`` on ``tensor``: the switch is on (and
+    ``PDECONTROL_FUSED`` / ``fused(False)`` does not override it), the tensor is on the GPU and the module tree is one of
+    the two factories'.  With the switch off this is False before it looks at anything."""
+    if not (_FUSED_FC["enabled"] and _FUSED["enabled"] and tensor.is_cuda and is_fc_lstm(surrogate)):
+        return False
+    from pdecontrol.surrogates import fclstm_hip
+    return fclstm_hip.fused_fc_supported(surrogate)
+
+
+def use_fused_fc_for(surrogate, tensor):
+    """True when the rollout of ``surrogate`` on ``tensor`` (the states) runs on the FC-LSTM kernels
+    (``fclstm_hip.fused_fc_rollout``): ``_fc_layout`` and a geometry the kernels take.  A supported tree they refuse for
+    this input (fp64, another width, an unknown dscaling) is announced once per reason and runs on PyTorch-ROCm kernels;
+    any other tree returns False silently (``use_fused_for`` / ``use_fused_latent_for`` announce it as before)."""
+    if not _fc_layout(surrogate, tensor):
+        return False
+    from pdecontrol.surrogates import fclstm_hip, hipops
+    hipops.load()           # raises when the library has not been built: no silent fallback
+    reason = fclstm_hip.geometry_unsupported(surrogate, tensor)
+    if reason is None:
+        return True
+    if reason not in _NOTIFIED:
+        _NOTIFIED.add(reason)
+        _LOG.warning("the FC-LSTM HIP kernels do not take this input (%s): it runs on plain PyTorch-ROCm kernels", reason)
+    return False
 
 
 def _use_fused_layout(surrogate, tensor, supported, layout, geometry=None, lib=None):

@@ -112,6 +112,10 @@ class AutoRegPDESurrogate(_EncDecSurrogate):
             # the KSDelayCNNSurrogateFactory layout: the whole rollout in one launch (delay_hip._DelayRolloutFn)
             from pdecontrol.surrogates import delay_hip
             return delay_hip.fused_delay_rollout(self, states, actions, times, targets, hidden)
+        if ops.use_fused_fc_for(self, states):
+            # KSAutoRegFullyConnectedLSTM with the opt-in switch on: the whole rollout in one launch (fclstm_hip._FCRolloutFn)
+            from pdecontrol.surrogates import fclstm_hip
+            return fclstm_hip.fused_fc_rollout(self, states, actions, times, targets, hidden)
         if ops.use_fused_for(self, states):
             # one launch per module instead of ~60 per time step (no inlatents in this mode)
             from pdecontrol.surrogates import hipops
@@ -157,6 +161,10 @@ class LatentAutoRegPDESurrogate(_EncDecSurrogate):
 
     def rollout(self, states: torch.Tensor, actions: torch.Tensor, times: torch.Tensor, targets: torch.Tensor,
                 hidden=None, **kwargs) -> ModelRollout:
+        if ops.use_fused_fc_for(self, states):
+            # KSLatentLSTM with the opt-in switch on: the whole rollout in one launch (fclstm_hip._FCRolloutFn)
+            from pdecontrol.surrogates import fclstm_hip
+            return fclstm_hip.fused_fc_rollout(self, states, actions, times, targets, hidden)
         if ops.use_fused_latent_for(self, states):
             # the KSLatentConvolutionalLSTM layout: two encoder launches and one latent chunk (hipops._LatentChunkFn)
             from pdecontrol.surrogates import hipops
