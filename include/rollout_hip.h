@@ -1,5 +1,5 @@
 /*
- * rollout_hip.h -- C ABI of librollout_hip.so: the two kernels that close the imagined-rollout loop of the controller on
+ * rollout_hip.h -- C ABI of librollout_hip.so: the kernels that close the imagined-rollout loop of the controller on
  * gfx950 (pdecontrol/mbrl/imagination_phase.py: imagine; kernels: csrc/rollout.hip).
  *
  * One imagined step is a captured chain  sac_policy_forward -> ro_act_chain -> every ensemble member's fused one-step
@@ -18,6 +18,8 @@
  *                      reward[t][b] = (float)((-1.0) * (1.0 / N) * sum_i (double)w_i * (double)w_i)
  *                  of the row rescaled by the optional per-column affine map w_i = affine_i(v_i) (fp64 sum over strided
  *                  lanes and xor shuffles, as the KS reward-row kernel).
+ *                  (The same kernel with the KS env's dissipation reward is declared in a header of its own,
+ *                  rollout/settle_dissipation.h, which includes this one.)
  *
  * Affine maps are ScaleTransform._affine's  out = ((v - a) / (b - a)) * (d - c) + c  with coef[0..3][j] = (a, b - a,
  * d - c, c) per OUTPUT column, as four separately rounded fp32 operations; NULL is the identity (replay_hip.h).
@@ -81,7 +83,7 @@ typedef struct ro_settle_args {
 /* Refusals: -1 NULL geometry, -2 B < 1, -3 T < 1, -4 N outside RO_MIN_STATE_DIM ... RO_MAX_STATE_DIM, -5 A outside
  * 1 ... RO_MAX_ACT_DIM, -6 forcing width < 1, -7 an action sensor with stride < 1 or a start outside the forcing row,
  * -8 an agent sensor with stride < 1 or a start outside the state row, -9 members outside 1 ... RO_MAX_MEMBERS.
- * 0 when both kernels run this geometry. */
+ * 0 when the kernels run this geometry. */
 int ro_supported(const ro_geometry* g);
 
 /* -10 a NULL pointer the kernel needs; -20 launch failure */

@@ -1,22 +1,26 @@
-// rollout.hip -- the two kernels that close the imagined-rollout loop in HBM (C ABI: include/rollout_hip.h;
+// rollout.hip -- the kernels that close the imagined-rollout loop in HBM (C ABI: include/rollout_hip.h and, for
+// ro_settle_dissipation, include/rollout/settle_dissipation.h;
 // binding: pdecontrol/mbrl/rollout_hip.py; caller: pdecontrol/mbrl/imagination_phase.py).
 //
 // ro_act_chain is the wrapper stack's action side (raw-action record, action scaling, Gaussian forcing, forcing scaling,
 // sensor), ro_settle its observation side (per-env elite pick, world state in place, trajectory slot, agent sensor, step
-// counters, l2control reward).  A wave owns an env, lanes run along the columns.  The ensemble members travel in the
-// kernel arguments and are picked by wave-uniform selects over constant indices, so the argument struct is never indexed
-// dynamically and nothing spills.  No LDS, no atomics; every store is a plain vector store.
+// counters, l2control reward); ro_settle_dissipation is ro_settle with the dissipation reward.  A wave owns an env, lanes
+// run along the columns.  The ensemble members travel in the kernel arguments and are picked by wave-uniform selects over
+// constant indices, so the argument struct is never indexed dynamically and nothing spills.  No LDS, no atomics; every
+// store is a plain vector store.
 //
 // The affine maps are row_ops.h's and the forcing chain is explicit fmaf, so the results equal the host wrappers' bit for
-// bit.
+// bit.  The dissipation reward's stencil is ks_internal.h's ref_terms, the one the KS reward-row kernel evaluates.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 
+#include "../../include/rollout/settle_dissipation.h"
 #include "../../include/rollout_hip.h"
 #include "capi_error.h"
+#include "ks_internal.h"
 #include "row_ops.h"
 
 namespace {
@@ -80,6 +84,19 @@ __device__ __forceinline__ void sense(float* __restrict__ pol, int i, float v, i
     if (j * stride == d && j < O) pol[j] = v;
 }
 
+// row b of the member chosen for `slot`, by wave-uniform selects over constant indices: the argument struct is never
+// indexed dynamically.  known: the index lies inside the ensemble; outside, the callers poison and read nothing
+__device__ __forceinline__ const float* member_row(const SettleKernelArgs& k, long slot, int b, bool& known)
+{
+    const int pick = k.a.chosen ? k.a.chosen[slot] : 0;
+    const float* src = k.a.member[0];
+#pragma unroll
+    for (int m = 1; m < RO_MAX_MEMBERS; ++m)
+        if (m < k.members && pick == m) src = k.a.member[m];
+    known = pick >= 0 && pick < k.members;
+    return src + (long)b * k.N;
+}
+
 __global__ __launch_bounds__(NT) void ro_settle_kernel(const SettleKernelArgs k)
 {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -88,15 +105,8 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const SettleKernelArgs k)
     if (blockIdx.x == 0 && threadIdx.x == 0) k.a.step[1] = t + 1;  // advance: ro_act_chain reads step[1], nobody here does
     if (b >= k.B || t < 0 || t >= k.T) return;                      // whole waves leave: the shuffles below stay complete
     const long slot = (long)t * k.B + b;
-
-    // wave-uniform selects over constant indices: the argument struct is never indexed dynamically
-    const int pick = k.a.chosen ? k.a.chosen[slot] : 0;
-    const float* src = k.a.member[0];
-#pragma unroll
-    for (int m = 1; m < RO_MAX_MEMBERS; ++m)
-        if (m < k.members && pick == m) src = k.a.member[m];
-    const bool known = pick >= 0 && pick < k.members;               // an index outside the ensemble: poison, read nothing
-    const float* __restrict__ row = src + (long)b * k.N;
+    bool known;
+    const float* __restrict__ row = member_row(k, slot, b, known);
     float* __restrict__ state = k.a.state + (long)b * k.N;
     float* __restrict__ traj = k.a.traj + (slot + k.B) * k.N;       // slot t + 1
     float* __restrict__ pol = k.a.policy_obs + (long)b * k.O;
@@ -134,6 +144,152 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const SettleKernelArgs k)
         k.a.rewards[slot] = (float)((-1.0) * (1.0 / k.N) * sum);
         k.a.steps[slot] = k.a.steps0[b] + t + 1;
     }
+}
+
+// ro_settle with the dissipation reward.  The stencil needs the rescaled row's periodic halo of 4 columns on both sides:
+// a lane re-reads its neighbours from the member's output row (read-only and cache-hot: the lanes next to it have just
+// fetched the same lines) and rescales them again, which costs arithmetic that this latency-bound step has to spare and
+// keeps the kernel free of LDS and of any wait between a store and a load.  On the float4 path the halo of a lane's
+// four columns is exactly the float4 before and the float4 after, wrapped around the row.
+struct DissKernelArgs {
+    SettleKernelArgs s;
+    const float* actions;     // [T][B][A]
+    const float* in_coef;     // [4][A] or NULL
+    const float* forcing;     // [A][N]
+    int A;
+    double dx, r_dx, dx2, r_dx2;
+};
+
+// column i of a periodic row of n, for -n <= i < 2n.  (ks_kernels.hip's wrap_idx, respelled: that function lives in the KS
+// translation unit, and bench.py quotes its counter profiles only while ks_kernels.hip and ks_internal.h are the files
+// they were measured on, so neither is edited for one line)
+__device__ __forceinline__ int wrap_col(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
+
+// the three partial sums of one point: window w, its squares q, centre c, forcing phi
+__device__ __forceinline__ void dissipation_point(const double* w, const double* q, int c, float phi, const DissKernelArgs& d,
+                                                  double& sxx, double& sx, double& sup)
+{
+    const ks::RefTerms p = ks::ref_terms<ks::DivMarkstein>(w, q, c, d.dx, d.r_dx, d.dx2, d.r_dx2);
+    sxx += p.d2 * p.d2;
+    sx += p.d1 * p.d1;
+    sup += w[c] * (double)phi;
+}
+
+__global__ __launch_bounds__(NT) void ro_settle_dissipation_kernel(const DissKernelArgs d)
+{
+    const SettleKernelArgs& k = d.s;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int b = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const int t = k.a.step[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) k.a.step[1] = t + 1;  // advance, as ro_settle_kernel
+    if (b >= k.B || t < 0 || t >= k.T) return;                      // whole waves leave: the shuffles below stay complete
+    const long slot = (long)t * k.B + b;
+    bool known;
+    const float* __restrict__ row = member_row(k, slot, b, known);
+    float* __restrict__ state = k.a.state + (long)b * k.N;
+    float* __restrict__ traj = k.a.traj + (slot + k.B) * k.N;       // slot t + 1
+    float* __restrict__ pol = k.a.policy_obs + (long)b * k.O;
+    const float* __restrict__ act = d.actions + slot * d.A;         // the raw actions ro_act_chain recorded for this step
+    const int N = k.N;
+
+    double sxx = 0.0, sx = 0.0, sup = 0.0;
+    if (k.vec) {                                                     // N a multiple of 4, every row 16-byte aligned
+        for (int i = 4 * lane; i < N; i += 4 * WAVE) {
+            const int il = wrap_col(i - 4, N), ir = wrap_col(i + 4, N);
+            f4 v = {NAN, NAN, NAN, NAN}, vl = v, vr = v;
+            if (known) {
+                v = *reinterpret_cast<const f4*>(row + i);
+                vl = *reinterpret_cast<const f4*>(row + il);
+                vr = *reinterpret_cast<const f4*>(row + ir);
+            }
+            *reinterpret_cast<f4*>(state + i) = v;
+            *reinterpret_cast<f4*>(traj + i) = v;
+            sense(pol, i, v.x, k.start, k.stride, k.O);
+            sense(pol, i + 1, v.y, k.start, k.stride, k.O);
+            sense(pol, i + 2, v.z, k.start, k.stride, k.O);
+            sense(pol, i + 3, v.w, k.start, k.stride, k.O);
+            const f4 u = affine_col4(k.a.reward_coef, N, i, v);
+            const f4 ul = affine_col4(k.a.reward_coef, N, il, vl);
+            const f4 ur = affine_col4(k.a.reward_coef, N, ir, vr);
+            // the forcing of the scaled action, as ro_act_chain forms it before its output map
+            const float* __restrict__ f = d.forcing + i;
+            const float a0 = affine_col(d.in_coef, d.A, 0, act[0]);
+            const f4 f0 = *reinterpret_cast<const f4*>(f);
+            f4 phi;
+            phi.x = __fmul_rn(a0, f0.x);
+            phi.y = __fmul_rn(a0, f0.y);
+            phi.z = __fmul_rn(a0, f0.z);
+            phi.w = __fmul_rn(a0, f0.w);
+            for (int m = 1; m < d.A; ++m) {
+                const float am = affine_col(d.in_coef, d.A, m, act[m]);
+                const f4 fm = *reinterpret_cast<const f4*>(f + (long)m * N);
+                phi.x = __fmaf_rn(am, fm.x, phi.x);
+                phi.y = __fmaf_rn(am, fm.y, phi.y);
+                phi.z = __fmaf_rn(am, fm.z, phi.z);
+                phi.w = __fmaf_rn(am, fm.w, phi.w);
+            }
+            const double w[12] = {(double)ul.x, (double)ul.y, (double)ul.z, (double)ul.w, (double)u.x,  (double)u.y,
+                                  (double)u.z,  (double)u.w,  (double)ur.x, (double)ur.y, (double)ur.z, (double)ur.w};
+            double q[12];
+#pragma unroll
+            for (int j = 0; j < 12; ++j) q[j] = w[j] * w[j];
+            dissipation_point(w, q, 4, phi.x, d, sxx, sx, sup);
+            dissipation_point(w, q, 5, phi.y, d, sxx, sx, sup);
+            dissipation_point(w, q, 6, phi.z, d, sxx, sx, sup);
+            dissipation_point(w, q, 7, phi.w, d, sxx, sx, sup);
+        }
+    } else {
+        for (int i = lane; i < N; i += WAVE) {
+            const float v = known ? row[i] : NAN;
+            state[i] = v;
+            traj[i] = v;
+            sense(pol, i, v, k.start, k.stride, k.O);
+            double w[9], q[9];
+#pragma unroll
+            for (int j = -4; j <= 4; ++j) {
+                const int c = wrap_col(i + j, N);
+                w[j + 4] = (double)affine_col(k.a.reward_coef, N, c, known ? row[c] : NAN);
+                q[j + 4] = w[j + 4] * w[j + 4];
+            }
+            const float* __restrict__ f = d.forcing + i;
+            float phi = __fmul_rn(affine_col(d.in_coef, d.A, 0, act[0]), f[0]);
+            for (int m = 1; m < d.A; ++m) phi = __fmaf_rn(affine_col(d.in_coef, d.A, m, act[m]), f[(long)m * N], phi);
+            dissipation_point(w, q, 4, phi, d, sxx, sx, sup);
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < WAVE; m <<= 1) {
+        sxx += __shfl_xor(sxx, m, WAVE);
+        sx += __shfl_xor(sx, m, WAVE);
+        sup += __shfl_xor(sup, m, WAVE);
+    }
+    if (lane == 0) {
+        k.a.rewards[slot] = (float)((-1.0) * ((sxx / N + sx / N) + sup / N));   // the KS reward-row kernel's expression
+        k.a.steps[slot] = k.a.steps0[b] + t + 1;
+    }
+}
+
+// the argument checks and the kernel arguments ro_settle and ro_settle_dissipation share; `who` names the caller
+int settle_kernel_args(const char* who, const ro_geometry* g, const ro_settle_args* a, SettleKernelArgs& k)
+{
+    if (!a || !a->state || !a->traj || !a->policy_obs || !a->steps0 || !a->steps || !a->rewards || !a->step)
+        return fail(-10, "%s: NULL argument, state, trajectory, observation, steps, rewards or step pointer", who);
+    if (g->members > 1 && !a->chosen) return fail(-10, "%s: %d members without a chosen-member array", who, g->members);
+    k = {};
+    k.a = *a;
+    k.B = g->B; k.T = g->T; k.N = g->N; k.members = g->members;
+    k.start = g->obs_start; k.stride = g->obs_stride;
+    k.O = width_of(g->N, g->obs_start, g->obs_stride);
+    k.vec = g->N % 4 == 0 && aligned16(a->state) && aligned16(a->traj) && aligned16(a->reward_coef);
+    for (int m = 0; m < RO_MAX_MEMBERS; ++m) {
+        if (m >= g->members) {
+            k.a.member[m] = nullptr;
+            continue;
+        }
+        if (!a->member[m]) return fail(-10, "%s: member %d has a NULL output pointer", who, m);
+        k.vec = k.vec && aligned16(a->member[m]);
+    }
+    return 0;
 }
 
 }  // namespace
@@ -180,25 +336,37 @@ int ro_settle(void* stream, const ro_geometry* g, const ro_settle_args* a)
 {
     const int rc = ro_supported(g);
     if (rc != 0) return rc;
-    if (!a || !a->state || !a->traj || !a->policy_obs || !a->steps0 || !a->steps || !a->rewards || !a->step)
-        return fail(-10, "ro_settle: NULL argument, state, trajectory, observation, steps, rewards or step pointer");
-    if (g->members > 1 && !a->chosen) return fail(-10, "ro_settle: %d members without a chosen-member array", g->members);
-    SettleKernelArgs k = {};
-    k.a = *a;
-    k.B = g->B; k.T = g->T; k.N = g->N; k.members = g->members;
-    k.start = g->obs_start; k.stride = g->obs_stride;
-    k.O = width_of(g->N, g->obs_start, g->obs_stride);
-    k.vec = g->N % 4 == 0 && aligned16(a->state) && aligned16(a->traj) && aligned16(a->reward_coef);
-    for (int m = 0; m < RO_MAX_MEMBERS; ++m) {
-        if (m >= g->members) {
-            k.a.member[m] = nullptr;
-            continue;
-        }
-        if (!a->member[m]) return fail(-10, "ro_settle: member %d has a NULL output pointer", m);
-        k.vec = k.vec && aligned16(a->member[m]);
-    }
+    SettleKernelArgs k;
+    const int bad = settle_kernel_args("ro_settle", g, a, k);
+    if (bad != 0) return bad;
     hipLaunchKernelGGL(ro_settle_kernel, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0, static_cast<hipStream_t>(stream), k);
     return launch_status(-20, "ro_settle");
+}
+
+int ro_settle_dissipation(void* stream, const ro_geometry* g, const ro_settle_args* a, const ro_dissipation_args* d)
+{
+    const int rc = ro_supported(g);
+    if (rc != 0) return rc;
+    DissKernelArgs k = {};
+    const int bad = settle_kernel_args("ro_settle_dissipation", g, a, k.s);
+    if (bad != 0) return bad;
+    if (!d || !d->actions || !d->forcing)
+        return fail(-10, "ro_settle_dissipation: NULL dissipation argument, recorded-actions or forcing pointer");
+    if (g->L != g->N)
+        return fail(-11, "ro_settle_dissipation: forcing width %d for a state width of %d (the reward needs the forcing at "
+                         "every grid point)", g->L, g->N);
+    if (!std::isfinite(d->dx) || d->dx <= 0.0)
+        return fail(-12, "ro_settle_dissipation: grid spacing %g (finite and above 0)", d->dx);
+    k.actions = d->actions; k.in_coef = d->in_coef; k.forcing = d->forcing;
+    k.A = g->A;
+    k.dx = d->dx;
+    k.dx2 = d->dx * d->dx;            // as ks::make_consts and the KS reward-row launch form them
+    k.r_dx = 1.0 / k.dx;
+    k.r_dx2 = 1.0 / k.dx2;
+    k.s.vec = k.s.vec && aligned16(d->forcing);
+    hipLaunchKernelGGL(ro_settle_dissipation_kernel, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0,
+                       static_cast<hipStream_t>(stream), k);
+    return launch_status(-20, "ro_settle_dissipation");
 }
 
 const char* ro_last_error(void) { return g_err; }

@@ -15,12 +15,16 @@ kernel tier   the closed loop stays in HBM for a whole round (one reset plus the
               ``WorldVecEnv.step_wait``, whose number is known on the host once the reset has drawn its windows).  One
               step is ``noise.normal_()`` plus one hipGraph replay of
                   sac_policy_forward -> ro_act_chain -> every member's fused one-step rollout -> ro_settle
-              (csrc/rollout.hip); the per-step elite draws are made on the host in the loop's order and uploaded once per
-              round; one D2H copy and one synchronisation per round bring the trajectory block back, and the replay is
-              built from it with one deque per episode and field.
+              (csrc/rollout.hip; under the KS env's dissipation objective the last launch is ro_settle_dissipation,
+              which recomputes the forcing of the recorded action for the reward's u * phi term); the per-step elite
+              draws are made on the host in the loop's order and uploaded once per round; one D2H copy and one
+              synchronisation per round bring the trajectory block back, and the replay is built from it with one deque
+              per episode and field.
 
 In both tiers the replay is the loop's (bit for bit but the rewards of the kernel tier, which are the fp64 row sums of
-``ro_settle`` where the loop squares an fp32 ``vector_norm``), numpy's global generator and torch's CPU and device
+``ro_settle`` where the loop squares an fp32 ``vector_norm``, and under dissipation the fp64 sums of
+``ro_settle_dissipation`` over the forcing of the recorded action, where the loop forces the action it recovers from the
+world's action row), numpy's global generator and torch's CPU and device
 generators are left where the loop leaves them, and so are the world's ``timesteps``, ``simulated``, state and hidden
 tensors.  ``deterministic`` reaches ``agent.select_action``, which ignores it as the reference's does: both tiers sample.
 The host-side stores of the wrapper stack are not written by the kernel tier: the controller drops them with
@@ -60,7 +64,9 @@ class StackGeometry:
     ``forcing``     the ``GaussianForcing`` matrix [A, L] (fp32, host)
     ``act_out``     sensor and scaling of the forcing columns: the world's action row
     ``agent_obs``   the agent sensor over the world's observation columns
-    ``reward``      the rescaling of the world's observation before the l2control reward
+    ``reward``      the rescaling of the world's observation before the reward
+    ``objective``   the KS env's reward, "l2control" or "dissipation" (``KuramotoSivashinskyEnv.step_objective``)
+    ``dx``          the env's grid spacing L / N (read by the dissipation reward)
     """
     world: object
     act_in: FieldMap
@@ -68,14 +74,17 @@ class StackGeometry:
     act_out: FieldMap
     agent_obs: FieldMap
     reward: FieldMap
+    objective: str = "l2control"
+    dx: float = 0.0
 
 
-def recognize_stack(stack):
+def recognize_stack(stack, objectives=("l2control",)):
     """``StackGeometry`` of the controller's imagined-rollout stack (mbrl.py:321-329), or raises ``Unrecognized``:
     ``StoreNActionsVecWrapper`` outermost, then ``TransformActionWrapper``s that flatten to at most one scaling, exactly
     one ``GaussianForcing``, at most one scaling and sensors; ``TransformObsWrapper``s holding only sensors over a
     ``StoreNObsVecWrapper``; a ``WorldVecEnv`` whose observation connector is a stride-1 sensor and at most one scaling
-    and whose batched reward is a ``KuramotoSivashinskyEnv``'s l2control."""
+    and whose batched reward is a ``KuramotoSivashinskyEnv``'s, under one of ``objectives`` (the kernel tier passes
+    both; the dissipation reward reads the forcing at every grid point, so its forcing must be as wide as the state)."""
     from pdecontrol.mbrl.world.world import WorldVecEnv
     from pdegym.kuramoto import KuramotoSivashinskyEnv
     env = stack.envs
@@ -111,11 +120,14 @@ def recognize_stack(stack):
     owner = getattr(world.batched_reward_func, "__self__", None)
     if not isinstance(owner, KuramotoSivashinskyEnv):
         raise Unrecognized("a world without the batched reward of a KuramotoSivashinskyEnv")
-    if not owner.objective:
-        raise Unrecognized("the dissipation objective")
+    objective = owner.step_objective
+    if objective not in objectives:
+        raise Unrecognized(f"the {objective} objective")
     if owner.N != N:
         raise Unrecognized(f"a reward over {owner.N} grid points for observations of {N}")
-    return StackGeometry(world, act_in, matrix, act_out, agent_obs, reward)
+    if objective == "dissipation" and int(matrix.shape[1]) != N:
+        raise Unrecognized(f"a forcing over {int(matrix.shape[1])} columns under the dissipation reward of {N} grid points")
+    return StackGeometry(world, act_in, matrix, act_out, agent_obs, reward, objective, owner.L / owner.N)
 
 
 def round_length(timesteps0, horizon, max_episode_steps):
@@ -166,6 +178,7 @@ class _CapturedStep:
         self.geometry = ro.Geometry(B, T, N, A, L, geo.act_out.start, geo.act_out.stride, geo.agent_obs.start,
                                     geo.agent_obs.stride, len(dev.members))
         self.maps = (geo.act_in, geo.act_out, geo.agent_obs, geo.reward)
+        self.objective, self.dx = geo.objective, float(geo.dx)
         self.forcing_host = geo.forcing
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=device)
         self.forcing = geo.forcing.to(device)
@@ -204,9 +217,13 @@ class _CapturedStep:
                 for h, new in zip(hid, r.hidden):
                     h.copy_(new)
             self.keep = outs
-            ro.settle(stream, self.geometry, ro.settle_args(
-                outs, self.chosen if len(outs) > 1 else None, dev.state, self.traj, self.policy_obs, self.steps0, self.steps,
-                self.rewards, self.coefs[2], self.step))
+            settle_args = ro.settle_args(outs, self.chosen if len(outs) > 1 else None, dev.state, self.traj, self.policy_obs,
+                                         self.steps0, self.steps, self.rewards, self.coefs[2], self.step)
+            if self.objective == "dissipation":
+                ro.settle_dissipation(stream, self.geometry, settle_args,
+                                      ro.dissipation_args(self.actions, self.coefs[0], self.forcing, self.dx))
+            else:
+                ro.settle(stream, self.geometry, settle_args)
 
         saved = (dev.state.clone(), [tuple(h.clone() for h in hid) for hid in dev.hidden])
         (stream,) = pooled_streams(device, 1, "capture")
@@ -233,7 +250,7 @@ class _CapturedStep:
         into the tensors the graph reads (the controller's observation scaling keeps learning between iterations)."""
         world = geo.world
         if (world._dev is not self.dev or not self.dev.valid() or fused is not self.fused or fused.version != self.version
-                or max(int(world.horizon), 1) != self.T):
+                or max(int(world.horizon), 1) != self.T or geo.objective != self.objective or float(geo.dx) != self.dx):
             return False
         now = (geo.act_in, geo.act_out, geo.agent_obs, geo.reward)
         if any((a.start, a.stride, a.width, a.coef is None) != (b.start, b.stride, b.width, b.coef is None)
@@ -267,7 +284,7 @@ def _kernel_tier(agent, stack):
     if agent.device.type != "cuda" or not ops.fused_enabled():
         return None, None
     try:
-        geo = recognize_stack(stack)
+        geo = recognize_stack(stack, objectives=("l2control", "dissipation"))
     except Unrecognized as e:
         _notice(str(e))
         return None, None

@@ -1,6 +1,7 @@
-"""ctypes binding of librollout_hip.so (C ABI: include/rollout_hip.h ``ro_*``; kernels: csrc/rollout.hip): the
-action chain and the settle kernel of the captured imagined step.  ``ro_supported`` and ``ro_last_error`` are pure host
-functions and work without a GPU.  A missing library raises: the kernel tier of pdecontrol/mbrl/imagination_phase.py has
+"""ctypes binding of librollout_hip.so (C ABI: include/rollout_hip.h ``ro_*`` and, for the dissipation objective,
+include/rollout/settle_dissipation.h; kernels: csrc/rollout.hip): the action chain and the settle kernels (one per reward
+objective) of the captured imagined step.  ``ro_supported`` and ``ro_last_error`` are pure host functions and work
+without a GPU.  A missing library raises: the kernel tier of pdecontrol/mbrl/imagination_phase.py has
 no silent fallback.
 """
 import ctypes
@@ -33,12 +34,22 @@ class SettleArgs(ctypes.Structure):
                 ("steps", _p), ("rewards", _p), ("reward_coef", _p), ("step", _p)]
 
 
+class DissipationArgs(ctypes.Structure):
+    """``ro_dissipation_args`` of include/rollout/settle_dissipation.h"""
+    _fields_ = [("actions", _p), ("in_coef", _p), ("forcing", _p), ("dx", ctypes.c_double)]
+
+
 _geo = ctypes.POINTER(Geometry)
 SYMBOLS = (
     ("ro_supported", _i, [_geo]),
     ("ro_act_chain", _i, [_p, _geo, ctypes.POINTER(ActArgs)]),
     ("ro_settle", _i, [_p, _geo, ctypes.POINTER(SettleArgs)]),
     ("ro_last_error", ctypes.c_char_p, []),
+)
+# include/rollout/settle_dissipation.h, the same library (tests/test_imagination_dissipation_host.py holds that header,
+# this table and the library to each other as tests/test_capi_symbols.py does for SYMBOLS)
+DISSIPATION_SYMBOLS = (
+    ("ro_settle_dissipation", _i, [_p, _geo, ctypes.POINTER(SettleArgs), ctypes.POINTER(DissipationArgs)]),
 )
 _lib = None
 
@@ -50,7 +61,7 @@ class RolloutHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, RolloutHipError, "The fused imagined-rollout step has no fallback.")
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + DISSIPATION_SYMBOLS, RolloutHipError, "The fused imagined-rollout step has no fallback.")
     return _lib
 
 
@@ -85,6 +96,12 @@ def settle_args(members, chosen, state, traj, policy_obs, steps0, steps, rewards
     return a
 
 
+def dissipation_args(actions, in_coef, forcing, dx):
+    """``ro_dissipation_args`` from device tensors: the raw-action record ``ro_act_chain`` writes, its ``in_coef`` (may be
+    None) and its forcing, which must span the whole state row; ``dx`` is the grid spacing."""
+    return DissipationArgs(actions.data_ptr(), None if in_coef is None else in_coef.data_ptr(), forcing.data_ptr(), float(dx))
+
+
 def act_chain(stream, geometry, args):
     """One launch on ``stream`` (a raw hipStream_t)."""
     _check(load().ro_act_chain(stream, ctypes.byref(geometry), ctypes.byref(args)))
@@ -92,3 +109,8 @@ def act_chain(stream, geometry, args):
 
 def settle(stream, geometry, args):
     _check(load().ro_settle(stream, ctypes.byref(geometry), ctypes.byref(args)))
+
+
+def settle_dissipation(stream, geometry, args, dissipation):
+    """``settle`` with the dissipation reward (``dissipation``: ``dissipation_args``)."""
+    _check(load().ro_settle_dissipation(stream, ctypes.byref(geometry), ctypes.byref(args), ctypes.byref(dissipation)))

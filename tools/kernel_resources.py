@@ -12,7 +12,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "model-based-pde-control_amd", "csrc")
 SOURCES = [("ks_kernels.hip", ["-ffp-contract=off"]), ("sur_kernels.hip", []), ("sur_windows.hip", ["-ffp-contract=off"]),
-           ("burgers.hip", ["-ffp-contract=off"]), ("spectral.hip", [])]
+           ("burgers.hip", ["-ffp-contract=off"]), ("spectral.hip", []), ("rollout.hip", ["-ffp-contract=off"])]
 
 
 def demangle(names):
