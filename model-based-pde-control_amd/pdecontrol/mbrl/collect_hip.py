@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "lib", "libcollect_hip.so"))
 
 MIN_STATE_DIM, MAX_STATE_DIM, MAX_ACT_DIM = 16, 1024, 16
+SPAN_MAX_PARTS = 1024            # CO_SPAN_MAX_PARTS of include/collect/span.h
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
 
@@ -31,6 +32,11 @@ class ObserveArgs(ctypes.Structure):
                 ("workspace", _p)]
 
 
+class ActSpanArgs(ctypes.Structure):
+    """``co_act_span_args`` of include/collect/span.h"""
+    _fields_ = [("table", _p), ("coef", _p), ("env_actions", _p), ("actions", _p), ("record_raw", _i)]
+
+
 _geo = ctypes.POINTER(Geometry)
 SYMBOLS = (
     ("co_supported", _i, [_geo]),
@@ -38,6 +44,13 @@ SYMBOLS = (
     ("co_act", _i, [_p, _geo, ctypes.POINTER(ActArgs), _i]),
     ("co_observe", _i, [_p, _geo, ctypes.POINTER(ObserveArgs), _i]),
     ("co_last_error", ctypes.c_char_p, []),
+)
+# include/collect/span.h, the same library (tests/test_collect_span_host.py holds that header, this table and the library
+# to each other as tests/test_capi_symbols.py does for SYMBOLS)
+SPAN_SYMBOLS = (
+    ("co_span_workspace_floats", ctypes.c_long, [_geo]),
+    ("co_act_span", _i, [_p, _geo, ctypes.POINTER(ActSpanArgs)]),
+    ("co_observe_span", _i, [_p, _geo, ctypes.POINTER(ObserveArgs)]),
 )
 _lib = None
 
@@ -49,7 +62,7 @@ class CollectHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.open_library(LIB_PATH, SYMBOLS, CollectHipError, "The device-resident collection step has no fallback.")
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + SPAN_SYMBOLS, CollectHipError, "The device-resident collection step has no fallback.")
     return _lib
 
 
@@ -97,3 +110,27 @@ def act(stream, geometry, args, t):
 def observe(stream, geometry, args, t):
     """Two launches with an updating scaling, else one."""
     _check(load().co_observe(stream, ctypes.byref(geometry), ctypes.byref(args), int(t)))
+
+
+def span_workspace_floats(geometry):
+    """Floats of scratch ``observe_span`` needs with ``update = 1``; raises for a geometry ``supported`` refuses."""
+    n = load().co_span_workspace_floats(ctypes.byref(geometry))
+    if n < 0:
+        raise CollectHipError(f"libcollect_hip error {n}: {last_error()}")
+    return int(n)
+
+
+def act_span_args(table, coef, env_actions, actions, record_raw=False):
+    """``co_act_span_args`` from device tensors of ``[T, E, A]`` (``coef`` may be None)."""
+    return ActSpanArgs(_ptr(table), _ptr(coef), _ptr(env_actions), _ptr(actions), int(bool(record_raw)))
+
+
+def act_span(stream, geometry, args):
+    """One launch for all ``geometry.T`` steps of a segment."""
+    _check(load().co_act_span(stream, ctypes.byref(geometry), ctypes.byref(args)))
+
+
+def observe_span(stream, geometry, args):
+    """The observation side of a whole segment (``args``: ``observe_args``; reads bounds cell 0, writes cell 1): two
+    launches with an updating scaling, else one."""
+    _check(load().co_observe_span(stream, ctypes.byref(geometry), ctypes.byref(args)))

@@ -8,7 +8,8 @@ appends per env) under a stop test that re-counts every deque.  ``collect(worker
 ``ExperienceReplay`` ``worker.rollout(agent, stop)`` returns, on one of two tiers (chosen per call, announced once per
 reason; the result carries ``tier``, ``tier_reason`` and ``host_steps``):
 
-loop tier     ``Worker.rollout`` itself: CPU agents and agents that are not a ``SAC``, ``PDECONTROL_FUSED=0``, a SAC
+loop tier     ``Worker.rollout`` itself: CPU agents and agents that are neither a ``SAC`` nor one of the two scripted
+              agents of pdecontrol/mbrl/utils.py, ``PDECONTROL_FUSED=0``, a SAC
               geometry the fused kernels refuse, the CPU twin and ``KSShardedVecEnv``, an env on another device than the
               agent, any stack ``recognize_real_stack`` does not reduce to the controller's.
 kernel tier   truncation is the only way an episode ends, so ``plan_phase`` knows from host integers alone how many steps
@@ -23,6 +24,16 @@ kernel tier   truncation is the only way an episode ends, so ``plan_phase`` know
               episode and field.  A step at which an env truncates is one ordinary host step of the stack between two
               segments, on the state just written back: the autoreset and the final-observation quirks of
               ``TransformObsWrapper`` are the stack's own.
+
+scripted tier the kernel tier for an agent whose class IS ``pdecontrol.mbrl.utils.RandomAgent`` or ``ActionRepeatAgent``
+              (the controller's warm-up and its surrogate evaluation): the actions do not depend on the observation, so a
+              segment's ``T`` actions are drawn on the host first, in the loop's order, uploaded once, and the segment is
+                  co_act_span -> T x ks_step_device -> co_observe_span
+              (include/collect/span.h): ``T + 3`` launches, ``T + 1`` with a frozen or absent scaling, where the SAC tier
+              takes ``5 T``.  The device is the env's.  Before anything is drawn the action space must be float32
+              ``(E, 1, A)``, the table float32 ``[E, >= nstep + K, 1, A]``; otherwise the loop runs, with that reason.
+              Plan, segments, truncation steps, replay build, sink and write-back are the kernel tier's; the result
+              carries ``tier = "kernel"``.
 
 In both tiers everything the loop mutates ends where the loop leaves it: the worker's two observations, the stores, the
 scaling's bounds, ``env.timestep``, the stepper's state, the env's MT19937 streams, numpy's and torch's generators, and
@@ -293,14 +304,79 @@ def _notice(reason, expected=False):
            "Worker.rollout", reason, expected)
 
 
-def _kernel_tier(worker, agent):
-    """(RealStackGeometry, FusedSAC, None) when this phase runs on the kernels, else (None, None, reason)."""
+def _is_scripted(agent):
+    """The agent's class IS one of the two scripted agents of pdecontrol/mbrl/utils.py (no subclass, no namesake)."""
+    from pdecontrol.mbrl import utils
+    return type(agent) in (utils.RandomAgent, utils.ActionRepeatAgent)
+
+
+def _scripted_refusal(agent, E, A, steps):
+    """Why the scripted tier cannot take this agent's actions for a phase of ``steps()`` steps, or None.  Reads shapes
+    and dtypes only: nothing is drawn from the agent."""
+    from pdecontrol.mbrl import utils
+    if type(agent) is utils.RandomAgent:
+        space = agent.action_space
+        shape, dtype = getattr(space, "shape", None), getattr(space, "dtype", None)
+        if shape is None or tuple(shape) != (E, 1, A) or dtype != np.float32:
+            return f"a RandomAgent over an action space of shape {shape} and dtype {dtype} (float32 {(E, 1, A)} is expected)"
+        return None
+    table = agent.actions
+    if not isinstance(table, np.ndarray) or table.dtype != np.float32 or table.ndim != 4 \
+            or (table.shape[0], table.shape[2], table.shape[3]) != (E, 1, A):
+        return (f"an ActionRepeatAgent whose table is not a float32 array of [{E}, steps, 1, {A}] "
+                f"({type(table).__name__} {getattr(table, 'dtype', None)} {tuple(getattr(table, 'shape', ()))})")
+    need = int(agent.nstep) + steps()
+    if table.shape[1] < need:
+        return f"an ActionRepeatAgent whose table holds {table.shape[1]} steps where the phase ends at step {need}"
+    return None
+
+
+def _scripted_tier(worker, agent, stop):
+    """(RealStackGeometry, None, None) when this phase of a scripted agent runs on the span kernels (co_act_span, the
+    stepper, co_observe_span: include/collect/span.h), else (None, None, reason).  The SAC tier's conditions minus the
+    agent's; the device is the env's."""
+    def loop(reason, expected=False):
+        _notice(reason, expected)
+        return None, None, reason
+
+    if not ops.fused_enabled():
+        return loop("PDECONTROL_FUSED=0", True)
+    try:
+        geo = recognize_real_stack(worker.stack)
+    except Unrecognized as e:
+        return loop(str(e))
+    env = geo.env
+    E, A = env.num_envs, geo.action.width
+
+    def steps():                                          # the phase's length, from host integers (a fresh worker resets first)
+        start = env.timestep if worker._last_obs is not None else np.zeros(E, dtype=np.int64)
+        return plan_phase(start, env.max_episode_steps, E, stop).K
+
+    reason = _scripted_refusal(agent, E, A, steps)
+    if reason is not None:
+        return loop(reason)
+    if env.stepper.device < 0:
+        return loop("the CPU twin of the KS stepper")
+    from pdecontrol.mbrl import collect_hip as co
+    if env.stepper.n_act != A:
+        return loop(f"a stepper with {env.stepper.n_act} actuators under {A} action columns")
+    reason = co.supported(co.Geometry(E, 1, env.N, A, geo.agent_obs.start, geo.agent_obs.stride))
+    if reason is not None:
+        return loop(reason)
+    return geo, None, None
+
+
+def _kernel_tier(worker, agent, stop=None):
+    """(RealStackGeometry, FusedSAC, None) when this phase runs on the kernels (FusedSAC is None for a scripted agent,
+    which needs ``stop`` to be recognised), else (None, None, reason)."""
     from pdecontrol.sac.sac import SAC
 
     def loop(reason, expected=False):
         _notice(reason, expected)
         return None, None, reason
 
+    if stop is not None and _is_scripted(agent):
+        return _scripted_tier(worker, agent, stop)
     if not isinstance(agent, SAC):
         return loop(f"a {type(agent).__name__} agent (not a SAC)", True)
     if agent.device.type != "cuda":
@@ -391,6 +467,42 @@ class _Buffers:
             self.index_host = torch.empty(words, dtype=torch.int64).pin_memory()
         cut = lambda block: (block[:n].view(T, self.E), block[n:words].view(torch.int32)[:n].view(T, self.E))
         return cut(self.index), cut(self.index_host), words
+
+
+class _SpanBuffers(_Buffers):
+    """``_Buffers`` of the scripted tier: no agent-side buffers, the segment's action table (pinned host and device) and
+    the stepper's action rows ``[T, E, A]``, and the span workspace (grown on demand)."""
+
+    def __init__(self, geo):
+        env = geo.env
+        self.device = torch.device("cuda", env.stepper.device)
+        self.E, self.N, self.A, self.O = env.num_envs, env.N, geo.action.width, geo.agent_obs.width
+        self.sensor = (geo.agent_obs.start, geo.agent_obs.stride)
+        self.coef = torch.zeros((4, self.A), dtype=torch.float32, device=self.device)
+        self.block = self.block_host = None
+        self.capacity = 0
+        self.index = self.index_host = None
+        self.table = self.table_host = self.env_actions = self.workspace = None
+
+    def matches(self, geo):
+        env = geo.env
+        return (same_device(self.device, torch.device("cuda", env.stepper.device))
+                and (self.E, self.N, self.A, self.O, self.sensor) ==
+                (env.num_envs, env.N, geo.action.width, geo.agent_obs.width, (geo.agent_obs.start, geo.agent_obs.stride)))
+
+    def span(self, T):
+        """(device table, pinned host table, stepper action rows) of ``[T, E, A]`` and the workspace of a ``T``-step span."""
+        from pdecontrol.mbrl import collect_hip as co
+        n = T * self.E * self.A
+        if self.table is None or self.table.numel() < n:
+            self.table = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.env_actions = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.table_host = torch.empty(n, dtype=torch.float32).pin_memory()
+        floats = co.span_workspace_floats(co.Geometry(self.E, T, self.N, self.A, *self.sensor))
+        if self.workspace is None or self.workspace.numel() < floats:
+            self.workspace = torch.empty(co.SPAN_MAX_PARTS * 2, dtype=torch.float32, device=self.device)
+        shape = (T, self.E, self.A)
+        return self.table[:n].view(shape), self.table_host[:n].view(shape), self.env_actions[:n].view(shape), self.workspace
 
 
 class _SinkPhase:
@@ -533,19 +645,79 @@ def _run_segment(worker, agent, fused, geo, buf, T, steps, phase=None):
                        h_status.numpy(), steps)
 
 
-def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, steps):
+def _run_span(worker, agent, geo, buf, T, steps, deterministic, phase=None):
+    """``_run_segment`` for a scripted agent: the agent's ``T`` actions are drawn on the host first, in order, and uploaded
+    once; then  co_act_span -> T x ks_step_device -> co_observe_span  (T + 3 launches, T + 1 with a frozen or absent
+    scaling), the sink's record launch and the same write-back, with the bounds taken from cell 1."""
+    from pdecontrol.mbrl import collect_hip as co
+    env, scaling = geo.env, geo.scaling
+    E, N, A = buf.E, buf.N, buf.A
+    (traj, actions, pobs, bounds, ssq, status), (h_traj, h_actions, h_pobs, h_bounds, h_ssq, h_status), used = buf.views(T)
+    table, h_table, env_actions, workspace = buf.span(T)
+    for t in range(T):                                    # the loop's draws, in the loop's order
+        drawn = agent.select_action(worker._last_obs, deterministic=deterministic)
+        h_table[t].copy_(torch.from_numpy(np.ascontiguousarray(drawn, dtype=np.float32).reshape(E, A)))
+    h_traj[0].copy_(torch.from_numpy(np.ascontiguousarray(worker._last_stored_obs, dtype=np.float32).reshape(E, N)))
+    if scaling is not None:
+        h_bounds[0] = h_bounds[2] = float(scaling.vmin)
+        h_bounds[1] = h_bounds[3] = float(scaling.vmax)
+    for dst, src in ((traj[0], h_traj[0]), (bounds, h_bounds), (table, h_table)):
+        dst.copy_(src, non_blocking=True)
+    geometry = co.Geometry(E, T, N, A, *buf.sensor)
+    coef = None
+    if geo.action.coef is not None:
+        buf.coef.copy_(geo.action.coef)
+        coef = buf.coef
+    current = torch.cuda.current_stream(buf.device)
+    if getattr(env, "_stream_handle", None) != current.cuda_stream:     # as ``KSBatchedVecEnv.step_torch`` binds it
+        env.stepper.set_stream(current.cuda_stream)
+        env._stream_handle = current.cuda_stream
+    env._set_objective(env.proto.step_objective)
+    stream = co.stream()
+    co.act_span(stream, geometry, co.act_span_args(table, coef, env_actions, actions, geo.record_raw))
+    substeps, row, slot = env.cfg_steps, E * N * 4, traj.data_ptr()
+    d_env_actions, d_ssq, d_status = env_actions.data_ptr(), ssq.data_ptr(), status.data_ptr()
+    for t in range(T):                                    # eager launches, no host synchronisation
+        env.stepper.step_device(d_actions=d_env_actions + t * E * A * 4, n_substeps=substeps, d_obs=slot + (t + 1) * row,
+                                d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)
+    co.observe_span(stream, geometry, co.observe_args(
+        traj, pobs, None if scaling is None else bounds, 0.0 if scaling is None else float(scaling.lower),
+        0.0 if scaling is None else float(scaling.upper), geo.update, workspace))
+    if phase is not None:
+        dst = phase.reserve(T)
+        (d_dst, d_steps), (h_dst, h_steps), words = buf.index_views(T)
+        h_dst.copy_(torch.from_numpy(dst))
+        h_steps.copy_(torch.from_numpy(np.asarray(steps, dtype=np.int32)))
+        buf.index[:words].copy_(buf.index_host[:words], non_blocking=True)
+        env.stepper.record_device(traj.data_ptr(), actions.data_ptr(), A, d_ssq, d_steps.data_ptr(), T, substeps,
+                                  d_dst.data_ptr(), dst, phase.slabs())
+        off = buf.layout(T)
+        for a, b in ((off[0] + T * E * N, off[1]), (off[1] + (T - 1) * E * A, off[2]), (off[2], off[4]), (off[6], off[7])):
+            buf.block_host[int(a):int(b)].copy_(buf.block[int(a):int(b)], non_blocking=True)
+        current.synchronize()                             # the segment's one synchronisation
+        _restore(worker, geo, T, h_traj[T].numpy(), h_actions[T - 1].numpy(), h_pobs.numpy(), h_bounds.numpy(),
+                 h_status.numpy(), cell=2)
+        return None
+    buf.block_host[:used].copy_(buf.block[:used], non_blocking=True)
+    current.synchronize()                                 # the segment's one synchronisation
+    return _write_back(worker, geo, T, h_traj.numpy(), h_actions.numpy(), h_pobs.numpy(), h_bounds.numpy(), h_ssq.numpy(),
+                       h_status.numpy(), steps, cell=2)
+
+
+def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, steps, cell=None):
     """A segment's host block (views of the pinned staging: copied here) into the state the loop would hold after these
     ``T`` steps -- stores, bounds, ``env.timestep``, the worker's two observations -- and the segment's replay piece."""
     env = geo.env
-    _restore(worker, geo, T, traj[T], actions[T - 1], policy_obs, bounds, status)
+    _restore(worker, geo, T, traj[T], actions[T - 1], policy_obs, bounds, status, cell)
     traj, actions = traj.copy(), actions.copy()
     rewards = (-1.0) * (1 / env.N) * ssq / env.cfg_steps  # ``KSBatchedVecEnv._finish_step``, every step at once
     return traj, actions, rewards, steps
 
 
-def _restore(worker, geo, T, last_obs, last_actions, policy_obs, bounds, status):
+def _restore(worker, geo, T, last_obs, last_actions, policy_obs, bounds, status, cell=None):
     """The state the loop would hold after these ``T`` steps, from views of the pinned staging (copied here): ``last_obs``
-    [E, N] the observations the last step ends with, ``last_actions`` [E, A] its recorded actions."""
+    [E, N] the observations the last step ends with, ``last_actions`` [E, A] its recorded actions.  ``cell``: the offset
+    in ``bounds`` of the cell the segment's last launch wrote (a span: 2; default: the per-step ping-pong's)."""
     env, scaling = geo.env, geo.scaling
     ostore, astore = worker.stack.ostore, worker.stack.astore
     bad = np.nonzero(status.any(axis=1))[0]
@@ -556,7 +728,8 @@ def _restore(worker, geo, T, last_obs, last_actions, policy_obs, bounds, status)
     astore.actions[:, -1] = last_actions[:, None, :]
     astore.mask[:, -1] = True
     if geo.update:
-        cell = 2 * (T & 1)                                # step T - 1 wrote cell T & 1
+        if cell is None:
+            cell = 2 * (T & 1)                            # step T - 1 wrote cell T & 1
         as_stat = lambda v: torch.from_numpy(np.asarray(v, dtype=np.float32).reshape(1, 1, 1).copy())
         scaling.vmin, scaling.vmax = as_stat(bounds[cell]), as_stat(bounds[cell + 1])
     env.timestep += T
@@ -564,14 +737,18 @@ def _restore(worker, geo, T, last_obs, last_actions, policy_obs, bounds, status)
     worker._last_stored_obs = _stored(ostore, ostore.obs)
 
 
-def _check_sink(sink, agent, kernel):
-    """The sink is a ``DeviceExperienceReplay`` on the agent's device, or (loop tier only) on the CPU."""
+def _check_sink(sink, agent, kernel, env_device=None):
+    """The sink is a ``DeviceExperienceReplay`` on the agent's device, or (loop tier only) on the CPU.  An agent without
+    a device (a scripted one) stands on the env's, ``env_device``, on the kernel tier."""
     from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
     if not isinstance(sink, DeviceExperienceReplay):
         raise ValueError(f"collect() takes a DeviceExperienceReplay as its sink, not a {type(sink).__name__}")
     device = getattr(agent, "device", None)
     if kernel:
-        if not _same_device(sink.device, device):
+        if device is None:
+            if not _same_device(sink.device, env_device):
+                raise ValueError(f"the sink is on {sink.device} and the env on {env_device}: the kernels write the env's device")
+        elif not _same_device(sink.device, device):
             raise ValueError(f"the sink is on {sink.device} and the agent on {device}: the kernels write the agent's device")
     elif sink.device.type != "cpu" and device is not None and not _same_device(sink.device, device):
         raise ValueError(f"the sink is on {sink.device} and the agent on {device}: a sink is on the agent's device or on "
@@ -589,9 +766,10 @@ def collect(worker, agent, stop, deterministic=False, sink=None):
     on either tier, a ``StagedRollout`` whose rows are in the sink's slabs and which ``sink.extend(result)`` commits
     (``result.to_host()`` is the host replay); the worker's callbacks receive ``result.to_host()``.  A step that
     overflows discards the staged rows before it raises."""
-    geo, fused, reason = _kernel_tier(worker, agent)
+    geo, fused, reason = _kernel_tier(worker, agent, stop)
+    scripted = geo is not None and fused is None
     if sink is not None:
-        _check_sink(sink, agent, kernel=geo is not None)
+        _check_sink(sink, agent, geo is not None, None if geo is None else torch.device("cuda", geo.env.stepper.device))
     if geo is None:
         replay = worker.rollout(agent, stop, deterministic)
         result = replay if sink is None else sink._stage_host(replay)
@@ -605,9 +783,14 @@ def collect(worker, agent, stop, deterministic=False, sink=None):
             worker._last_obs = worker.stack.envs.reset()
             worker._last_stored_obs = _stored(worker.stack.ostore, worker.stack.ostore.obs)
         plan = plan_phase(env.timestep, env.max_episode_steps, E, stop)
-        buf = getattr(worker, "_collect_buffers", None)
-        if buf is None or not buf.matches(agent, geo):
-            buf = worker._collect_buffers = _Buffers(agent, geo)
+        if scripted:
+            buf = getattr(worker, "_span_buffers", None)
+            if buf is None or not buf.matches(geo):
+                buf = worker._span_buffers = _SpanBuffers(geo)
+        else:
+            buf = getattr(worker, "_collect_buffers", None)
+            if buf is None or not buf.matches(agent, geo):
+                buf = worker._collect_buffers = _Buffers(agent, geo)
         pieces, host_steps = [], 0
         phase = None if sink is None else _SinkPhase(sink, E, env.N, buf.A, plan.K * E)
         try:
@@ -619,6 +802,10 @@ def collect(worker, agent, stop, deterministic=False, sink=None):
                         pieces.append(sample)
                     else:
                         phase.host_step(sample)
+                elif scripted:
+                    piece = _run_span(worker, agent, geo, buf, n, plan.steps[first:first + n], deterministic, phase)
+                    if phase is None:
+                        pieces.append(piece)
                 else:
                     piece = _run_segment(worker, agent, fused, geo, buf, n, plan.steps[first:first + n], phase)
                     if phase is None:

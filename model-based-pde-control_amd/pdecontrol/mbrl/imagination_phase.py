@@ -281,6 +281,9 @@ def _kernel_tier(agent, stack):
     """(StackGeometry, FusedSAC) when this phase runs on the kernels, else (None, None)."""
     from pdecontrol.mbrl import rollout_hip as ro
     from pdecontrol.sac import sac_hip
+    if getattr(agent, "device", None) is None:            # a scripted agent (pdecontrol/mbrl/utils.py): no policy to fuse
+        _notice(f"a {type(agent).__name__} agent (not a SAC)")
+        return None, None
     if agent.device.type != "cuda" or not ops.fused_enabled():
         return None, None
     try:

@@ -247,7 +247,7 @@ def _train_kernel(module, tier, fit, loader, target, batch_size):
 # ----------------------------------------------------------------------------------------------------------------------
 # the phase
 # ----------------------------------------------------------------------------------------------------------------------
-def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience, max_epochs=None, timings=None):
+def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience, max_epochs=None, timings=None, tier=None):
     """Fits ``module`` on ``datamodule`` and returns the last epoch's "Val. Loss" as a float: ``reset_trainer`` +
     ``trainer.fit`` + ``logged_metrics["Val. Loss"]`` of the reference (mbrl.py:568-595), with ``fit`` (a ``FitState``)
     in the trainer's place.  The rule below is this repository's reading of that fit loop; it is unpinned against
@@ -282,6 +282,9 @@ def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience,
     the module allows it, else ``training_step -> zero_grad -> backward -> step`` with the optimizer of
     ``configure_optimizers`` kept on ``fit``; validation through ``module.validation_step`` under ``no_grad``.
 
+    ``tier="loop"`` forces the loop tier (the controller's ``phase_tiers="loop"``): the datamodule's own loaders, which
+    with ``device_data`` yield device batches, and ``fused_step`` where the module allows it.
+
     ``timings`` (tools/surrogate_phase_bench.py) is an optional dict that receives the host seconds of the plan
     (dataloaders, ``locate_many``, uploads), of training and of validation, and the tier that ran; on a CUDA module each
     lap then ends in a device synchronisation, which the phase otherwise does only for an epoch's validation metrics."""
@@ -298,7 +301,9 @@ def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience,
     fit.wait_count = 0
     target, min_target = fit.global_step + int(max_steps), fit.global_step + int(min_steps)
     datamodule.trainer = fit
-    tier, reason = _pick_tier(module, datamodule)
+    if tier not in (None, "loop"):
+        raise ValueError(f"tier is {tier!r}: None or 'loop'")
+    tier, reason = (None, "the loop tier was asked for") if tier == "loop" else _pick_tier(module, datamodule)
     fit.tier, fit.tier_reason = ("kernel", None) if tier is not None else ("loop", reason)
     if tier is None:
         notice("the surrogate-update phase runs on its loop tier: %s", reason, expected=not cuda)

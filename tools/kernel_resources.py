@@ -2,7 +2,7 @@
 """Register / LDS / scratch footprint of every kernel this repo compiles for gfx950, from the assembler metadata
 (hipcc -S --cuda-device-only), and the wave occupancy it allows: gfx950 has 512 unified VGPRs per SIMD lane, allocated
 in granules of 8, at most 8 waves per SIMD.  Dynamic LDS is chosen at launch and is not in this table (DESIGN.md lists
-the per-kernel sizes).  usage: tools/kernel_resources.py > profiles/rNN_kernel_resources.txt"""
+the per-kernel sizes).  usage: tools/kernel_resources.py [source.hip ...] > profiles/rNN_kernel_resources.txt"""
 import os
 import re
 import subprocess
@@ -12,7 +12,10 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "model-based-pde-control_amd", "csrc")
 SOURCES = [("ks_kernels.hip", ["-ffp-contract=off"]), ("sur_kernels.hip", []), ("sur_windows.hip", ["-ffp-contract=off"]),
-           ("burgers.hip", ["-ffp-contract=off"]), ("spectral.hip", []), ("rollout.hip", ["-ffp-contract=off"])]
+           ("burgers.hip", ["-ffp-contract=off"]), ("spectral.hip", []), ("rollout.hip", ["-ffp-contract=off"]),
+           ("collect.hip", ["-ffp-contract=off"])]
+if sys.argv[1:]:                                           # tools/kernel_resources.py collect.hip: these sources only
+    SOURCES = [row for row in SOURCES if row[0] in sys.argv[1:]]
 
 
 def demangle(names):
