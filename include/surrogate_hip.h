@@ -205,6 +205,42 @@ int sur_flush_all_grads(void* stream, const sur_encoder_params* e0, const sur_ad
 int sur_adam_apply(void* stream, const sur_encoder_params* e0, const sur_adam* a0, const sur_encoder_params* e1,
                    const sur_adam* a1, const sur_chunk_params* c2, const sur_adam* a2);
 
+/* Gradient-norm clipping (pl.Trainer's gradient_clip_val, i.e. torch.nn.utils.clip_grad_norm_ over all parameters) for the
+ * step whose Adam update lives on the device: the global norm must be known before the first weight changes, so the
+ * clipped step is TWO launches, sur_flush_all_grads_sumsq then sur_clip_adam_apply, with no trip to the host between them.
+ *
+ * sur_flush_block_count: blocks of sur_flush_all_grads' grid for these three packs (32 columns each, pack by pack) = doubles
+ * of `sumsq` below; <= 0: bad argument. */
+int sur_flush_block_count(const sur_encoder_params* e0, const sur_encoder_params* e1, const sur_chunk_params* c2);
+
+/* sur_flush_all_grads without Adam descriptors, g = sum of the rows (rows re-zeroed; the same bits), and block k also
+ * writes sumsq[k] = the fp64 sum of the squares of the totals it stored (columns past the pack's end count as 0).  The
+ * square of an fp32 value is exact in fp64; the 32 squares of a block are added pairwise, partners 16, 8, 4, 2, 1 columns
+ * apart.  Every pack, partial buffer and g[i] must be non-NULL, and sumsq; -1 otherwise, before any launch. */
+int sur_flush_all_grads_sumsq(void* stream, const sur_encoder_params* e0, const sur_encoder_params* e1,
+                              const sur_chunk_params* c2, double* sumsq);
+
+typedef struct sur_clip {
+    const double* sumsq; int count;   /* what sur_flush_all_grads_sumsq wrote; count = sur_flush_block_count */
+    float max_norm;                   /* > 0 and finite, by value */
+    float* total_norm;                /* DEVICE [1], may be NULL: receives the norm BEFORE clipping */
+} sur_clip;
+
+/* torch.nn.utils.clip_grad_norm_(all three packs, max_norm) followed by sur_adam_apply, in ONE launch.  Every block
+ *   1. folds sumsq[0 .. count) in fp64 in this fixed order: thread j of the block's 256 adds sumsq[j], sumsq[j + 256], ...
+ *      in ascending order; the 64 threads of each wavefront are added pairwise, partners 32, 16, 8, 4, 2, 1 lanes apart;
+ *      the four wavefronts' sums are added in ascending order -- so every block holds the same bits;
+ *   2. total = (float)sqrt(sum);   3. coef = max_norm / (total + 1e-6f) in fp32, then coef = coef > 1 ? 1 : coef;
+ *   4. stores g = g * coef (one fp32 multiply, always, as torch does);   5. feeds that product to the Adam update.
+ * The norm is taken over the three packs together.  A pack whose descriptor is NULL is scaled but not updated (its step
+ * counter stays).  Block 0 alone writes total_norm.  Non-finite values go through the arithmetic as written.  No
+ * floating-point atomics; each updated pack's step counter advances once and its ticket is left at zero.  Refused with -1
+ * before any launch: a NULL pack, partial buffer, clip or clip->sumsq; a count that is not sur_flush_block_count; a
+ * max_norm that is not finite and positive; an incomplete descriptor; a NULL g[i], or a NULL w[i] under a descriptor.
+ * (The partial buffers are not read: a pack without one cannot have been through sur_flush_all_grads_sumsq.) */
+int sur_clip_adam_apply(void* stream, const sur_encoder_params* e0, const sur_adam* a0, const sur_encoder_params* e1,
+                        const sur_adam* a1, const sur_chunk_params* c2, const sur_adam* a2, const sur_clip* clip);
+
 /* Delta-mode TBPTT loss in one launch (reference: pdecontrol/surrogates/training.py:100-121):
  *   deltas[b,t]  = ((states[b,t+1] - states[b,t]) / delta - mean) / stdv          t < T-1   (undscaling forward)
  *   loss         = mean over (b, t < T-1, i) of (d_all[t,b,i] - deltas[b,t,i])^2  (MSE, reduction "none" + mean)

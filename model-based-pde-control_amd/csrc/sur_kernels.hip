@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -3076,9 +3077,14 @@ __device__ __forceinline__ void adam_finish_step(const sur_adam& adam, int step,
     }
 }
 
-template <int NP, typename Params>
+// SUMSQ: `sumsq` receives the fp64 sum of the squares of the block's FLUSH_COLS column totals, columns past the pack's end
+// counting as 0: the square of an fp32 value is exact in fp64, and the 32 squares -- held by lanes 0 .. 31 of the block's
+// first wavefront -- are added by a butterfly over partners 16, 8, 4, 2, 1 lanes apart (five roundings deep).  A template
+// switch, so that the instantiations without it are the code they have always been.  SUMSQ squares the column total, which
+// is the stored gradient only when the total overwrites g: a SUMSQ caller passes overwrite = true and no Adam descriptor.
+template <int NP, typename Params, bool SUMSQ = false>
 __device__ __forceinline__ void flush_grads_body(const Params& p, int psize, const sur_adam& adam, bool overwrite, int blk,
-                                                 int nblk) {
+                                                 int nblk, double* sumsq = nullptr) {
     // block = FLUSH_COLS columns x FLUSH_RG row groups: each thread sums every FLUSH_RG-th row of its column, LDS combines
     // the partials (a wave reads 2 rows x 128 contiguous bytes per load instruction).  The kernel is a chain of memory
     // round trips (rows -> LDS -> Adam state -> ticket), so whatever does not depend on the sum is fetched FIRST: the row
@@ -3116,6 +3122,19 @@ __device__ __forceinline__ void flush_grads_body(const Params& p, int psize, con
             *gdst += tot;
         }
     }
+    if constexpr (SUMSQ) {
+        static_assert(FLUSH_COLS == 32, "the butterfly below spans the 32 finishers of a block");
+        if (threadIdx.x < 64) {   // the first wavefront: row groups 0 (the finishers) and 1 (whose lanes add 0)
+            double sq = 0.0;
+            if (finisher) {
+                const float tot = combine_row_groups(part, col);   // the bits just stored: LDS has not changed since
+                sq = (double)tot * (double)tot;
+            }
+#pragma unroll
+            for (int off = FLUSH_COLS / 2; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
+            if (threadIdx.x == 0) *sumsq = sq;
+        }
+    }
     if (adam.m) adam_finish_step(adam, step, nblk);
 }
 
@@ -3133,6 +3152,19 @@ flush_all_kernel(const sur_encoder_params e0, const sur_adam a0, int n0, const s
     if (blk < b0) flush_grads_body<SUR_ENC_NPARAM, sur_encoder_params>(e0, n0, a0, overwrite_mask & 1, blk, b0);
     else if (blk < b0 + b1) flush_grads_body<SUR_ENC_NPARAM, sur_encoder_params>(e1, n1, a1, overwrite_mask & 2, blk - b0, b1);
     else flush_grads_body<SUR_ST_NPARAM, sur_chunk_params>(c2, n2, a2, overwrite_mask & 4, blk - b0 - b1, b2);
+}
+
+// flush_all_kernel without Adam, g = sum of the rows, and block k's sum of squares in sumsq[k]: the first of the two launches
+// of a step whose gradient norm is clipped (clip_adam_kernel below is the second)
+__global__ void __launch_bounds__(FLUSH_TPB)
+flush_all_sumsq_kernel(const sur_encoder_params e0, int n0, const sur_encoder_params e1, int n1, const sur_chunk_params c2, int n2,
+                       double* __restrict__ sumsq) {
+    const int b0 = flush_blocks(n0), b1 = flush_blocks(n1), b2 = flush_blocks(n2);
+    const int blk = blockIdx.x;
+    const sur_adam none{};
+    if (blk < b0) flush_grads_body<SUR_ENC_NPARAM, sur_encoder_params, true>(e0, n0, none, true, blk, b0, sumsq + blk);
+    else if (blk < b0 + b1) flush_grads_body<SUR_ENC_NPARAM, sur_encoder_params, true>(e1, n1, none, true, blk - b0, b1, sumsq + blk);
+    else flush_grads_body<SUR_ST_NPARAM, sur_chunk_params, true>(c2, n2, none, true, blk - b0 - b1, b2, sumsq + blk);
 }
 
 // Fold the partial-gradient rows [base, base + count) of up to three packs into ONE row each (dst += their sum, fixed order)
@@ -3186,6 +3218,54 @@ adam_all_kernel(const sur_encoder_params e0, const sur_adam a0, int n0, const su
     if (blk < b0) adam_apply_body<SUR_ENC_NPARAM, sur_encoder_params>(e0, n0, a0, blk, b0);
     else if (blk < b0 + b1) adam_apply_body<SUR_ENC_NPARAM, sur_encoder_params>(e1, n1, a1, blk - b0, b1);
     else adam_apply_body<SUR_ST_NPARAM, sur_chunk_params>(c2, n2, a2, blk - b0 - b1, b2);
+}
+
+// torch.nn.utils.clip_grad_norm_ over the three packs together, then adam_all_kernel's update, in one launch.  Every block
+// folds the per-block sums of squares of flush_all_sumsq_kernel itself, in one fixed order (include/surrogate_hip.h), so all
+// blocks scale by the same bits and nothing waits for another block: thread j adds sumsq[j], sumsq[j + TPB], ... in ascending
+// order, a butterfly (partners 32 .. 1 lanes apart) combines the 64 threads of a wavefront, the wavefronts' sums are added in
+// ascending order.
+__device__ __forceinline__ double fold_sumsq(const double* __restrict__ sumsq, int count) {
+    __shared__ double wave_sum[TPB / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < count; i += TPB) acc += sumsq[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x / 64] = acc;
+    __syncthreads();
+    double total = 0.0;
+#pragma unroll
+    for (int w = 0; w < TPB / 64; ++w) total += wave_sum[w];
+    return total;
+}
+
+// g *= coef (always multiplied, as torch does), then the update of adam_apply_body from the scaled gradient; a pack without
+// a descriptor is scaled only
+template <int NP, typename Params>
+__device__ __forceinline__ void clip_adam_body(const Params& p, int psize, const sur_adam& adam, float coef, int blk, int nblk) {
+    const int t = blk * TPB + threadIdx.x;
+    if (t < psize) {
+        float* g = nullptr;
+        float* w = nullptr;
+        locate_param<NP>(p, t, g, w);
+        *g = *g * coef;
+    }
+    if (adam.m) adam_apply_body<NP, Params>(p, psize, adam, blk, nblk);   // each thread reads back the element it has just stored
+}
+
+__global__ void __launch_bounds__(TPB)
+clip_adam_kernel(const sur_encoder_params e0, const sur_adam a0, int n0, const sur_encoder_params e1, const sur_adam a1, int n1,
+                 const sur_chunk_params c2, const sur_adam a2, int n2, const double* __restrict__ sumsq, int count, float max_norm,
+                 float* __restrict__ total_norm) {
+    const float total = (float)sqrt(fold_sumsq(sumsq, count));
+    float coef = max_norm / (total + 1e-6f);
+    coef = coef > 1.0f ? 1.0f : coef;
+    const int b0 = (n0 + TPB - 1) / TPB, b1 = (n1 + TPB - 1) / TPB, b2 = (n2 + TPB - 1) / TPB;
+    const int blk = blockIdx.x;
+    if (total_norm != nullptr && blk == 0 && threadIdx.x == 0) *total_norm = total;
+    if (blk < b0) clip_adam_body<SUR_ENC_NPARAM, sur_encoder_params>(e0, n0, a0, coef, blk, b0);
+    else if (blk < b0 + b1) clip_adam_body<SUR_ENC_NPARAM, sur_encoder_params>(e1, n1, a1, coef, blk - b0, b1);
+    else clip_adam_body<SUR_ST_NPARAM, sur_chunk_params>(c2, n2, a2, coef, blk - b0 - b1, b2);
 }
 
 template <typename F>
@@ -3852,6 +3932,61 @@ int sur_flush_all_grads(void* stream, const sur_encoder_params* e0, const sur_ad
         hipLaunchKernelGGL(flush_all_kernel, dim3(grid), dim3(FLUSH_TPB), 0, (hipStream_t)stream, *e0, ad[0], n0, *e1, ad[1], n1, *c2, ad[2],
                            n2, overwrite_mask);
     }, "flush_all");
+}
+
+// the three packs of the clipped step's two launches: all present, every gradient tensor, and the weights under a descriptor
+static int check_clip_packs(const char* who, const sur_encoder_params* e0, const sur_adam* a0, const sur_encoder_params* e1,
+                            const sur_adam* a1, const sur_chunk_params* c2, const sur_adam* a2) {
+    if (!e0 || !e1 || !c2) return fail(-1, "%s: bad argument (a NULL parameter pack)", who);
+    if (int rc = check_pack_tensors<SUR_ENC_NPARAM>(who, "encoder 0 ", *e0, a0 != nullptr)) return rc;
+    if (int rc = check_pack_tensors<SUR_ENC_NPARAM>(who, "encoder 1 ", *e1, a1 != nullptr)) return rc;
+    return check_pack_tensors<SUR_ST_NPARAM>(who, "chunk ", *c2, a2 != nullptr);
+}
+
+int sur_flush_block_count(const sur_encoder_params* e0, const sur_encoder_params* e1, const sur_chunk_params* c2) {
+    if (!e0 || !e1 || !c2) return fail(-1, "sur_flush_block_count: bad argument (a NULL parameter pack)");
+    return flush_blocks(psize_of<SUR_ENC_NPARAM>(e0->size)) + flush_blocks(psize_of<SUR_ENC_NPARAM>(e1->size)) +
+           flush_blocks(psize_of<SUR_ST_NPARAM>(c2->size));
+}
+
+int sur_flush_all_grads_sumsq(void* stream, const sur_encoder_params* e0, const sur_encoder_params* e1, const sur_chunk_params* c2,
+                              double* sumsq) {
+    const char* who = "sur_flush_all_grads_sumsq";
+    if (int rc = check_clip_packs(who, e0, nullptr, e1, nullptr, c2, nullptr)) return rc;
+    if (!e0->partial || !e1->partial || !c2->partial) return fail(-1, "%s: bad argument (a NULL partial buffer)", who);
+    if (!sumsq) return fail(-1, "%s: bad argument (sumsq is NULL)", who);
+    const int n0 = psize_of<SUR_ENC_NPARAM>(e0->size), n1 = psize_of<SUR_ENC_NPARAM>(e1->size), n2 = psize_of<SUR_ST_NPARAM>(c2->size);
+    const int grid = flush_blocks(n0) + flush_blocks(n1) + flush_blocks(n2);
+    if (grid <= 0) return fail(-1, "%s: bad argument (empty parameter packs)", who);
+    return launch_checked([&] {
+        hipLaunchKernelGGL(flush_all_sumsq_kernel, dim3(grid), dim3(FLUSH_TPB), 0, (hipStream_t)stream, *e0, n0, *e1, n1, *c2, n2, sumsq);
+    }, "flush_all_sumsq");
+}
+
+int sur_clip_adam_apply(void* stream, const sur_encoder_params* e0, const sur_adam* a0, const sur_encoder_params* e1,
+                        const sur_adam* a1, const sur_chunk_params* c2, const sur_adam* a2, const sur_clip* clip) {
+    const char* who = "sur_clip_adam_apply";
+    const sur_adam* in[3] = {a0, a1, a2};
+    sur_adam ad[3] = {};
+    for (int j = 0; j < 3; ++j)
+        if (in[j]) {
+            if (!adam_complete(*in[j])) return fail(-1, "%s: incomplete Adam descriptor %d", who, j);
+            ad[j] = *in[j];
+        }
+    if (int rc = check_clip_packs(who, e0, a0, e1, a1, c2, a2)) return rc;
+    // not read here, but a pack without its rows cannot have been through sur_flush_all_grads_sumsq
+    if (!e0->partial || !e1->partial || !c2->partial) return fail(-1, "%s: bad argument (a NULL partial buffer)", who);
+    if (!clip || !clip->sumsq) return fail(-1, "%s: bad argument (%s is NULL)", who, clip ? "sumsq" : "clip");
+    if (clip->count <= 0 || clip->count != sur_flush_block_count(e0, e1, c2))
+        return fail(-1, "%s: count is %d, sur_flush_block_count of these packs %d", who, clip->count, sur_flush_block_count(e0, e1, c2));
+    if (!(clip->max_norm > 0.0f) || !std::isfinite(clip->max_norm))
+        return fail(-1, "%s: max_norm is %g (finite and > 0)", who, (double)clip->max_norm);
+    const int n0 = psize_of<SUR_ENC_NPARAM>(e0->size), n1 = psize_of<SUR_ENC_NPARAM>(e1->size), n2 = psize_of<SUR_ST_NPARAM>(c2->size);
+    const int grid = (n0 + TPB - 1) / TPB + (n1 + TPB - 1) / TPB + (n2 + TPB - 1) / TPB;
+    return launch_checked([&] {
+        hipLaunchKernelGGL(clip_adam_kernel, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, *e0, ad[0], n0, *e1, ad[1], n1, *c2, ad[2],
+                           n2, clip->sumsq, clip->count, clip->max_norm, clip->total_norm);
+    }, "clip_adam");
 }
 
 int sur_fold_rows(void* stream, const sur_encoder_params* e0, const sur_encoder_params* e1, const sur_chunk_params* c2,

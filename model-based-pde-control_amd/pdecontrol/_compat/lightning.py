@@ -69,6 +69,8 @@ except ImportError:
             module.__dict__["_shim_schedulers"] = [s["scheduler"] for s in schedulers]
             module.train()
             manual = not getattr(module, "automatic_optimization", True)
+            if manual:      # the clip below never runs: the module's own optimizer step reads the value from here
+                module.__dict__["_trainer_gradient_clip_val"] = self.gradient_clip_val
             for _ in range(self.max_epochs):
                 for bidx, batch in enumerate(loader):
                     if 0 <= self.max_steps <= self.global_step:

@@ -437,9 +437,15 @@ class PDEModelBasedController:
         phase = self._phase()
         training_config = dict(self.config.training[phase])
         trainer_config = self.config.trainer[phase]
+        algorithm = trainer_config.get("gradient_clip_algorithm")
+        if algorithm not in (None, "norm"):
+            raise ValueError(f"trainer config: gradient_clip_algorithm is {algorithm!r}, and only 'norm' (gradient_clip_val "
+                             f"as a bound on the global gradient norm) is built")
         if self.device.type == "cuda":
             training_config.setdefault("device_data", self.device)
         forced = {"tier": "loop"} if self.phase_tiers == "loop" else {}   # the datamodule's own loaders
+        if trainer_config.get("gradient_clip_val") is not None:           # the trainer's own key (reference mbrl.py:357-365)
+            forced["gradient_clip_val"] = trainer_config["gradient_clip_val"]
         datamodule = PDEDataModule(data=self.replay.data, train=train, val=val, tau=self.tau, stransf=self.replay_to_world,
                                    curriculum=self.curriculum, iteration=self.iteration, bootstrapping=True,
                                    **training_config)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from pdecontrol.mbrl.recognition import Unrecognized, notice, same_device, world_connector
+from pdecontrol.surrogates.graph_step import clip_value
 
 METRICS = ("Val. Loss", "Val. Scaled Loss", "Val. Delta Loss")
 
@@ -205,8 +206,9 @@ def _captured_lr(module, fit):
     return module.lr * module.lr_gamma ** (fit.current_epoch // module.step_size)
 
 
-def _train_loop(module, fit, loader, target, fused):
+def _train_loop(module, fit, loader, target, fused, clip=None):
     """One epoch over the datamodule's loader; True when the step target cut it."""
+    clipped = {} if clip is None else {"clip": clip}        # without a clip: the calls as they have always been
     module.train()
     if not fused and fit.optimizers is None:
         optimizers, schedulers = module.configure_optimizers()
@@ -215,12 +217,14 @@ def _train_loop(module, fit, loader, target, fused):
         if fit.global_step >= target:
             return True
         if fused:
-            module.fused_step(batch, lr=_captured_lr(module, fit))
+            module.fused_step(batch, lr=_captured_lr(module, fit), **clipped)
         else:                                   # the shim's closure order: training_step -> zero_grad -> backward -> step
             opt = fit.optimizers[0]
             out = module.training_step(batch, bidx)
             opt.zero_grad(set_to_none=True)
             out["loss"].backward()
+            if clip is not None:
+                torch.nn.utils.clip_grad_norm_(module.surrogate.parameters(), clip)
             opt.step()
         fit.global_step += 1
     if not fused:
@@ -229,15 +233,16 @@ def _train_loop(module, fit, loader, target, fused):
     return fit.global_step >= target
 
 
-def _train_kernel(module, tier, fit, loader, target, batch_size):
+def _train_kernel(module, tier, fit, loader, target, batch_size, clip=None):
     module.train()
     first, n, l = tier.plan(loader)
     lr = _captured_lr(module, fit)
+    clipped = {} if clip is None else {"clip": clip}
     for i0 in range(0, n, batch_size):
         if fit.global_step >= target:
             return True
         b = min(batch_size, n - i0)
-        step = module.graphed_step_for(*tier.shapes(b, l), lr=lr)      # captured on first use; keeps the valid() check
+        step = module.graphed_step_for(*tier.shapes(b, l), lr=lr, **clipped)   # captured on first use; keeps the valid() check
         tier.gather(first, i0, b, l, step.states, step.actions)
         step.step(lr=lr)
         fit.global_step += 1
@@ -247,7 +252,8 @@ def _train_kernel(module, tier, fit, loader, target, batch_size):
 # ----------------------------------------------------------------------------------------------------------------------
 # the phase
 # ----------------------------------------------------------------------------------------------------------------------
-def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience, max_epochs=None, timings=None, tier=None):
+def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience, max_epochs=None, timings=None, tier=None,
+                     gradient_clip_val=None):
     """Fits ``module`` on ``datamodule`` and returns the last epoch's "Val. Loss" as a float: ``reset_trainer`` +
     ``trainer.fit`` + ``logged_metrics["Val. Loss"]`` of the reference (mbrl.py:568-595), with ``fit`` (a ``FitState``)
     in the trainer's place.  The rule below is this repository's reading of that fit loop; it is unpinned against
@@ -258,6 +264,10 @@ def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience,
     - **Per epoch, training:** call `datamodule.train_dataloader()`. It builds its `SubSeqDataset`, so the bootstrap
       `np.random.randint` draw and the curriculum lookup happen exactly as in the loop. Train over its batches in order,
       and stop mid-epoch when the step target is reached.
+    - **Per training step, clipping:** with `gradient_clip_val` > 0 (the trainer's key; `None` or <= 0 is none) the
+      gradient of all the surrogate's parameters is scaled to that norm between backward and the optimizer step
+      (`clip_grad_norm_`), on every route: inside the captured step on the kernel tier and under `fused_step`, by
+      torch in the closure order.
     - **Per epoch, validation:** call `datamodule.val_dataloader()`. Its epoch "Val. Loss" is the sample-weighted mean
       over batches.
     - **Early stopping** (mode min, min_delta 0):
@@ -303,6 +313,7 @@ def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience,
     datamodule.trainer = fit
     if tier not in (None, "loop"):
         raise ValueError(f"tier is {tier!r}: None or 'loop'")
+    clip = clip_value(gradient_clip_val)
     tier, reason = (None, "the loop tier was asked for") if tier == "loop" else _pick_tier(module, datamodule)
     fit.tier, fit.tier_reason = ("kernel", None) if tier is not None else ("loop", reason)
     if tier is None:
@@ -315,9 +326,9 @@ def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience,
         loader = datamodule.train_dataloader()
         t = lap("plan_s", t)
         if tier is not None:
-            cut = _train_kernel(module, tier, fit, loader, target, batch_size)
+            cut = _train_kernel(module, tier, fit, loader, target, batch_size, clip)
         else:
-            cut = _train_loop(module, fit, loader, target, fused)
+            cut = _train_loop(module, fit, loader, target, fused, clip)
         t = lap("train_s", t)
         loader = datamodule.val_dataloader()
         t = lap("plan_s", t)

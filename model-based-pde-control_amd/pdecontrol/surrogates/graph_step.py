@@ -7,7 +7,8 @@ launch cost, no host synchronisation inside the step.
 
 Single GPU : [ zero grads | forward | backward | Adam ]                       = one graph
              (on the fused kernels: [ forward | backward ] only -- the launches that reduce the partial
-             gradient rows apply the Adam update themselves, and nothing needs zeroing)
+             gradient rows apply the Adam update themselves, and nothing needs zeroing; with ``clip`` the
+             reduction also writes per-block sums of squares and ONE more launch clips the norm and applies Adam)
 Data parallel: [ zero | forward | backward ] -> all-reduce(flat bucket) -> [ Adam ]  = two graphs with one
              RCCL call between them (pdecontrol.surrogates.distributed.FlatGradBucket).
 
@@ -29,6 +30,13 @@ import os
 import torch
 
 from pdecontrol.surrogates.distributed import FlatGradBucket
+
+
+def clip_value(gradient_clip_val):
+    """pl.Trainer's rule for ``gradient_clip_val``: None or a value <= 0 is no clipping (None), anything else the bound."""
+    if gradient_clip_val is None or float(gradient_clip_val) <= 0.0:
+        return None
+    return float(gradient_clip_val)
 
 
 def capture_graph(graph, fn, stream):
@@ -113,10 +121,19 @@ class GraphedTBPTTStep:
     """``step()`` replays one optimizer step of ``module`` for one batch shape."""
 
     def __init__(self, module, batch_shape, action_shape=None, lr=None, distributed=False, warmup=3, capture=True,
-                 pipelined=None):
+                 pipelined=None, clip=None):
         """module: PDETrainingModule on a CUDA device; batch_shape: [B, T, 1, N] of states.
         capture=False prepares everything (static buffers, warmed-up kernels, optimizer state) but leaves
-        the capture to the caller (EnsembleTBPTTStep records several members into one graph)."""
+        the capture to the caller (EnsembleTBPTTStep records several members into one graph).
+        clip: pl.Trainer's ``gradient_clip_val`` -- ``clip_grad_norm_`` over all the surrogate's parameters between the
+        backward pass and the Adam update, inside the graph (None or <= 0: no clipping, Lightning's rule).  ``grad_norm`` is
+        then the static device scalar that holds the norm BEFORE clipping of the last replay, and ``param.grad`` the clipped
+        gradient."""
+        self.clip = clip_value(clip)
+        if self.clip is not None and distributed:
+            # there the clip belongs between the all-reduce and the optimizer graph, which is not built
+            raise ValueError("GraphedTBPTTStep: gradient clipping (clip) is not available in the data-parallel captured step")
+        self.grad_norm = self._clip_desc = None
         self.module = module
         # pipelined: chunk c's backward beside chunk c+1's forward (hipops.fused_tbptt_train).  True / False force one schedule;
         # None (default, PDECONTROL_PIPELINED=auto) captures both and keeps the faster one: the pipelined graph needs its two
@@ -221,8 +238,15 @@ class GraphedTBPTTStep:
                 betas, eps = (0.9, 0.999), 1e-8
                 self._adam_state = packs.adam_descriptors(self.shared.lr, betas, eps)
                 self.adam_in_flush = True
+                if self.clip is not None:
+                    # the captured tail becomes two launches: reduction + per-block sums of squares, clip + Adam
+                    self._clip_desc = packs.clip_descriptor(self.clip)
+                    self.grad_norm = packs.grad_norm
+                    self._clip_packs = packs   # owns the buffers whose addresses the captured launches carry by value
             else:
                 self.shared.torch_adam()
+                if self.clip is not None:
+                    self.grad_norm = torch.zeros(1, device=self.device, dtype=torch.float32)
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         torch.cuda.synchronize(self.device)
 
@@ -280,6 +304,9 @@ class GraphedTBPTTStep:
             with self.capturing():
                 res = self._fwd_bwd()
             if not self.adam_in_flush and not self.distributed:
+                if self.clip is not None:
+                    norm = torch.nn.utils.clip_grad_norm_(self.shared._params, self.clip)
+                    self.grad_norm.copy_(norm.reshape(1))
                 self.shared.opt.step()
             return res
 
@@ -312,7 +339,7 @@ class _LendAdam:
 
     def __enter__(self):
         if self.step.adam_in_flush:
-            self.step.module.surrogate._fused_packs.lend_adam(self.step._adam_state)
+            self.step.module.surrogate._fused_packs.lend_adam(self.step._adam_state, clip=self.step._clip_desc)
 
     def __exit__(self, *exc):
         if self.step.adam_in_flush:

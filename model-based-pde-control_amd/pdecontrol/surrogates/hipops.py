@@ -12,6 +12,7 @@ differentiable even when their data inputs are not.
 There is no fallback in here: if the library is missing, ``load()`` raises.
 """
 import ctypes
+import math
 import os
 
 import types
@@ -45,6 +46,11 @@ class ChunkParams(ctypes.Structure):
 class AdamParams(ctypes.Structure):
     _fields_ = [("m", _fp), ("v", _fp), ("step", _fp), ("ticket", _fp), ("lr", _fp), ("beta1", ctypes.c_float),
                 ("beta2", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
+class ClipParams(ctypes.Structure):
+    """``sur_clip``: the per-block sums of squares, the norm bound and where the pre-clip norm goes."""
+    _fields_ = [("sumsq", _fp), ("count", ctypes.c_int), ("max_norm", ctypes.c_float), ("total_norm", _fp)]
 
 
 class ChunkSpan(ctypes.Structure):
@@ -84,6 +90,9 @@ SYMBOLS = (
     ("sur_flush_chunk_grads", _i, [_fp, _CP, _AP, _i]),
     ("sur_flush_all_grads", _i, [_fp, _EP, _AP, _EP, _AP, _CP, _AP, _i]),
     ("sur_adam_apply", _i, [_fp, _EP, _AP, _EP, _AP, _CP, _AP]),
+    ("sur_flush_block_count", _i, [_EP, _EP, _CP]),
+    ("sur_flush_all_grads_sumsq", _i, [_fp, _EP, _EP, _CP, _fp]),
+    ("sur_clip_adam_apply", _i, [_fp, _EP, _AP, _EP, _AP, _CP, _AP, ctypes.POINTER(ClipParams)]),
     ("sur_tbptt_delta_loss", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                   ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     ("sur_chunk_integrate", _i, [_fp, _CP, _fp, _fp, _i, _i, _i, _fp]),
@@ -410,6 +419,9 @@ class FusedPacks:
         self.loss_scratch = {}
         self.lr_dev = torch.zeros(1, device=dev, dtype=torch.float32)   # Adam's learning rate, read by the flush launch
         self._lr_host = None
+        self.clip = None            # a ClipParams while a clipped optimizer step runs inside the flush (lend_adam)
+        self._clip_buffers = None   # (per-block sums of squares, pre-clip norm), created by clip_descriptor
+        self.grad_norm = None
 
     @staticmethod
     def _key(surrogate, n):
@@ -438,6 +450,20 @@ class FusedPacks:
             return
         for pack in dirty:
             pack.resolve_grads()
+        if self.clip is not None:
+            # a clipped step (lend_adam(..., clip=...)): the reduction with the per-block sums of squares, then ONE launch that
+            # folds them into the norm of all three packs, scales the gradients and applies Adam
+            if len(dirty) != 3:
+                raise SurrogateHipError("gradient-norm clipping inside the flush needs the gradients of all three parameter "
+                                        "packs from the same backward pass")
+            ad = lambda pack: None if pack.adam is None else ctypes.byref(pack.adam[0])
+            refs = [ctypes.byref(pack.c) for pack in self.packs]
+            _check(load().sur_flush_all_grads_sumsq(_stream(), refs[0], refs[1], refs[2], self.clip.sumsq))
+            _check(load().sur_clip_adam_apply(_stream(), refs[0], ad(self.state_enc), refs[1], ad(self.action_enc), refs[2],
+                                              ad(self.chunk), ctypes.byref(self.clip)))
+            for pack in dirty:
+                pack.dirty = False
+            return
         if len(dirty) == 3:   # the usual case: one launch reduces (and, with Adam enabled, applies) all three packs
             ad = lambda pack: None if pack.adam is None else ctypes.byref(pack.adam[0])
             mask = sum((1 << j) for j, pack in enumerate(self.packs) if pack.overwrite and pack.adam is None)
@@ -482,13 +508,32 @@ class FusedPacks:
         for pack in self.packs:
             pack.reset_adam()
 
-    def lend_adam(self, descriptors):
+    def clip_descriptor(self, max_norm):
+        """``sur_clip`` for ``lend_adam``: clip the norm of all three packs' gradients to ``max_norm`` before the Adam update.
+        The per-block sums of squares and the one-float pre-clip norm (``grad_norm``) are allocated once per packs object,
+        here, outside any capture; every descriptor handed out points at them."""
+        max_norm = float(max_norm)
+        if not (math.isfinite(max_norm) and max_norm > 0.0):
+            raise ValueError(f"gradient-norm bound {max_norm!r}: finite and > 0")
+        count = load().sur_flush_block_count(*(ctypes.byref(pack.c) for pack in self.packs))
+        if count <= 0:
+            _check(count)
+        if self._clip_buffers is None:
+            dev = self.chunk.params[0].device
+            self._clip_buffers = (torch.zeros(count, device=dev, dtype=torch.float64), torch.zeros(1, device=dev, dtype=torch.float32))
+        sumsq, self.grad_norm = self._clip_buffers
+        assert sumsq.numel() == count
+        return ClipParams(sumsq.data_ptr(), count, max_norm, self.grad_norm.data_ptr())
+
+    def lend_adam(self, descriptors, clip=None):
         for pack, d in zip(self.packs, descriptors):
             pack.adam = d
+        self.clip = clip
 
     def disable_adam(self):
         for pack in self.packs:
             pack.disable_adam()
+        self.clip = None
 
     def schedule_flush(self):
         """Called from inside a backward: run ``flush`` when the current backward pass finishes."""

@@ -251,20 +251,24 @@ class PDETrainingModule(pl.LightningModule):
                 "actions": actions.detach(), "states": states.detach(), "outdeltas": outdeltas.detach(),
                 "deltas": deltas.detach()}
 
-    def fused_step(self, batch, lr=None):
+    def fused_step(self, batch, lr=None, clip=None):
         """One optimizer step -- training_step + backward + Adam(lr) -- as ONE replayed HIP graph on static
         buffers (pdecontrol.surrogates.graph_step.GraphedTBPTTStep; a graph per batch shape, captured on first
         use; ONE Adam state and learning rate for all of them).  Returns training_step's dict; its tensors are
-        overwritten by the next call.  CUDA only."""
+        overwritten by the next call.  CUDA only.  ``clip``: pl.Trainer's ``gradient_clip_val`` (``clip_grad_norm_`` between
+        backward and Adam, inside the graph); None or <= 0 is no clipping and exactly the unclipped graph."""
         states, actions, *_ = batch
-        return self.graphed_step_for(states.shape, actions.shape, lr=lr).step(states, actions, lr=lr)
+        return self.graphed_step_for(states.shape, actions.shape, lr=lr, clip=clip).step(states, actions, lr=lr)
 
-    def graphed_step_for(self, states_shape, actions_shape, lr=None):
-        """The captured step of ``fused_step`` for one batch shape (captured on first use, re-captured once it is no longer
-        ``valid()``).  A caller that fills its static ``states`` / ``actions`` itself -- the surrogate-update phase's window
-        gather -- replays it with ``step()``."""
-        from pdecontrol.surrogates.graph_step import GraphedTBPTTStep
+    def graphed_step_for(self, states_shape, actions_shape, lr=None, clip=None):
+        """The captured step of ``fused_step`` for one batch shape and one clip value (captured on first use, re-captured once
+        it is no longer ``valid()``).  A caller that fills its static ``states`` / ``actions`` itself -- the surrogate-update
+        phase's window gather -- replays it with ``step()``."""
+        from pdecontrol.surrogates.graph_step import GraphedTBPTTStep, clip_value
+        clip = clip_value(clip)
         key = (tuple(states_shape), tuple(actions_shape))
+        if clip is not None:
+            key += (clip,)
         cache = self.__dict__.setdefault("_graphed_steps", {})
         trained = self.__dict__.get("_graphed_trained")
         stale = key not in cache or not cache[key].valid()
@@ -282,7 +286,7 @@ class PDETrainingModule(pl.LightningModule):
             # (forward/backward graph -> one flat-bucket all-reduce -> Adam graph), never train the ranks apart silently
             dist = torch.distributed
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-            cache[key] = GraphedTBPTTStep(self, key[0], key[1], lr=lr, distributed=distributed)
+            cache[key] = GraphedTBPTTStep(self, key[0], key[1], lr=lr, distributed=distributed, clip=clip)
         self.__dict__["_last_graphed_step"] = cache[key]
         return cache[key]
 
@@ -296,7 +300,8 @@ class PDETrainingModule(pl.LightningModule):
             lr = float(opt.param_groups[0]["lr"])
         except Exception:   # no trainer attached (direct call): the module's own lr
             lr = None
-        out = self.fused_step(batch, lr=lr)
+        # manual optimization: Lightning's own clip never runs, so the shim Trainer leaves its gradient_clip_val here
+        out = self.fused_step(batch, lr=lr, clip=self.__dict__.get("_trainer_gradient_clip_val"))
         if lr is not None:
             opt.step()      # bookkeeping only (_GraphOwnedAdam): keeps scheduler / Lightning step counters consistent
         # the five "Train ..." metrics of the step that was just replayed (static tensors of that captured step)
