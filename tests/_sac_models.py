@@ -161,10 +161,12 @@ def cast_batch(batch, dtype=None, device=None):
     return tuple(t.to(device=device, dtype=dtype if t.is_floating_point() else None) for t in batch)
 
 
-def terms(agent, batch, noises):
+def terms(agent, batch, noises, terminated=None):
     """Losses and gradients of one update of ``agent`` at its current state, in its own dtype on its own device, with the
-    policy gradient taken against the not-yet-updated critic (what ``sac_grads`` computes)."""
-    obs, actions, nxtobs, rewards, terminated, _ = agent._prepare(batch)
+    policy gradient taken against the not-yet-updated critic (what ``sac_grads`` computes).  ``terminated`` (a float [B]
+    vector such as ``flagged(B)``) replaces the batch's flags past the host assert of ``_prepare``."""
+    obs, actions, nxtobs, rewards, flags, _ = agent._prepare(batch)
+    terminated = flags if terminated is None else terminated.to(device=obs.device).reshape(flags.shape)
     n_next, n_cur = (n.to(device=obs.device, dtype=obs.dtype) for n in noises)
     with torch.no_grad():
         a2, lp2, _ = agent.policy.sample(nxtobs, noise=n_next)
@@ -286,3 +288,154 @@ def adam_units(p, m, v, g, got_p, got_m, got_v, ref):
 def polyak_units(target, p_new, got, ref):
     target, p_new = _f64(target), _f64(p_new)
     return _worst_units(got, ref, U * np.maximum(np.abs(target), np.abs(p_new)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the head where it clamps and saturates: regimes, a cancellation-free yardstick, terminated flags
+# ---------------------------------------------------------------------------------------------------------------------
+_F32 = np.float32
+#: regime -> (log_std bias pattern, mean bias pattern), cycled over the action components (component j takes entry j % 4)
+HEAD_REGIMES = {
+    # clamped below, inside, clamped above, inside; a standard deviation of e^2 carries the pre-tanh value to |x| ~ 30
+    "mixed": ([-25.0, -1.0, 3.5, 0.5], [0.0, 6.0, -9.0, 0.3]),
+    # nothing clamped; |x| ~ 6 ... 9 in both signs, where scale * sech^2 crosses the 1e-6 floor inside the logarithm
+    "knee": ([-1.0, -2.0, -1.5, -3.0], [7.0, -6.5, 8.0, -7.5]),
+    # with log_std_linear.weight zeroed the raw log_std is the bias bit for bit: two components on the clamp's edges, two
+    # one fp32 ulp outside
+    "boundary": ([_F32(-20.0), _F32(2.0), np.nextafter(_F32(-20.0), _F32(-np.inf)), np.nextafter(_F32(2.0), _F32(np.inf))],
+                 [0.2, -0.4, 1.0, -1.5]),
+}
+#: (obs_dim, act_dim, B, seed) of the regime tests: test_sac_gpu.py's gradient geometries and one 33-sample batch
+HEAD_GEOMETRIES = [(64, 4, 256, 0), (256, 1, 37, 3), (64, 7, 129, 1), (64, 4, 1, 1), (128, 16, 130, 34), (64, 4, 33, 5)]
+#: the boundary case's floor on min |Q1 - Q2| over the Q scale.  A tie in min(Q1, Q2) flips when the fp32 Q values are off
+#: by the gap; three layers of dot products over K <= 272 terms leave about sqrt(K) 2^-24 ~ 1e-6 of the Q scale, and this
+#: is ten times that (the (64, 4, 33, 5) batch has 2.8e-5 there; the gradient tests keep test_sac_gpu.py's 1e-4)
+BOUNDARY_Q_GAP = 1e-5
+#: (log_std bias, mean bias) of the one-component agents at SINGLE_GEOMETRY: one regime each
+SINGLE_HEADS = [(-25.0, 0.0), (3.5, -9.0), (-1.0, 6.0), (-2.0, -6.5), (0.5, 0.3)]
+SINGLE_GEOMETRY = (64, 1, 17, 2)           # one full 16-sample tile and a one-sample tail
+#: (obs_dim, act_dim, B) of the one-update cases; the agent, batch and noise seeds are B, as in test_one_update_against_fp64
+HEAD_UPDATES = [(64, 4, 256), (128, 16, 100)]
+
+
+def action_box(A):
+    """A box that differs per component: (lo, hi) fp32 [A]."""
+    return np.linspace(-2.0, -0.25, A, dtype=np.float32), np.linspace(0.5, 3.0, A, dtype=np.float32)
+
+
+def set_head(agent, log_std_bias, mean_bias, zero_log_std_weight=False):
+    """Overwrite the policy's two head biases with the patterns cycled over the components and give it the box of
+    ``action_box``.  Call before the first fused call: ``FusedSAC`` copies scale and bias at construction."""
+    pol = agent.policy
+    A = pol.mean_linear.out_features
+    dev, dtype = pol.mean_linear.bias.device, pol.mean_linear.bias.dtype
+    cycle = lambda pattern: torch.tensor([float(_F32(pattern[j % len(pattern)])) for j in range(A)], dtype=torch.float64).to(dev, dtype)
+    with torch.no_grad():
+        pol.log_std_linear.bias.copy_(cycle(log_std_bias))
+        pol.mean_linear.bias.copy_(cycle(mean_bias))
+        if zero_log_std_weight:
+            pol.log_std_linear.weight.zero_()
+    lo, hi = (torch.from_numpy(v) for v in action_box(A))
+    pol.action_scale = ((hi - lo) / 2).reshape(1, A).to(dev, dtype)
+    pol.action_bias = ((hi + lo) / 2).reshape(1, A).to(dev, dtype)
+    return agent
+
+
+def head_regime(agent, name):
+    ls, mean = HEAD_REGIMES[name]
+    return set_head(agent, ls, mean, zero_log_std_weight=name == "boundary")
+
+
+class _Squash(torch.autograd.Function):
+    """x -> (tanh x, sech^2 x) from e = exp(-2|x|), with d tanh / dx = sech^2 and d sech^2 / dx = -2 tanh sech^2: no
+    difference of nearly equal numbers on the way there or back."""
+
+    @staticmethod
+    def forward(ctx, x):
+        e = torch.exp(-2.0 * x.abs())
+        d = 1.0 / (1.0 + e)
+        y, om = torch.sign(x) * (1.0 - e) * d, 4.0 * e * d * d
+        ctx.save_for_backward(y, om)
+        return y, om
+
+    @staticmethod
+    def backward(ctx, gy, gom):
+        y, om = ctx.saved_tensors
+        return gy * om - 2.0 * gom * y * om
+
+
+def stable_sample(policy, state, noise=None):
+    """``GaussianPolicy.sample`` written cancellation-free: Normal.log_prob(mean + noise std) is -noise^2 / 2 - log_std -
+    log(2 pi) / 2 without forming x - mean, and 1 - tanh^2 comes from ``_Squash``.  The yardstick of the regime tests, on an
+    fp32 CPU twin only."""
+    from pdecontrol.sac import policies
+    mean, log_std = policy.forward(state)
+    if noise is None:
+        noise = policies.draw_noise(mean)
+    y, om = _Squash.apply(mean + noise * log_std.exp())
+    action = y * policy.action_scale + policy.action_bias
+    log_prob = -0.5 * noise * noise - log_std - 0.5 * float(np.log(2.0 * np.pi)) - torch.log(policy.action_scale * om + policies.epsilon)
+    return action, log_prob.sum((1, 2)).reshape(-1, 1), torch.tanh(mean) * policy.action_scale + policy.action_bias
+
+
+def stable_twin(agent, logs=None):
+    """The fp32 CPU twin of ``agent`` whose policy samples through ``stable_sample``."""
+    out = twin(agent, torch.float32, logs)
+    pol = out.policy
+    pol.sample = lambda state, noise=None: stable_sample(pol, state, noise)
+    return out
+
+
+def flagged(B):
+    """A float [B] vector of ``terminated`` flags: every third sample (0, 3, 6, ...) is set."""
+    out = torch.zeros(B, dtype=torch.float32)
+    out[::3] = 1.0
+    return out
+
+
+def head_inputs(agent, batch, noises):
+    """(raw log_std, pre-tanh x) of ``agent``'s policy over both samples of an update (next state with the first noise,
+    current state with the second), each [2 B, A], in the agent's dtype."""
+    pol = agent.policy
+    raw, xs = [], []
+    with torch.no_grad():
+        for state, noise in ((batch[2], noises[0]), (batch[0], noises[1])):
+            state = state.squeeze(1).to(pol.linear1.weight.dtype)
+            h = torch.relu(pol.linear2(torch.relu(pol.linear1(state.reshape(state.shape[0], -1)))))
+            ls, mean = pol.log_std_linear(h), pol.mean_linear(h)
+            raw.append(ls)
+            xs.append(mean + noise.reshape(ls.shape).to(ls.dtype) * ls.clamp(-20, 2).exp())
+    return torch.cat(raw), torch.cat(xs)
+
+
+def steps_off(before, after, before64, after64, net, lr):
+    """The share of ``net``'s elements whose step differs from the fp64 step by more than 0.1 lr."""
+    bad = total = 0
+    for k in before:
+        if k.startswith(net + "."):
+            d = (after[k] - before[k]).double() - (after64[k] - before64[k]).double()
+            bad += int((d.abs() > 0.1 * lr).sum())
+            total += d.numel()
+    return bad / total
+
+
+def one_update(agent, batch, noises):
+    """(state before, state after) of one ``update`` of ``agent`` on ``batch`` (cast to the agent's dtype) with stored noise."""
+    dtype = agent.policy.linear1.weight.dtype
+    pre = full_state(agent)
+    with stored_noise(list(noises)):
+        agent.update(cast_batch(batch, dtype))
+    return pre, full_state(agent)
+
+
+def regime_case(regime, obs_dim, act_dim, B, seed, auto=True, device="cpu", flags=None):
+    """An agent in ``regime`` on ``device`` with its fp64 twin, its yardstick twin, the seeded batch and noise, the flags
+    (``flagged(B)`` unless given) and both twins' ``terms`` under them."""
+    agent = head_regime(build(256, auto=auto, obs_dim=obs_dim, act_dim=act_dim, seed=seed, device=device), regime)
+    ref64, yard = twin(agent, torch.float64), stable_twin(agent)
+    batch, noises = make_batch(B, seed, obs_dim, act_dim), noise_pair(B, seed, act_dim)
+    flags = flagged(B) if flags is None else flags
+    t64 = terms(ref64, cast_batch(batch, torch.float64), noises, terminated=flags)
+    ty = terms(yard, batch, noises, terminated=flags)
+    dev = {net: tensor_dev(ty[net], t64[net]) for net in ("critic", "policy")}
+    return Namespace(agent=agent, ref64=ref64, yard=yard, batch=batch, noises=noises, flags=flags, t64=t64, ty=ty, dev=dev)

@@ -15,6 +15,7 @@ Other modes:
   --profile-run        twenty fused updates and twenty ``act`` calls and nothing else: the program to put behind
                        ``rocprofv3 --kernel-trace --stats`` (in a run of its own)
   --parity FILE.jsonl  collect the records tests/test_sac_gpu.py appends (observed deviations) into ``--out``
+  --regimes FILE.jsonl the same for the records of tests/test_sac_head_regimes_gpu.py
 
 Usage (repo root, on an MI355X):  python tools/sac_bench.py --out profiles/sac_bench.json
 """
@@ -92,7 +93,18 @@ def bench(paths, rounds, min_seconds):
     return {k: {"ms": v, "ms_median": round(float(np.median(v)), 4)} for k, v in ms.items()}
 
 
-def collect_parity(path, out):
+PARITY_WHAT = ("deviations tests/test_sac_gpu.py observed on an MI355X: forward outputs and gradients against the CPU "
+               "module in fp64 relative to each tensor's maximum (next to the fp32 torch spelling on the CPU against the "
+               "same fp64), shares of elements whose first Adam step differs from the fp64 step by more than 0.1 lr, "
+               "relative loss differences; from tests/test_sac_optimizer_gpu.py the worst distance, in units (bound 4), of every "
+               "Adam moment, parameter, log_alpha and target element from the fp64 replay of each update")
+REGIMES_WHAT = ("deviations tests/test_sac_head_regimes_gpu.py observed on an MI355X where the tanh-Gaussian head clamps and "
+                "saturates (head regimes of tests/_sac_models.py, every third sample terminated): per case the fused kernels "
+                "against the CPU module in fp64 relative to each tensor's maximum, next to the yardstick (stable_sample on an "
+                "fp32 CPU twin) and, recorded only, the fp32 class (the torch tier's spelling) against the same fp64")
+
+
+def collect_parity(path, out, what=PARITY_WHAT):
     rows = [json.loads(line) for line in open(path) if line.strip()]
     worst = {}
 
@@ -110,12 +122,7 @@ def collect_parity(path, out):
             group = r["case"].split("-")[0] + ":" + key
             if val >= worst.get(group, {"max": -1.0})["max"]:
                 worst[group] = {"max": val, "case": r["case"]}
-    rec = {"what": "deviations tests/test_sac_gpu.py observed on an MI355X: forward outputs and gradients against the CPU "
-                   "module in fp64 relative to each tensor's maximum (next to the fp32 torch spelling on the CPU against the "
-                   "same fp64), shares of elements whose first Adam step differs from the fp64 step by more than 0.1 lr, "
-                   "relative loss differences; from tests/test_sac_optimizer_gpu.py the worst distance, in units (bound 4), of every "
-                   "Adam moment, parameter, log_alpha and target element from the fp64 replay of each update", "worst": worst,
-           "cases": rows}
+    rec = {"what": what, "worst": worst, "cases": rows}
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
@@ -129,9 +136,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--profile-run", action="store_true")
     ap.add_argument("--parity", default=None)
+    ap.add_argument("--regimes", default=None)
     args = ap.parse_args()
     if args.parity:
         return collect_parity(args.parity, args.out or os.path.join(ROOT, "profiles", "sac_parity_observed.json"))
+    if args.regimes:
+        return collect_parity(args.regimes, args.out or os.path.join(ROOT, "profiles", "sac_head_regimes_observed.json"), REGIMES_WHAT)
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda", 0)
     from pdecontrol.surrogates import ops
