@@ -92,6 +92,7 @@ ROLLOUT_CASES = [
     (1, 1, 1, False, False, "every"), (7, 3, 3, True, True, "every"), (64, 5, 10, False, True, "every"),
     (300, 1, 20, True, False, "every"), (1, 5, 10, True, False, "every"), (7, 1, 20, False, True, "every"),
     (64, 1, 1, True, True, "every"), (300, 3, 3, False, False, "every"), (7, 5, 10, True, True, "skip"),
+    (5, 6, 4, False, True, "every"), (7, 1, 2, True, False, "every"),
 ]
 
 
