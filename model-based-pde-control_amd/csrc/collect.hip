@@ -9,7 +9,8 @@
 //
 // The span entries (include/collect/span.h) do a whole segment at once for agents whose actions are known beforehand:
 // co_act_span_kernel owns one wave per (t, e) row; co_span_extrema_kernel reduces the rows of slots 1 ... T to at most
-// CO_SPAN_MAX_PARTS partials with a grid stride, and co_scale_kernel folds them as it folds a step's.
+// CO_SPAN_MAX_PARTS partials with a grid stride, and co_scale_kernel folds them as it folds a step's.  A step is a span
+// of one: co_act and co_observe launch the same two kernels over the E rows of their step.
 //
 // The affine maps are row_ops.h's, so the results equal the host wrappers' bit for bit.
 #include <hip/hip_runtime.h>
@@ -37,23 +38,6 @@ __device__ __forceinline__ void wave_minmax(float& lo, float& hi)
     }
 }
 
-struct ActKernelArgs {
-    co_act_args a;
-    int E, A, t;
-};
-
-__global__ __launch_bounds__(NT) void co_act_kernel(const ActKernelArgs k)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int e = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (e >= k.E || lane >= k.A) return;
-    const long at = (long)e * k.A + lane;
-    const float raw = k.a.action[at];
-    const float env = affine_col(k.a.coef, k.A, lane, raw);
-    k.a.env_action[at] = env;
-    k.a.actions[(long)k.t * k.E * k.A + at] = k.a.record_raw ? raw : env;
-}
-
 struct ActSpanKernelArgs {
     co_act_span_args a;
     long rows;                                                       // T * E
@@ -72,11 +56,11 @@ __global__ __launch_bounds__(NT) void co_act_span_kernel(const ActSpanKernelArgs
     k.a.actions[at] = k.a.record_raw ? raw : env;
 }
 
-// slot: the trajectory slot read; cell_in / cell_out: the bounds cells read and (with update) written
+// slot: the trajectory slot scaled; cell_in / cell_out: the bounds cells read and (with update) written
 struct ObserveKernelArgs {
     co_observe_args a;
     int E, N, O, start, stride, slot, cell_in, cell_out, parts, vec;
-    long rows;                                                       // span: T * E rows from slot 1 on
+    long first, rows;                                                // the rows of [T + 1][E] the extrema are taken over
 };
 
 __device__ __forceinline__ void row_minmax(const float* __restrict__ row, int N, int vec, int lane, float& lo, float& hi)
@@ -119,26 +103,17 @@ __device__ __forceinline__ void store_partial(float* __restrict__ workspace, flo
     }
 }
 
-// launch one: partial[block] = (min, max) over the rows of this workgroup
-__global__ __launch_bounds__(NT) void co_extrema_kernel(const ObserveKernelArgs k)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int e = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    float lo = INFINITY, hi = -INFINITY;
-    if (e < k.E)                                                     // rows past the end keep the identities
-        row_minmax(k.a.traj + ((long)k.slot * k.E + e) * k.N, k.N, k.vec, lane, lo, hi);
-    store_partial(k.a.workspace, lo, hi);
-}
-
-// launch one of a span: partial[block] = (min, max) over the rows block * 4 + wave, + 4 * gridDim.x, ... of slots 1 ... T
-// (the rows of [T + 1][E][N] are contiguous: row r of the span is row E + r of the block)
+// launch one: partial[block] = (min, max) over the rows block * 4 + wave, + 4 * gridDim.x, ... of the span (the rows of
+// [T + 1][E][N] are contiguous: row r of the span is row first + r of the block).  A step is the span of the E rows of
+// slot t + 1 on ceil(E / 4) workgroups, one row per wave; a segment the T * E rows of slots 1 ... T.  Rows past the end
+// keep the identities.
 __global__ __launch_bounds__(NT) void co_span_extrema_kernel(const ObserveKernelArgs k)
 {
     const int lane = threadIdx.x & (WAVE - 1);
     const long step = (long)gridDim.x * WAVES;
     float lo = INFINITY, hi = -INFINITY;
-    for (long r = (long)blockIdx.x * WAVES + (threadIdx.x >> 6); r < k.rows; r += step)
-        row_minmax(k.a.traj + (k.E + r) * k.N, k.N, k.vec, lane, lo, hi);
+    for (long r = k.first + (long)blockIdx.x * WAVES + (threadIdx.x >> 6); r < k.first + k.rows; r += step)
+        row_minmax(k.a.traj + r * k.N, k.N, k.vec, lane, lo, hi);
     store_partial(k.a.workspace, lo, hi);
 }
 
@@ -248,10 +223,12 @@ int co_act(void* stream, const co_geometry* g, const co_act_args* a, int t)
     if (!a || !a->action || !a->env_action || !a->actions)
         return fail(-10, "co_act: NULL argument, action, stepper action or trajectory pointer");
     if (t < 0 || t >= g->T) return fail(-11, "co_act: step %d outside 0 ... %d", t, g->T - 1);
-    ActKernelArgs k = {};
-    k.a = *a;
-    k.E = g->E; k.A = g->A; k.t = t;
-    hipLaunchKernelGGL(co_act_kernel, dim3(blocks_of(g->E)), dim3(NT), 0, static_cast<hipStream_t>(stream), k);
+    ActSpanKernelArgs k = {};                                        // a step is a span of E rows, recorded at step t
+    k.a.table = a->action; k.a.coef = a->coef; k.a.env_actions = a->env_action;
+    k.a.actions = a->actions + (long)t * g->E * g->A;
+    k.a.record_raw = a->record_raw;
+    k.rows = g->E; k.A = g->A;
+    hipLaunchKernelGGL(co_act_span_kernel, dim3(blocks_of(g->E)), dim3(NT), 0, static_cast<hipStream_t>(stream), k);
     return launch_status(-20, "co_act");
 }
 
@@ -266,10 +243,11 @@ int co_observe(void* stream, const co_geometry* g, const co_observe_args* a, int
     ObserveKernelArgs k = {};
     observe_shape(k, g, a);
     k.slot = t + 1; k.cell_in = t & 1; k.cell_out = (t + 1) & 1;
+    k.first = (long)(t + 1) * g->E; k.rows = g->E;                   // a step is the span of slot t + 1, a row per wave
     k.parts = blocks_of(g->E);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (update) {
-        hipLaunchKernelGGL(co_extrema_kernel, dim3(k.parts), dim3(NT), 0, s, k);
+        hipLaunchKernelGGL(co_span_extrema_kernel, dim3(k.parts), dim3(NT), 0, s, k);
         const int rc1 = launch_status(-20, "co_observe (extrema)");
         if (rc1 != 0) return rc1;
     }
@@ -309,7 +287,7 @@ int co_observe_span(void* stream, const co_geometry* g, const co_observe_args* a
     ObserveKernelArgs k = {};
     observe_shape(k, g, a);
     k.slot = g->T; k.cell_in = 0; k.cell_out = 1;
-    k.rows = (long)g->T * g->E;
+    k.first = g->E; k.rows = (long)g->T * g->E;                      // slots 1 ... T
     k.parts = (int)span_parts(g);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (update) {

@@ -7,8 +7,8 @@
 // row with lanes along the columns: obs and nxtobs through the sensor and the observation coefficients, actions through
 // the action coefficients, reward and terminated flag by lane 0.  float4 where the source allows it (see `vec` below).
 //
-// The affine map is row_ops.h's, so the batch equals the host loader's bit for bit.  Plain vector stores only; nothing is
-// stored through the scalar unit.
+// The affine map and the row copy (copy_row, copy_row4) are row_ops.h's, so the batch equals the host loader's bit for
+// bit.  Plain vector stores only; nothing is stored through the scalar unit.
 //
 // rpd_moments reads the same rows the other way round: nothing is copied, the scaled state changes of all rows are
 // reduced to per-column fp64 sums in two or three launches (partials per workgroup, then folds in index order).
@@ -38,21 +38,6 @@ struct GatherArgs {
     float* rewards;
     float* terminated;
 };
-
-// n output columns of one row: out[j] = affine(in[start + j * stride]); coef is [4][n] or NULL
-__device__ __forceinline__ void copy_row(const float* __restrict__ in, const float* __restrict__ coef, float* __restrict__ out,
-                                         int n, int start, int stride, int lane)
-{
-    for (int j = lane; j < n; j += WAVE) out[j] = affine_col(coef, n, j, in[start + (long)j * stride]);
-}
-
-// the same for stride 1 with every address a multiple of 16 bytes and n a multiple of 4
-__device__ __forceinline__ void copy_row4(const float* __restrict__ in, const float* __restrict__ coef, float* __restrict__ out,
-                                          int n, int start, int lane)
-{
-    for (int j = 4 * lane; j < n; j += 4 * WAVE)
-        *reinterpret_cast<f4*>(out + j) = affine_col4(coef, n, j, *reinterpret_cast<const f4*>(in + start + j));
-}
 
 __global__ __launch_bounds__(NT) void rp_gather_kernel(const GatherArgs g)
 {

@@ -4,18 +4,19 @@
 //
 // ro_act_chain is the wrapper stack's action side (raw-action record, action scaling, Gaussian forcing, forcing scaling,
 // sensor), ro_settle its observation side (per-env elite pick, world state in place, trajectory slot, agent sensor, step
-// counters, l2control reward); ro_settle_dissipation is ro_settle with the dissipation reward.  A wave owns an env, lanes
-// run along the columns.  The ensemble members travel in the kernel arguments and are picked by wave-uniform selects over
+// counters, l2control reward); ro_settle_dissipation is ro_settle with the dissipation reward: the two are instantiations
+// of one kernel template, which differ in the reward alone.  A wave owns an env, lanes run along the columns.  The ensemble members travel in the kernel arguments and are picked by wave-uniform selects over
 // constant indices, so the argument struct is never indexed dynamically and nothing spills.  No LDS, no atomics; every
 // store is a plain vector store.
 //
-// The affine maps are row_ops.h's and the forcing chain is explicit fmaf, so the results equal the host wrappers' bit for
-// bit.  The dissipation reward's stencil is ks_internal.h's ref_terms, the one the KS reward-row kernel evaluates.
+// The affine maps and the forcing chain are row_ops.h's, so the results equal the host wrappers' bit for bit.  The
+// dissipation reward's stencil is ks_internal.h's ref_terms, the one the KS reward-row kernel evaluates.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/rollout/settle_dissipation.h"
 #include "../../include/rollout_hip.h"
@@ -41,33 +42,14 @@ __global__ __launch_bounds__(NT) void ro_act_chain_kernel(const ActKernelArgs k)
     if (lane < k.A) k.a.actions[((long)t * k.B + b) * k.A + lane] = act[lane];
     float* __restrict__ out = k.a.world_action + (long)b * k.W;
     if (k.vec) {                                                     // stride 1, start, L and W multiples of 4, aligned
-        for (int j = 4 * lane; j < k.W; j += 4 * WAVE) {
-            const float* __restrict__ f = k.a.forcing + k.start + j;
-            const float a0 = affine_col(k.a.in_coef, k.A, 0, act[0]);
-            const f4 f0 = *reinterpret_cast<const f4*>(f);
-            f4 acc;
-            acc.x = __fmul_rn(a0, f0.x);
-            acc.y = __fmul_rn(a0, f0.y);
-            acc.z = __fmul_rn(a0, f0.z);
-            acc.w = __fmul_rn(a0, f0.w);
-            for (int m = 1; m < k.A; ++m) {
-                const float am = affine_col(k.a.in_coef, k.A, m, act[m]);
-                const f4 fm = *reinterpret_cast<const f4*>(f + (long)m * k.L);
-                acc.x = __fmaf_rn(am, fm.x, acc.x);
-                acc.y = __fmaf_rn(am, fm.y, acc.y);
-                acc.z = __fmaf_rn(am, fm.z, acc.z);
-                acc.w = __fmaf_rn(am, fm.w, acc.w);
-            }
-            *reinterpret_cast<f4*>(out + j) = affine_col4(k.a.out_coef, k.W, j, acc);
-        }
+        for (int j = 4 * lane; j < k.W; j += 4 * WAVE)
+            *reinterpret_cast<f4*>(out + j) =
+                affine_col4(k.a.out_coef, k.W, j, forcing_col4(k.a.in_coef, k.A, act, k.a.forcing + k.start + j, k.L));
         return;
     }
-    for (int j = lane; j < k.W; j += WAVE) {
-        const float* __restrict__ f = k.a.forcing + k.start + (long)j * k.stride;
-        float acc = __fmul_rn(affine_col(k.a.in_coef, k.A, 0, act[0]), f[0]);
-        for (int m = 1; m < k.A; ++m) acc = __fmaf_rn(affine_col(k.a.in_coef, k.A, m, act[m]), f[(long)m * k.L], acc);
-        out[j] = affine_col(k.a.out_coef, k.W, j, acc);
-    }
+    for (int j = lane; j < k.W; j += WAVE)
+        out[j] = affine_col(k.a.out_coef, k.W, j,
+                            forcing_col(k.a.in_coef, k.A, act, k.a.forcing + k.start + (long)j * k.stride, k.L));
 }
 
 struct SettleKernelArgs {
@@ -84,6 +66,14 @@ __device__ __forceinline__ void sense(float* __restrict__ pol, int i, float v, i
     if (j * stride == d && j < O) pol[j] = v;
 }
 
+__device__ __forceinline__ void sense4(float* __restrict__ pol, int i, f4 v, int start, int stride, int O)
+{
+    sense(pol, i, v.x, start, stride, O);
+    sense(pol, i + 1, v.y, start, stride, O);
+    sense(pol, i + 2, v.z, start, stride, O);
+    sense(pol, i + 3, v.w, start, stride, O);
+}
+
 // row b of the member chosen for `slot`, by wave-uniform selects over constant indices: the argument struct is never
 // indexed dynamically.  known: the index lies inside the ensemble; outside, the callers poison and read nothing
 __device__ __forceinline__ const float* member_row(const SettleKernelArgs& k, long slot, int b, bool& known)
@@ -97,62 +87,8 @@ __device__ __forceinline__ const float* member_row(const SettleKernelArgs& k, lo
     return src + (long)b * k.N;
 }
 
-__global__ __launch_bounds__(NT) void ro_settle_kernel(const SettleKernelArgs k)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int b = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    const int t = k.a.step[0];
-    if (blockIdx.x == 0 && threadIdx.x == 0) k.a.step[1] = t + 1;  // advance: ro_act_chain reads step[1], nobody here does
-    if (b >= k.B || t < 0 || t >= k.T) return;                      // whole waves leave: the shuffles below stay complete
-    const long slot = (long)t * k.B + b;
-    bool known;
-    const float* __restrict__ row = member_row(k, slot, b, known);
-    float* __restrict__ state = k.a.state + (long)b * k.N;
-    float* __restrict__ traj = k.a.traj + (slot + k.B) * k.N;       // slot t + 1
-    float* __restrict__ pol = k.a.policy_obs + (long)b * k.O;
-
-    double sum = 0.0;
-    if (k.vec) {                                                     // N a multiple of 4, every row 16-byte aligned
-        for (int i = 4 * lane; i < k.N; i += 4 * WAVE) {
-            f4 v = {NAN, NAN, NAN, NAN};
-            if (known) v = *reinterpret_cast<const f4*>(row + i);
-            *reinterpret_cast<f4*>(state + i) = v;
-            *reinterpret_cast<f4*>(traj + i) = v;
-            sense(pol, i, v.x, k.start, k.stride, k.O);
-            sense(pol, i + 1, v.y, k.start, k.stride, k.O);
-            sense(pol, i + 2, v.z, k.start, k.stride, k.O);
-            sense(pol, i + 3, v.w, k.start, k.stride, k.O);
-            const f4 w = affine_col4(k.a.reward_coef, k.N, i, v);
-            sum += (double)w.x * (double)w.x;
-            sum += (double)w.y * (double)w.y;
-            sum += (double)w.z * (double)w.z;
-            sum += (double)w.w * (double)w.w;
-        }
-    } else {
-        for (int i = lane; i < k.N; i += WAVE) {
-            const float v = known ? row[i] : NAN;
-            state[i] = v;
-            traj[i] = v;
-            sense(pol, i, v, k.start, k.stride, k.O);
-            const double w = (double)affine_col(k.a.reward_coef, k.N, i, v);
-            sum += w * w;
-        }
-    }
-#pragma unroll
-    for (int m = 1; m < WAVE; m <<= 1) sum += __shfl_xor(sum, m, WAVE);
-    if (lane == 0) {
-        k.a.rewards[slot] = (float)((-1.0) * (1.0 / k.N) * sum);
-        k.a.steps[slot] = k.a.steps0[b] + t + 1;
-    }
-}
-
-// ro_settle with the dissipation reward.  The stencil needs the rescaled row's periodic halo of 4 columns on both sides:
-// a lane re-reads its neighbours from the member's output row (read-only and cache-hot: the lanes next to it have just
-// fetched the same lines) and rescales them again, which costs arithmetic that this latency-bound step has to spare and
-// keeps the kernel free of LDS and of any wait between a store and a load.  On the float4 path the halo of a lane's
-// four columns is exactly the float4 before and the float4 after, wrapped around the row.
-struct DissKernelArgs {
-    SettleKernelArgs s;
+// what ro_settle_dissipation adds to ro_settle's arguments
+struct DissKernelArgs : SettleKernelArgs {
     const float* actions;     // [T][B][A]
     const float* in_coef;     // [4][A] or NULL
     const float* forcing;     // [A][N]
@@ -175,13 +111,23 @@ __device__ __forceinline__ void dissipation_point(const double* w, const double*
     sup += w[c] * (double)phi;
 }
 
-__global__ __launch_bounds__(NT) void ro_settle_dissipation_kernel(const DissKernelArgs d)
+// ro_settle (Args = SettleKernelArgs, the l2control reward) and ro_settle_dissipation (Args = DissKernelArgs): one body,
+// of which the reward's sums (one for l2control; sxx, sx and sup for dissipation) and its closing expression depend on Args.
+//
+// The dissipation stencil needs the rescaled row's periodic halo of 4 columns on both sides: a lane re-reads its
+// neighbours from the member's output row (read-only and cache-hot: the lanes next to it have just fetched the same
+// lines) and rescales them again, which costs arithmetic that this latency-bound step has to spare and keeps the kernel
+// free of LDS and of any wait between a store and a load.  On the float4 path the halo of a lane's four columns is
+// exactly the float4 before and the float4 after, wrapped around the row.  Its forcing is that of the scaled action, as
+// ro_act_chain forms it before its output map.
+template <class Args>
+__global__ __launch_bounds__(NT) void ro_settle_kernel(const Args k)
 {
-    const SettleKernelArgs& k = d.s;
+    constexpr bool DISS = std::is_same<Args, DissKernelArgs>::value;
     const int lane = threadIdx.x & (WAVE - 1);
     const int b = blockIdx.x * WAVES + (threadIdx.x >> 6);
     const int t = k.a.step[0];
-    if (blockIdx.x == 0 && threadIdx.x == 0) k.a.step[1] = t + 1;  // advance, as ro_settle_kernel
+    if (blockIdx.x == 0 && threadIdx.x == 0) k.a.step[1] = t + 1;  // advance: ro_act_chain reads step[1], nobody here does
     if (b >= k.B || t < 0 || t >= k.T) return;                      // whole waves leave: the shuffles below stay complete
     const long slot = (long)t * k.B + b;
     bool known;
@@ -189,54 +135,47 @@ __global__ __launch_bounds__(NT) void ro_settle_dissipation_kernel(const DissKer
     float* __restrict__ state = k.a.state + (long)b * k.N;
     float* __restrict__ traj = k.a.traj + (slot + k.B) * k.N;       // slot t + 1
     float* __restrict__ pol = k.a.policy_obs + (long)b * k.O;
-    const float* __restrict__ act = d.actions + slot * d.A;         // the raw actions ro_act_chain recorded for this step
+    [[maybe_unused]] const float* __restrict__ act = nullptr;       // the raw actions ro_act_chain recorded for this step
+    if constexpr (DISS) act = k.actions + slot * k.A;
     const int N = k.N;
 
-    double sxx = 0.0, sx = 0.0, sup = 0.0;
+    double sum[DISS ? 3 : 1] = {};
     if (k.vec) {                                                     // N a multiple of 4, every row 16-byte aligned
         for (int i = 4 * lane; i < N; i += 4 * WAVE) {
-            const int il = wrap_col(i - 4, N), ir = wrap_col(i + 4, N);
-            f4 v = {NAN, NAN, NAN, NAN}, vl = v, vr = v;
+            // the halo is the dissipation reward's alone; its loads stay beside the row's own, under the one test of `known`
+            [[maybe_unused]] const int il = wrap_col(i - 4, N), ir = wrap_col(i + 4, N);
+            f4 v = {NAN, NAN, NAN, NAN};
+            [[maybe_unused]] f4 vl = v, vr = v;
             if (known) {
                 v = *reinterpret_cast<const f4*>(row + i);
-                vl = *reinterpret_cast<const f4*>(row + il);
-                vr = *reinterpret_cast<const f4*>(row + ir);
+                if constexpr (DISS) {
+                    vl = *reinterpret_cast<const f4*>(row + il);
+                    vr = *reinterpret_cast<const f4*>(row + ir);
+                }
             }
             *reinterpret_cast<f4*>(state + i) = v;
             *reinterpret_cast<f4*>(traj + i) = v;
-            sense(pol, i, v.x, k.start, k.stride, k.O);
-            sense(pol, i + 1, v.y, k.start, k.stride, k.O);
-            sense(pol, i + 2, v.z, k.start, k.stride, k.O);
-            sense(pol, i + 3, v.w, k.start, k.stride, k.O);
+            sense4(pol, i, v, k.start, k.stride, k.O);
             const f4 u = affine_col4(k.a.reward_coef, N, i, v);
-            const f4 ul = affine_col4(k.a.reward_coef, N, il, vl);
-            const f4 ur = affine_col4(k.a.reward_coef, N, ir, vr);
-            // the forcing of the scaled action, as ro_act_chain forms it before its output map
-            const float* __restrict__ f = d.forcing + i;
-            const float a0 = affine_col(d.in_coef, d.A, 0, act[0]);
-            const f4 f0 = *reinterpret_cast<const f4*>(f);
-            f4 phi;
-            phi.x = __fmul_rn(a0, f0.x);
-            phi.y = __fmul_rn(a0, f0.y);
-            phi.z = __fmul_rn(a0, f0.z);
-            phi.w = __fmul_rn(a0, f0.w);
-            for (int m = 1; m < d.A; ++m) {
-                const float am = affine_col(d.in_coef, d.A, m, act[m]);
-                const f4 fm = *reinterpret_cast<const f4*>(f + (long)m * N);
-                phi.x = __fmaf_rn(am, fm.x, phi.x);
-                phi.y = __fmaf_rn(am, fm.y, phi.y);
-                phi.z = __fmaf_rn(am, fm.z, phi.z);
-                phi.w = __fmaf_rn(am, fm.w, phi.w);
-            }
-            const double w[12] = {(double)ul.x, (double)ul.y, (double)ul.z, (double)ul.w, (double)u.x,  (double)u.y,
-                                  (double)u.z,  (double)u.w,  (double)ur.x, (double)ur.y, (double)ur.z, (double)ur.w};
-            double q[12];
+            if constexpr (DISS) {
+                const f4 ul = affine_col4(k.a.reward_coef, N, il, vl);
+                const f4 ur = affine_col4(k.a.reward_coef, N, ir, vr);
+                const f4 phi = forcing_col4(k.in_coef, k.A, act, k.forcing + i, N);
+                const double w[12] = {(double)ul.x, (double)ul.y, (double)ul.z, (double)ul.w, (double)u.x,  (double)u.y,
+                                      (double)u.z,  (double)u.w,  (double)ur.x, (double)ur.y, (double)ur.z, (double)ur.w};
+                double q[12];
 #pragma unroll
-            for (int j = 0; j < 12; ++j) q[j] = w[j] * w[j];
-            dissipation_point(w, q, 4, phi.x, d, sxx, sx, sup);
-            dissipation_point(w, q, 5, phi.y, d, sxx, sx, sup);
-            dissipation_point(w, q, 6, phi.z, d, sxx, sx, sup);
-            dissipation_point(w, q, 7, phi.w, d, sxx, sx, sup);
+                for (int j = 0; j < 12; ++j) q[j] = w[j] * w[j];
+                dissipation_point(w, q, 4, phi.x, k, sum[0], sum[1], sum[2]);
+                dissipation_point(w, q, 5, phi.y, k, sum[0], sum[1], sum[2]);
+                dissipation_point(w, q, 6, phi.z, k, sum[0], sum[1], sum[2]);
+                dissipation_point(w, q, 7, phi.w, k, sum[0], sum[1], sum[2]);
+            } else {
+                sum[0] += (double)u.x * (double)u.x;
+                sum[0] += (double)u.y * (double)u.y;
+                sum[0] += (double)u.z * (double)u.z;
+                sum[0] += (double)u.w * (double)u.w;
+            }
         }
     } else {
         for (int i = lane; i < N; i += WAVE) {
@@ -244,27 +183,29 @@ __global__ __launch_bounds__(NT) void ro_settle_dissipation_kernel(const DissKer
             state[i] = v;
             traj[i] = v;
             sense(pol, i, v, k.start, k.stride, k.O);
-            double w[9], q[9];
+            if constexpr (DISS) {
+                double w[9], q[9];
 #pragma unroll
-            for (int j = -4; j <= 4; ++j) {
-                const int c = wrap_col(i + j, N);
-                w[j + 4] = (double)affine_col(k.a.reward_coef, N, c, known ? row[c] : NAN);
-                q[j + 4] = w[j + 4] * w[j + 4];
+                for (int j = -4; j <= 4; ++j) {
+                    const int c = wrap_col(i + j, N);
+                    w[j + 4] = (double)affine_col(k.a.reward_coef, N, c, known ? row[c] : NAN);
+                    q[j + 4] = w[j + 4] * w[j + 4];
+                }
+                dissipation_point(w, q, 4, forcing_col(k.in_coef, k.A, act, k.forcing + i, N), k, sum[0], sum[1], sum[2]);
+            } else {
+                const double w = (double)affine_col(k.a.reward_coef, N, i, v);
+                sum[0] += w * w;
             }
-            const float* __restrict__ f = d.forcing + i;
-            float phi = __fmul_rn(affine_col(d.in_coef, d.A, 0, act[0]), f[0]);
-            for (int m = 1; m < d.A; ++m) phi = __fmaf_rn(affine_col(d.in_coef, d.A, m, act[m]), f[(long)m * N], phi);
-            dissipation_point(w, q, 4, phi, d, sxx, sx, sup);
         }
     }
 #pragma unroll
-    for (int m = 1; m < WAVE; m <<= 1) {
-        sxx += __shfl_xor(sxx, m, WAVE);
-        sx += __shfl_xor(sx, m, WAVE);
-        sup += __shfl_xor(sup, m, WAVE);
-    }
+    for (int m = 1; m < WAVE; m <<= 1)
+        for (double& s : sum) s += __shfl_xor(s, m, WAVE);
     if (lane == 0) {
-        k.a.rewards[slot] = (float)((-1.0) * ((sxx / N + sx / N) + sup / N));   // the KS reward-row kernel's expression
+        if constexpr (DISS)                                          // the KS reward-row kernel's expression
+            k.a.rewards[slot] = (float)((-1.0) * ((sum[0] / N + sum[1] / N) + sum[2] / N));
+        else
+            k.a.rewards[slot] = (float)((-1.0) * (1.0 / N) * sum[0]);
         k.a.steps[slot] = k.a.steps0[b] + t + 1;
     }
 }
@@ -339,7 +280,8 @@ int ro_settle(void* stream, const ro_geometry* g, const ro_settle_args* a)
     SettleKernelArgs k;
     const int bad = settle_kernel_args("ro_settle", g, a, k);
     if (bad != 0) return bad;
-    hipLaunchKernelGGL(ro_settle_kernel, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0, static_cast<hipStream_t>(stream), k);
+    hipLaunchKernelGGL(ro_settle_kernel<SettleKernelArgs>, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0,
+                       static_cast<hipStream_t>(stream), k);
     return launch_status(-20, "ro_settle");
 }
 
@@ -348,7 +290,7 @@ int ro_settle_dissipation(void* stream, const ro_geometry* g, const ro_settle_ar
     const int rc = ro_supported(g);
     if (rc != 0) return rc;
     DissKernelArgs k = {};
-    const int bad = settle_kernel_args("ro_settle_dissipation", g, a, k.s);
+    const int bad = settle_kernel_args("ro_settle_dissipation", g, a, k);
     if (bad != 0) return bad;
     if (!d || !d->actions || !d->forcing)
         return fail(-10, "ro_settle_dissipation: NULL dissipation argument, recorded-actions or forcing pointer");
@@ -363,8 +305,8 @@ int ro_settle_dissipation(void* stream, const ro_geometry* g, const ro_settle_ar
     k.dx2 = d->dx * d->dx;            // as ks::make_consts and the KS reward-row launch form them
     k.r_dx = 1.0 / k.dx;
     k.r_dx2 = 1.0 / k.dx2;
-    k.s.vec = k.s.vec && aligned16(d->forcing);
-    hipLaunchKernelGGL(ro_settle_dissipation_kernel, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0,
+    k.vec = k.vec && aligned16(d->forcing);
+    hipLaunchKernelGGL(ro_settle_kernel<DissKernelArgs>, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0,
                        static_cast<hipStream_t>(stream), k);
     return launch_status(-20, "ro_settle_dissipation");
 }

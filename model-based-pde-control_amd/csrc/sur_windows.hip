@@ -4,11 +4,11 @@
 //
 // One launch assembles the `states` and `actions` of one TBPTT batch from the packed replay: a wave owns one
 // (window, step) row, lanes run along the columns.  The observation row goes through the sensor and the observation
-// coefficients; the action row through the action scaling, the Gaussian forcing chain (the chain of ro_act_chain and of
-// the KS stepper's action path), the sensor and the forcing scaling.  float4 where the host found the geometry and every
+// coefficients; the action row through the action scaling, the Gaussian forcing chain (row_ops.h's forcing_col, which
+// ro_act_chain calls too: the chain of the KS stepper's action path), the sensor and the forcing scaling.  float4 where the host found the geometry and every
 // base and stride 16-byte aligned, the scalar path otherwise.  No LDS, no atomics; every store is a plain vector store.
 //
-// The affine map is row_ops.h's and the forcing chain is explicit fmaf, so a batch equals the host loader's connector
+// The affine map, the row copy and the forcing chain are row_ops.h's, so a batch equals the host loader's connector
 // bit for bit.  row_ops.h demands an uncontracted includer and the rest of the library is built with the compiler's
 // default contraction: hence this translation unit of its own, which the Makefile compiles with EXACT (-ffp-contract=off).
 // The pragma below covers this file's own expressions only: the _rn intrinsics are plain operators in headers the
@@ -50,48 +50,26 @@ __global__ __launch_bounds__(NT) void sur_gather_windows_kernel(const SurWindows
         return;
     }
 
-    const float* __restrict__ obs = k.obs + row * k.obs_width + k.obs_start;
-    if (k.vec_obs) {
-        for (int j = 4 * lane; j < k.No; j += 4 * WAVE)
-            *reinterpret_cast<f4*>(st + j) = affine_col4(k.obs_coef, k.No, j, *reinterpret_cast<const f4*>(obs + j));
-    } else {
-        for (int j = lane; j < k.No; j += WAVE) st[j] = affine_col(k.obs_coef, k.No, j, obs[(long)j * k.obs_stride]);
-    }
+    const float* __restrict__ obs = k.obs + row * k.obs_width + k.obs_start;     // from the sensor's first column on
+    if (k.vec_obs)
+        copy_row4(obs, k.obs_coef, st, k.No, 0, lane);
+    else
+        copy_row(obs, k.obs_coef, st, k.No, 0, k.obs_stride, lane);
 
     const float* __restrict__ act = k.actions + row * k.A;
     if (!k.forcing) {                            // no forcing: sensor and output scaling over the action row itself
-        for (int j = lane; j < k.Na; j += WAVE)
-            ac[j] = affine_col(k.act_out_coef, k.Na, j, act[k.act_start + (long)j * k.act_stride]);
+        copy_row(act, k.act_out_coef, ac, k.Na, k.act_start, k.act_stride, lane);
         return;
     }
     if (k.vec_act) {                             // stride 1; start, Lf and Na multiples of 4; aligned
-        for (int j = 4 * lane; j < k.Na; j += 4 * WAVE) {
-            const float* __restrict__ f = k.forcing + k.act_start + j;
-            const float a0 = affine_col(k.act_in_coef, k.A, 0, act[0]);
-            const f4 f0 = *reinterpret_cast<const f4*>(f);
-            f4 acc;
-            acc.x = __fmul_rn(a0, f0.x);
-            acc.y = __fmul_rn(a0, f0.y);
-            acc.z = __fmul_rn(a0, f0.z);
-            acc.w = __fmul_rn(a0, f0.w);
-            for (int m = 1; m < k.A; ++m) {
-                const float am = affine_col(k.act_in_coef, k.A, m, act[m]);
-                const f4 fm = *reinterpret_cast<const f4*>(f + (long)m * k.Lf);
-                acc.x = __fmaf_rn(am, fm.x, acc.x);
-                acc.y = __fmaf_rn(am, fm.y, acc.y);
-                acc.z = __fmaf_rn(am, fm.z, acc.z);
-                acc.w = __fmaf_rn(am, fm.w, acc.w);
-            }
-            *reinterpret_cast<f4*>(ac + j) = affine_col4(k.act_out_coef, k.Na, j, acc);
-        }
+        for (int j = 4 * lane; j < k.Na; j += 4 * WAVE)
+            *reinterpret_cast<f4*>(ac + j) =
+                affine_col4(k.act_out_coef, k.Na, j, forcing_col4(k.act_in_coef, k.A, act, k.forcing + k.act_start + j, k.Lf));
         return;
     }
-    for (int j = lane; j < k.Na; j += WAVE) {
-        const float* __restrict__ f = k.forcing + k.act_start + (long)j * k.act_stride;
-        float acc = __fmul_rn(affine_col(k.act_in_coef, k.A, 0, act[0]), f[0]);
-        for (int m = 1; m < k.A; ++m) acc = __fmaf_rn(affine_col(k.act_in_coef, k.A, m, act[m]), f[(long)m * k.Lf], acc);
-        ac[j] = affine_col(k.act_out_coef, k.Na, j, acc);
-    }
+    for (int j = lane; j < k.Na; j += WAVE)
+        ac[j] = affine_col(k.act_out_coef, k.Na, j,
+                           forcing_col(k.act_in_coef, k.A, act, k.forcing + k.act_start + (long)j * k.act_stride, k.Lf));
 }
 
 }  // namespace

@@ -87,7 +87,7 @@ def test_gather_matches_the_twin_over_every_size(N, forcing):
 
 
 @pytest.mark.parametrize("forcing", (True, False), ids=("forcing", "noforcing"))
-@pytest.mark.parametrize("N,A,B,L", ((64, 4, 5, 6), (98, 16, 5, 6)))
+@pytest.mark.parametrize("N,A,B,L", ((64, 4, 5, 6), (98, 16, 5, 6), (64, 1, 2, 3), (98, 1, 2, 3)))
 def test_gather_matches_the_twin_over_every_path(N, A, B, L, forcing):
     """The full cross of sensor stride and start, coefficients, row map, output layout and base alignment at one size
     whose widths are multiples of four (the float4 path is taken exactly where the host decides so) and one where they

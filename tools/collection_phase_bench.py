@@ -142,7 +142,8 @@ def timed(call):
 def kernel_times(path):
     """{kernel family: median device microseconds per launch, launches} from a rocprofv3 ``*_kernel_trace.csv``.  The
     median leaves out the one long KS launch of the reset's burn-in."""
-    want = {"ks": ("ks_rk4",), "co_act": ("co_act_kernel",), "co_observe_extrema": ("co_extrema_kernel",),
+    want = {"ks": ("ks_rk4",), "co_act": ("co_act_span_kernel", "co_act_kernel"),
+            "co_observe_extrema": ("co_span_extrema_kernel", "co_extrema_kernel"),
             "co_observe_scale": ("co_scale_kernel",), "sac_policy_forward": ("sac_policy_fwd",)}
     seen = {}
     with open(path) as f:
