@@ -22,8 +22,8 @@
  * `rp_source` entries are HOST structs, read during the call and passed to the kernel by value; every pointer in them is
  * a DEVICE pointer.  In every entry the arguments are validated on the host before any device call and everything is
  * enqueued on `stream`: no host synchronisation, no device allocation.  Return 0 on success, negative on error
- * (rp_last_error()).  Plain vector stores, no scratch, no atomics; LDS only in rpd_moments, where the four waves of a
- * workgroup add up their partial sums.
+ * (rp_last_error()).  Plain vector stores, no scratch, no atomics; LDS only in rpd_moments and in rpn_moments
+ * (replay/fit.h: the scaling fits of the offline evaluation), where the four waves of a workgroup add up their partial sums.
  */
 #ifndef REPLAY_HIP_H
 #define REPLAY_HIP_H

@@ -12,6 +12,8 @@
 //
 // rpd_moments reads the same rows the other way round: nothing is copied, the scaled state changes of all rows are
 // reduced to per-column fp64 sums in two or three launches (partials per workgroup, then folds in index order).
+// rpn_moments (include/replay/fit.h) is the same scheme over three fields of the rows at once: observations, actions and
+// forced actions, the scaling fits of the offline evaluation.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -19,6 +21,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "../../include/replay/fit.h"
 #include "../../include/replay_hip.h"
 #include "capi_error.h"
 #include "row_ops.h"
@@ -317,6 +320,169 @@ int delta_groups(long n, int groups)
 // partial rows the middle launch leaves of G (0: there is no middle launch)
 int delta_middle_rows(int G) { return G > FOLD ? (G + FOLD - 1) / FOLD : 0; }
 
+// ---- the moments of observations, actions and forced actions (fit_scalings of the offline evaluation) --------------
+struct FitArgs {
+    const float* obs;                  // [slab_rows][N]
+    const float* actions;              // [slab_rows][A]
+    const float* F;                    // [A][N] or NULL: no forced field
+    const long* rows;                  // [n] or NULL: rows 0 ... n - 1
+    long n, slab_rows;
+    int N, A, W;                       // W = N + A (+ N with F): columns of a workspace row
+    double* ws;                        // [groups][2][W], then the rows of the middle launch
+};
+
+// The four waves' pairs of one field meet in LDS and are added in wave order into columns first + j0 ... of the
+// workgroup's workspace row.  Every thread of the workgroup calls it.
+template <bool VEC>
+__device__ __forceinline__ void meet(double (*part)[2][TILE], const double* s, const double* q, int j0, int width, int first,
+                                     double* __restrict__ out, int W)
+{
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = VEC ? 4 * lane + k : lane + k * WAVE;
+        part[wave][0][c] = s[k];
+        part[wave][1][c] = q[k];
+    }
+    __syncthreads();
+    const int j = j0 + threadIdx.x;    // NT == TILE: a thread per column of the tile
+    if (j < width) {
+        double S = part[0][0][threadIdx.x], Q = part[0][1][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            S += part[w][0][threadIdx.x];
+            Q += part[w][1][threadIdx.x];
+        }
+        out[first + j] = S;
+        out[W + first + j] = Q;
+    }
+    __syncthreads();
+}
+
+// rpd_moments_kernel's shape: a wave owns TURN consecutive rows of the list at a time and keeps the sums of its four
+// columns of the tile, per field, in fp64 registers.  The forced value of a column is forcing_col's chain over the row's
+// A actions, which every lane reads (a wave-uniform address); the A action columns themselves are lanes 0 ... A - 1 of
+// tile 0.
+template <bool VEC>
+__global__ __launch_bounds__(NT) void rpn_moments_kernel(const FitArgs a)
+{
+    __shared__ double part[WAVES][2][TILE];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    const int j0 = blockIdx.y * TILE;
+    const bool forced = a.F != nullptr, act_tile = blockIdx.y == 0;
+    double so[4] = {0.0, 0.0, 0.0, 0.0}, qo[4] = {0.0, 0.0, 0.0, 0.0};
+    double sf[4] = {0.0, 0.0, 0.0, 0.0}, qf[4] = {0.0, 0.0, 0.0, 0.0};
+    double sa[4] = {0.0, 0.0, 0.0, 0.0}, qa[4] = {0.0, 0.0, 0.0, 0.0};     // entry 0 alone is used: a lane per action
+    for (long i0 = ((long)blockIdx.x * WAVES + wave) * TURN; i0 < a.n; i0 += (long)gridDim.x * WAVES * TURN) {
+        long row[TURN];
+        int state[TURN];               // 0: past the list, 1: a row of the slab, 2: outside it (read nothing, poison)
+        float o[TURN][4], f[TURN][4], u[TURN];
+#pragma unroll
+        for (int t = 0; t < TURN; ++t) {
+            const long i = i0 + t;
+            const long r = i < a.n ? (a.rows ? a.rows[i] : i) : -1;
+            const bool inside = r >= 0 && r < a.slab_rows;
+            state[t] = i < a.n ? (inside ? 1 : 2) : 0;
+            row[t] = inside ? r : 0;
+        }
+#pragma unroll
+        for (int t = 0; t < TURN; ++t) {
+            u[t] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[t][k] = f[t][k] = 0.0f;
+            if (state[t] != 1) continue;
+            const float* __restrict__ src = a.obs + row[t] * a.N;
+            const float* __restrict__ act = a.actions + row[t] * a.A;
+            if (act_tile && lane < a.A) u[t] = act[lane];
+            if (VEC) {
+                const int j = j0 + 4 * lane;
+                if (j < a.N) {
+                    const f4 vo = *reinterpret_cast<const f4*>(src + j);
+                    o[t][0] = vo.x, o[t][1] = vo.y, o[t][2] = vo.z, o[t][3] = vo.w;
+                    if (forced) {
+                        const f4 vf = forcing_col4(nullptr, a.A, act, a.F + j, a.N);
+                        f[t][0] = vf.x, f[t][1] = vf.y, f[t][2] = vf.z, f[t][3] = vf.w;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = j0 + lane + k * WAVE;
+                    if (j0 + k * WAVE >= a.N) break;            // wave-uniform: a narrow row costs what it holds
+                    if (j < a.N) {
+                        o[t][k] = src[j];
+                        if (forced) f[t][k] = forcing_col(nullptr, a.A, act, a.F + j, a.N);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < TURN; ++t) {
+            if (state[t] == 0) continue;
+            const bool poison = state[t] == 2;
+            if (act_tile && lane < a.A) {
+                const double v = poison ? (double)NAN : (double)u[t];
+                sa[0] += v;
+                qa[0] += v * v;        // the product of two fp32 values is exact in fp64
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = j0 + (VEC ? 4 * lane + k : lane + k * WAVE);
+                if (!VEC && j0 + k * WAVE >= a.N) break;
+                if (j >= a.N) continue;
+                const double v = poison ? (double)NAN : (double)o[t][k];
+                so[k] += v;
+                qo[k] += v * v;
+                if (forced) {
+                    const double w = poison ? (double)NAN : (double)f[t][k];
+                    sf[k] += w;
+                    qf[k] += w * w;
+                }
+            }
+        }
+    }
+    double* __restrict__ out = a.ws + (long)blockIdx.x * 2 * a.W;
+    meet<VEC>(part, so, qo, j0, a.N, 0, out, a.W);
+    if (act_tile) meet<false>(part, sa, qa, 0, a.A, a.N, out, a.W);        // blockIdx.y is uniform over the workgroup
+    if (forced) meet<VEC>(part, sf, qf, j0, a.N, a.N + a.A, out, a.W);
+}
+
+// the closing launch, one workgroup: the partial rows per column in index order, then every field's total over its
+// columns in column order, a thread per field.  Column j of the workspace row lies in field 0 (j < N), 1 (j < N + A) or
+// 2, and goes to entry j + field of the output: each earlier field leaves a slot for its total.
+__global__ __launch_bounds__(NT) void rpn_fold_kernel(const double* __restrict__ ws, int groups, int N, int A, int forced, long n,
+                                                      double* __restrict__ sums, float* __restrict__ stats)
+{
+    __shared__ double col[2][2 * RP_MAX_OBS_DIM + RP_MAX_ACT_DIM];
+    const int W = N + A + (forced ? N : 0), ld = W + (forced ? 3 : 2);
+    for (int j = threadIdx.x; j < W; j += NT) {
+        double S = 0.0, Q = 0.0;
+#pragma unroll 8
+        for (int g = 0; g < groups; ++g) {
+            S += ws[(long)g * 2 * W + j];
+            Q += ws[(long)g * 2 * W + W + j];
+        }
+        const int e = j + (j < N ? 0 : (j < N + A ? 1 : 2));
+        col[0][j] = sums[e] = S;
+        col[1][j] = sums[ld + e] = Q;
+        write_stats(S, Q, (double)n, stats + e, stats + ld + e);
+    }
+    __syncthreads();
+    if (threadIdx.x < (forced ? 3 : 2)) {
+        const int field = threadIdx.x;
+        const int first = field == 0 ? 0 : (field == 1 ? N : N + A), width = field == 1 ? A : N;
+        double S = 0.0, Q = 0.0;
+        for (int j = first; j < first + width; ++j) {
+            S += col[0][j];
+            Q += col[1][j];
+        }
+        const int e = first + width + field;
+        sums[e] = S;
+        sums[ld + e] = Q;
+        write_stats(S, Q, (double)n * width, stats + e, stats + ld + e);
+    }
+}
+
 int obs_dim_of(const rp_source& s) { return width_of(s.obs_width, s.sensor_start, s.sensor_stride); }
 
 }  // namespace
@@ -493,6 +659,57 @@ int rpd_moments(void* stream, const float* obs, const float* nxtobs, long slab_r
     }
     hipLaunchKernelGGL(rpd_fold_kernel, dim3(1), dim3(NT), 0, s, partials, left, obs_dim, n, sums, stats);
     return launch_status(-80, "rpd_moments");
+}
+
+long rpn_workspace_doubles(int N, int A, int forced, long n, int groups)
+{
+    if (N < 1 || N > RP_MAX_OBS_DIM || A < 1 || A > RP_MAX_ACT_DIM || n < 1 || groups < 0) return 0;
+    const int G = delta_groups(n, groups);
+    return (long)(G + delta_middle_rows(G)) * 2 * (N + A + (forced ? N : 0));
+}
+
+int rpn_moments(void* stream, const float* obs, const float* actions, long slab_rows, int N, int A, const float* F,
+                const long* rows, long n, int groups, double* workspace, double* sums, float* stats)
+{
+    if (!obs || !actions || !workspace || !sums || !stats)
+        return fail(-90, "rpn_moments: NULL obs, actions, workspace, sums or stats");
+    if (n < 1) return fail(-91, "rpn_moments: %ld rows (at least 1)", n);
+    if (slab_rows < 1) return fail(-92, "rpn_moments: a slab of %ld rows (at least 1)", slab_rows);
+    if (N < 1 || N > RP_MAX_OBS_DIM) return fail(-93, "rpn_moments: observation width %d (1 ... %d are supported)", N, RP_MAX_OBS_DIM);
+    if (A < 1 || A > RP_MAX_ACT_DIM) return fail(-94, "rpn_moments: action width %d (1 ... %d are supported)", A, RP_MAX_ACT_DIM);
+    if (groups < 0) return fail(-95, "rpn_moments: %d workgroups (0 for the default, or at least 1)", groups);
+    FitArgs a = {};
+    a.obs = obs;
+    a.actions = actions;
+    a.F = F;
+    a.rows = rows;
+    a.n = n;
+    a.slab_rows = slab_rows;
+    a.N = N;
+    a.A = A;
+    a.W = N + A + (F ? N : 0);
+    a.ws = workspace;
+    const int G = delta_groups(n, groups);
+    const dim3 grid(G, (N + TILE - 1) / TILE);
+    // float4 under rpd_moments' conditions: from 193 columns on, every row and the forcing matrix 16-byte aligned
+    const bool vec = N > 3 * WAVE && N % 4 == 0 && aligned16(obs) && aligned16(F);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(rpn_moments_kernel<true>, grid, dim3(NT), 0, s, a);
+    else
+        hipLaunchKernelGGL(rpn_moments_kernel<false>, grid, dim3(NT), 0, s, a);
+    const int rc = launch_status(-100, "rpn_moments");
+    if (rc != 0) return rc;
+    const double* partials = workspace;
+    int left = G;
+    if (const int M = delta_middle_rows(G)) {
+        double* middle = workspace + (long)G * 2 * a.W;
+        hipLaunchKernelGGL(rpd_middle_kernel, dim3(M, (a.W + NT - 1) / NT), dim3(NT), 0, s, workspace, G, a.W, middle);
+        partials = middle;
+        left = M;
+    }
+    hipLaunchKernelGGL(rpn_fold_kernel, dim3(1), dim3(NT), 0, s, partials, left, N, A, F ? 1 : 0, n, sums, stats);
+    return launch_status(-100, "rpn_moments");
 }
 
 const char* rp_last_error(void) { return g_err; }

@@ -37,28 +37,40 @@ class FieldMap:
             return (((v - a) / ba) * dc + c).astype(np.float32)
 
 
-def flatten(t):
-    """The chain as a list of ("sensor", stride) / ("scale", ScaleTransform, inverse) steps."""
+def _settled(norm):
+    """A ``Normalize`` whose statistics can no longer move: frozen and fitted.  It is then an affine map per column."""
+    return bool(norm.frozen) and norm.mean is not None and norm.var is not None
+
+
+def flatten(t, normalize=False):
+    """The chain as a list of ("sensor", stride) / ("scale", ScaleTransform, inverse) steps.  With ``normalize`` a
+    ``Normalize`` that is frozen and fitted is a ("norm", Normalize, inverse) step as well; without it, and for every other
+    ``Normalize``, the chain is refused.  Only the callers whose kernels are pinned with such a step ask for it
+    (``world_connector`` and the validation loss)."""
     if t is None or isinstance(t, tr.Identity):
         return []
     if isinstance(t, tr.Operation):
-        return [step for inner in t.transforms for step in flatten(inner)]
+        return [step for inner in t.transforms for step in flatten(inner, normalize)]
     if isinstance(t, tr._OperationInverse):
-        return [step for inner in t.transfs for step in flatten(inner)]
+        return [step for inner in t.transfs for step in flatten(inner, normalize)]
     if isinstance(t, tr._BatchInverse):
-        return flatten(t.transform)
+        return flatten(t.transform, normalize)
     if isinstance(t, tr.BatchTransform):
-        return flatten(t.transform)
+        return flatten(t.transform, normalize)
     if isinstance(t, tr.SensorTransform):
         return [("sensor", int(t.stride))]
     if type(t) is tr.ScaleTransform:
         return [("scale", t, False)]
+    if normalize and type(t) is tr.Normalize and _settled(t):
+        return [("norm", t, False)]
     if type(t) is tr._InverseView:
         inner = t.transf
         if isinstance(inner, tr.Identity):
             return []
         if type(inner) is tr.ScaleTransform:
             return [("scale", inner, True)]
+        if normalize and type(inner) is tr.Normalize and _settled(inner):
+            return [("norm", inner, True)]
         if isinstance(inner, tr.SensorTransform) and int(inner.stride) == 1:
             return []
         raise Unrecognized(f"the inverse of a {type(inner).__name__}")
@@ -76,10 +88,39 @@ def _columns(stat, width, what):
     raise Unrecognized(f"a ScaleTransform whose {what} of shape {tuple(stat.shape)} is not one value or one per column")
 
 
-def field_map(chain, width):
-    """``FieldMap`` of a chain over a field whose rows are ``width`` columns wide; raises ``Unrecognized``."""
+_HOST_COPIES = {}
+
+
+def _host_copy(stat):
+    """``stat`` on the host.  The copy of a device tensor is cached per tensor object -- a frozen ``Normalize`` never
+    re-assigns its statistics --, so recognising the same chain again (every validation batch does) costs no
+    device-to-host copy and no synchronisation."""
+    if not (isinstance(stat, torch.Tensor) and stat.is_cuda):
+        return torch.as_tensor(stat).detach().cpu()
+    hit = _HOST_COPIES.get(id(stat))
+    if hit is None or hit[0] is not stat:
+        if len(_HOST_COPIES) > 256:
+            _HOST_COPIES.clear()
+        hit = _HOST_COPIES[id(stat)] = (stat, stat.detach().cpu())
+    return hit[1]
+
+
+def _normalize_coef(norm, inverse, width):
+    """The four-step coefficients of a frozen, fitted ``Normalize``: with s = sqrt(var + epsilon) in fp32 torch, as
+    ``_fwd`` / ``_inv`` take it, forward is (mean, s, 1, -0.0) and the inverse (+0.0, 1, s, mean).  Multiplying by 1 and
+    subtracting +0.0 change no bit; the forward map adds MINUS zero, so that a quotient that underflows to -0.0 stays
+    -0.0."""
+    scale = _statistic(torch.sqrt(_host_copy(norm.var) + norm.epsilon), width, "variance")
+    mean = _statistic(_host_copy(norm.mean), width, "mean")
+    zero, one = torch.zeros(width), torch.ones(width)
+    return torch.stack([zero, one, scale, mean] if inverse else [mean, scale, one, -zero])
+
+
+def field_map(chain, width, normalize=False):
+    """``FieldMap`` of a chain over a field whose rows are ``width`` columns wide; raises ``Unrecognized``.
+    ``normalize``: take a frozen, fitted ``Normalize`` as the affine map it is (``flatten``)."""
     start, stride, coef = 0, 1, None
-    for step in flatten(chain):
+    for step in flatten(chain, normalize):
         if step[0] == "sensor":
             r = step[1]
             if r < 1:
@@ -94,6 +135,9 @@ def field_map(chain, width):
             if coef is not None:
                 raise Unrecognized("two scalings in a row")
             _, scale, inverse = step
+            if step[0] == "norm":
+                coef = _normalize_coef(scale, inverse, width)
+                continue
             vmin, vmax, lower, upper = (torch.as_tensor(s).detach().cpu() for s in (scale.vmin, scale.vmax, scale.lower, scale.upper))
             a, b, c, d = (lower, upper, vmin, vmax) if inverse else (vmin, vmax, lower, upper)
             coef = torch.stack([_columns(a, width, "bounds"), _columns(b - a, width, "bounds"),
@@ -182,15 +226,15 @@ def forcing_matrix(forcing):
     return matrix.contiguous()
 
 
-def action_maps(before, forcing, after):
+def action_maps(before, forcing, after, normalize=False):
     """(``act_in`` FieldMap over the A action columns, the forcing matrix, ``act_out`` FieldMap over its L columns) of an
     action chain split by ``split_at_forcing`` around a forcing."""
     matrix = forcing_matrix(forcing)
     A, L = (int(v) for v in matrix.shape)
-    act_in = field_map(tr.Operation(before), A)
+    act_in = field_map(tr.Operation(before), A, normalize)
     if (act_in.start, act_in.stride, act_in.width) != (0, 1, A):
         raise Unrecognized("a sensor on the agent's actions")
-    return act_in, matrix, field_map(tr.Operation(after), L)
+    return act_in, matrix, field_map(tr.Operation(after), L, normalize)
 
 
 def _steps(t):
@@ -212,12 +256,12 @@ def world_connector(stransf, obs_width, act_width):
     carries the whole action chain.  Anything else raises ``Unrecognized``."""
     if type(stransf) is not tr.SampleTransform:
         raise Unrecognized(f"a {type(stransf).__name__} in place of the SampleTransform")
-    obs = field_map(stransf.otransf, int(obs_width))
+    obs = field_map(stransf.otransf, int(obs_width), normalize=True)
     before, forcing, after = split_at_forcing(_steps(stransf.atransf))
     A = int(act_width)
     if forcing is None:
-        return obs, (FieldMap(0, 1, A, None), None, field_map(tr.Operation(before), A))
-    act_in, matrix, act_out = action_maps(before, forcing, after)
+        return obs, (FieldMap(0, 1, A, None), None, field_map(tr.Operation(before), A, normalize=True))
+    act_in, matrix, act_out = action_maps(before, forcing, after, normalize=True)
     if act_in.width != A:
         raise Unrecognized(f"a forcing over {act_in.width} actuators for actions of {A} columns")
     return obs, (act_in, matrix, act_out)
@@ -227,7 +271,7 @@ def updates_statistics(wrapper):
     """A ``TransformActionWrapper`` whose step changes its transform: not frozen, over a scaling that is not frozen."""
     if wrapper.frozen or is_forcing(wrapper.transform) is not None:
         return False
-    return any(step[0] == "scale" and not step[1].frozen for step in flatten(wrapper.transform))
+    return any(step[0] == "scale" and not step[1].frozen for step in flatten(wrapper.transform, normalize=True))
 
 
 def action_store(env, stack, otherwise):

@@ -44,6 +44,13 @@ DELTA_SYMBOLS = (
 )
 MAX_DELTA_GROUPS = 2048
 DELTA_LAUNCH_FAILURE = -80
+# the ``rpn_*`` entries (include/replay/fit.h: the scaling fits of the offline evaluation,
+# pdecontrol/surrogates/evaluation/evaluate.py), a third table; refusals through ``rp_last_error`` as well
+FIT_SYMBOLS = (
+    ("rpn_moments", _i, [_p, _p, _p, _l, _i, _i, _p, _p, _l, _i, _p, _p, _p]),
+    ("rpn_workspace_doubles", _l, [_i, _i, _i, _l, _i]),
+)
+FIT_LAUNCH_FAILURE = -100
 _lib = None
 
 
@@ -54,7 +61,7 @@ class ReplayHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + DELTA_SYMBOLS, ReplayHipError, "The fused batch gather has no fallback.")
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + DELTA_SYMBOLS + FIT_SYMBOLS, ReplayHipError, "The fused batch gather has no fallback.")
     return _lib
 
 
@@ -112,6 +119,32 @@ def delta_moments(stream, obs, nxtobs, start, stride, coef, rows, n, delta, grou
     rc = load().rpd_moments(stream, obs.data_ptr(), nxtobs.data_ptr(), int(obs.shape[0]), int(obs.shape[-1]), int(start),
                                  int(stride), hipbind.ptr(coef), hipbind.ptr(rows), int(n), float(delta), int(groups),
                                  workspace.data_ptr(), sums.data_ptr(), stats.data_ptr())
+    if rc != 0:
+        error = ReplayHipError(f"libreplay_hip error {rc}: {last_error()}")
+        error.code = rc
+        raise error
+
+
+def fit_layout(N, A, forced):
+    """(offsets of the three fields, ld) of ``rpn_moments``' outputs: each field's columns, then its total."""
+    N, A = int(N), int(A)
+    return (0, N + 1, N + A + 2), (2 * N + A + 3 if forced else N + A + 2)
+
+
+def fit_workspace_doubles(N, A, forced, n, groups=0):
+    """fp64 elements of the workspace ``fit_moments`` needs; 0 where it would refuse the arguments."""
+    return int(load().rpn_workspace_doubles(int(N), int(A), int(bool(forced)), int(n), int(groups)))
+
+
+def fit_moments(stream, obs, actions, forcing, rows, n, groups, workspace, sums, stats):
+    """``rpn_moments`` on ``stream``, two or three launches: ``obs`` and ``actions`` are contiguous fp32 device tensors
+    [slab rows, (1,) N] and [slab rows, (1,) A], ``forcing`` fp32 [A, N] or None, ``rows`` int64 [n] or None (rows
+    0 ... n - 1); ``workspace`` fp64 of ``fit_workspace_doubles`` elements, ``sums`` fp64 and ``stats`` fp32 [2, ld] of
+    ``fit_layout``.  A refusal raises ``ReplayHipError`` with the status as its ``code``; nothing was enqueued then unless
+    the code is ``FIT_LAUNCH_FAILURE``."""
+    rc = load().rpn_moments(stream, obs.data_ptr(), actions.data_ptr(), int(obs.shape[0]), int(obs.shape[-1]),
+                            int(actions.shape[-1]), hipbind.ptr(forcing), hipbind.ptr(rows), int(n), int(groups),
+                            workspace.data_ptr(), sums.data_ptr(), stats.data_ptr())
     if rc != 0:
         error = ReplayHipError(f"libreplay_hip error {rc}: {last_error()}")
         error.code = rc

@@ -42,12 +42,17 @@ class Worker:
         self._last_obs = None
         self._last_stored_obs = None
 
+    def start(self, **reset_kwargs) -> None:
+        """The reset a fresh worker's first rollout makes, made now: ``envs.reset(**reset_kwargs)`` (``seed=`` for a
+        reproducible first episode) and the stored observation that goes with it."""
+        self._last_obs = self.stack.envs.reset(**reset_kwargs)
+        self._last_stored_obs = _stored(self.stack.ostore, self.stack.ostore.obs)
+
     def rollout(self, agent, stop: Callable, deterministic: bool = False) -> ExperienceReplay:
         replay = ExperienceReplay()
         envs, ostore, astore = self.stack.envs, self.stack.ostore, self.stack.astore
         if self._last_obs is None:
-            self._last_obs = envs.reset()
-            self._last_stored_obs = _stored(ostore, ostore.obs)
+            self.start()
         while not stop(replay.ntimesteps, replay.nstopped):
             with torch.no_grad():
                 actions = agent.select_action(self._last_obs, deterministic=deterministic)

@@ -179,6 +179,15 @@ class DeviceSubSeqStore:
         self.tensors = tuple(pack(store, dt) for store, dt in zip(fields, _DTYPES))
         self._steps_host = None
 
+    @classmethod
+    def over(cls, tensors, starts, total):
+        """A store over packed tensors that exist already (``tensors[f]`` is ``[total, ...]`` on one device, in the
+        dtypes ``pack`` gives; ``starts[key]`` the first row of episode ``key``): nothing is packed or copied."""
+        store = cls.__new__(cls)
+        store.device, store.tensors = tensors[0].device, tuple(tensors)
+        store.starts, store.total, store._steps_host = dict(starts), int(total), None
+        return store
+
     def gather(self, rows):
         """The seven fields of these packed rows (a device int64 tensor): one ``index_select`` per field."""
         return [t.index_select(0, rows) for t in self.tensors]

@@ -324,11 +324,12 @@ class PDETrainingModule(pl.LightningModule):
     # -- validation / test: one un-truncated rollout ------------------------------------------
     def _inverse_scaling(self, n, device):
         """[4, n] device coefficients of ``stransf.otransf.Inverse`` when it is an identity sensor and at most one
-        ``ScaleTransform`` (``False`` for the identity; None for anything else, e.g. a ``Normalize``).  The host
-        coefficients are worked out on every call (a few tiny CPU ops); they go up again only when their values change."""
+        ``ScaleTransform`` or one frozen, fitted ``Normalize`` (``False`` for the identity; None for anything else, e.g.
+        a ``Normalize`` that is not frozen).  The host coefficients are worked out on every call (a few tiny CPU ops);
+        they go up again only when their values change."""
         from pdecontrol.mbrl.recognition import Unrecognized, field_map
         try:
-            fmap = field_map(self.stransf.otransf.Inverse, n)
+            fmap = field_map(self.stransf.otransf.Inverse, n, normalize=True)
         except (Unrecognized, NotImplementedError):
             return None
         if (fmap.start, fmap.stride, fmap.width) != (0, 1, n):
