@@ -194,6 +194,37 @@ int sur_latent_chunk_backward(void* stream, const sur_chunk_params* p, const flo
                               float* dxlat_t, float* dlstates_t, float* dh0, float* dc0, int row_base, int row_count,
                               const float* saved /* what sur_latent_chunk_forward wrote */,
                               float* workspace /* sur_latent_workspace_floats */);
+/* ---- the decoded-mode loss of the latent rollout: csrc/sur_decoded.hip ---------------------------------------------------------
+ * Decoded-mode TBPTT loss in one launch (reference: pdecontrol/surrogates/training.py:100-121 with training_mode == "decoded").
+ * With prev[b,0] = states[b,0] and prev[b,t] = out_all[t-1,b] (the IC-augmented prediction):
+ *   loss          = mean over (b, t < T, i) of (prev[b,t,i] - states[b,t,i])^2       (MSE, reduction "none" + mean)
+ *   hsteploss[t]  = the same mean per time step, t < T; hsteploss[0] is exactly 0 (both sides are the same value)
+ *   dout_all      = d loss / d out_all  [T,B,1,N]: (float)(2 / (B T N)) * (out_all[t] - states[b,t+1]) for t < T-1, row T-1
+ *                   exactly zero; may be NULL
+ *   outdeltas[b,t] = ((out_all[t,b] - prev[b,t]) / delta - mean) / stdv              t < T-1: what the chunk loop's
+ *                   dscaling.Inverse(diff(cat(states[:, :1], outputs)) / delta) yields across chunk boundaries (a later chunk
+ *                   is seeded with the previous chunk's last output)
+ *   deltas[b,t]   = ((states[b,t+1] - states[b,t]) / delta - mean) / stdv            t < T-1, the bits sur_tbptt_delta_loss writes
+ *   stats         = {mean, unbiased std} of outdeltas, then of deltas (the four "Train ... Delta" metrics)
+ * states [B,T,1,N] with element strides as in sur_tbptt_delta_loss; out_all [T,B,1,N] time-major as sur_latent_chunk_forward
+ * writes it (row T-1 is not read); outdeltas, deltas [B,T-1,1,N]; hsteploss [T]; loss [1]; stats [4]; partial: scratch of
+ * 40*T doubles; ticket: one zero-initialised unsigned the kernel leaves at zero.  Elementwise values are fp32 with one rounding
+ * per operation (multiply and add are not contracted); every sum is fp64 and reduced in a fixed order by the workgroup that
+ * arrives last; no floating-point atomics.  Refused on the host before any HIP call (-1, the message starts
+ * "sur_tbptt_decoded_loss:"): a NULL pointer other than dout_all, B < 1, T < 2, N < 1, B*N > 2^30, a state stride below N,
+ * delta == 0, stdv <= 0 (or either NaN).  -2: the launch failed. */
+int sur_tbptt_decoded_loss(void* stream, const float* states, long states_bstride, long states_tstride, const float* out_all, int b,
+                           int t, int n, float delta, float mean, float stdv, float* outdeltas, float* deltas, float* dout_all,
+                           float* hsteploss, float* loss, float* stats, double* partial, unsigned int* ticket);
+
+/* The deltas of a latent rollout in one launch, time-major: d_all[k,b] = ((out_all[k,b] - prev) / delta - mean) / stdv with
+ * prev = state0[b] for k = 0 and out_all[k-1,b] afterwards -- dscaling.Inverse(diff(cat(states[:, :1], outputs)) / delta) for a
+ * dscaling that is the identity (mean 0, stdv 1) or the inverse of a Normalize with scalar statistics.  state0 [B,1,N] with
+ * state_bstride elements between samples; out_all, d_all [K,B,1,N].  Same arithmetic and the same refusals (the message starts
+ * "sur_latent_deltas:") as above. */
+int sur_latent_deltas(void* stream, const float* state0, long state_bstride, const float* out_all, int k, int b, int n, float delta,
+                      float mean, float stdv, float* d_all);
+
 /* The reductions of a surrogate's three parameter packs (two encoders, chunk) in ONE launch; bit j of overwrite_mask
  * is the `overwrite` flag of pack j. */
 int sur_flush_all_grads(void* stream, const sur_encoder_params* e0, const sur_adam* a0, const sur_encoder_params* e1,

@@ -37,6 +37,7 @@
 
 #include "../../include/surrogate_hip.h"
 #include "capi_error.h"
+#include "sur_loss_sums.h"
 #include "sur_windows.h"
 
 // Diagnostic build only (-DSUR_STAMP): shader-clock stamps per phase for workgroup 0 of each launch,
@@ -1754,38 +1755,8 @@ constexpr int LOSS_NSUM = 5;  // squared error, sum / sum of squares of predicte
 constexpr int LOSS_UNROLL = 4;
 constexpr int LOSS_MAX_SPLIT = 8;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// The end of a loss workgroup: its NSUM fp64 sums (waves first, then the waves' sums in wave order) go to `out`, the
-// workgroup's slot of the partial sums; then, unless the caller finishes the loss in a launch of its own, the workgroup takes
-// a ticket.  True for the workgroup that takes the last of `tickets`: every slot is visible to it once it has fenced.
-template <int NSUM>
-__device__ __forceinline__ bool loss_block_sums(const double (&acc)[NSUM], double* __restrict__ out, unsigned int* __restrict__ ticket,
-                                                int tickets, bool take_ticket = true) {
-    __shared__ double red[TPB / 64][NSUM];
-    __shared__ bool last;
-#pragma unroll
-    for (int j = 0; j < NSUM; ++j) {
-        const double w = wave_sum(acc[j]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < NSUM) {
-        double v = 0.0;
-        for (int w = 0; w < TPB / 64; ++w) v += red[w][threadIdx.x];
-        out[threadIdx.x] = v;
-    }
-    if (!take_ticket) return false;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = (atomicAdd(ticket, 1u) == (unsigned)(tickets - 1));
-    __syncthreads();
-    return last;
-}
+// wave_sum and loss_block_sums -- the end of a loss workgroup -- are sur_loss_sums.h's (shared with sur_decoded.hip)
+static_assert(TPB == LOSS_TPB, "the loss kernels run sur_loss_sums.h's workgroup size");
 
 __device__ void delta_loss_finish(int B, int T, int N, int nsplit, float* __restrict__ hsteploss, float* __restrict__ loss,
                                   float* __restrict__ stats, double* __restrict__ partial, unsigned int* __restrict__ ticket);

@@ -68,7 +68,13 @@ class _KernelTier:
                                                                           "_fused_validation_loss")):
             raise Unrecognized(f"a {type(module).__name__} without the captured TBPTT step of PDETrainingModule")
         surrogate = getattr(module, "surrogate", None)
-        if not isinstance(surrogate, AutoRegPDESurrogate) or not hipops.fused_supported(surrogate):
+        if hipops.fused_latent_supported(surrogate):
+            # the latent ConvLSTM: the captured decoded-mode step, on the conditions of PDETrainingModule._latent_training_step
+            constants = getattr(module, "_latent_constants", None)
+            if not callable(constants) or constants() is None:
+                raise Unrecognized(f"a latent {type(surrogate).__name__} whose loss or delta scalings the decoded-mode kernels "
+                                   f"do not take")
+        elif not isinstance(surrogate, AutoRegPDESurrogate) or not hipops.fused_supported(surrogate):
             raise Unrecognized(f"a {type(surrogate).__name__} the fused TBPTT step does not implement")
         if module._frozen_parameters():
             raise Unrecognized("a partly frozen surrogate")
@@ -286,7 +292,8 @@ def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience,
     follows ``configure_optimizers``' ``StepLR`` over ``fit.current_epoch``.
 
     The kernel tier applies when the module is on CUDA, the fused kernels are enabled, ``fused_step`` accepts the module
-    (the fused TBPTT architecture, nothing frozen), there is a single process, the datamodule has ``device_data`` on that
+    (the fused TBPTT architecture, or the latent ConvLSTM under ``PDETrainingModule._latent_constants``; nothing frozen),
+    there is a single process, the datamodule has ``device_data`` on that
     device, ``recognition.world_connector`` recognises ``datamodule.stransf`` and ``sur_gather_windows`` does not refuse
     the geometry.  Everything else runs on the loop tier over the datamodule's own loaders: ``fused_step`` on CUDA where
     the module allows it, else ``training_step -> zero_grad -> backward -> step`` with the optimizer of

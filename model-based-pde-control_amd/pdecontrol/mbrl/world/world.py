@@ -296,8 +296,11 @@ class WorldVecEnv(BaseWorldVecEnv):
             dev = _surrogate_device(self.surrogate)
             from pdecontrol.surrogates import hipops
             members = _members(self.surrogate)[0]
+            # one kernel family for the whole ensemble: every member the autoregressive layout, or every member the latent one
+            same_layout = (all(hipops.fused_supported(m) for m in members)
+                           or all(hipops.fused_latent_supported(m) for m in members))
             self.device_resident = bool(dev.type == "cuda" and ops.fused_enabled() and self.batched_reward_func is not None
-                                        and all(hipops.fused_supported(m) for m in members))
+                                        and same_layout)
         return self.device_resident
 
     def setup(self, starting: Dataset):

@@ -146,6 +146,7 @@ class GraphedTBPTTStep:
         self.autotune = pipelined is None
         self.pipelined = True if pipelined is None else bool(pipelined)
         self.used_pipelined = False
+        self.used_latent = False    # the step is module._latent_training_step (a latent surrogate on the latent kernels)
         dev = next(module.surrogate.parameters()).device
         assert dev.type == "cuda", "HIP graphs need the module on a GPU"
         self.device = dev
@@ -195,9 +196,22 @@ class GraphedTBPTTStep:
         from pdecontrol.surrogates import ops
         return ops.use_fused_for(self.module.surrogate, self.states)
 
+    def _fused_latent(self):
+        """A latent surrogate on the latent kernels (single GPU): its step is ``module._latent_training_step``."""
+        from pdecontrol.surrogates import ops
+        from pdecontrol.surrogates.surrogate import LatentAutoRegPDESurrogate
+        return (not self.distributed and isinstance(self.module.surrogate, LatentAutoRegPDESurrogate)
+                and ops.use_fused_latent_for(self.module.surrogate, self.states))
+
     def _fwd_bwd(self):
         if not self.adam_in_flush:
             self.bucket.zero_()
+        if self._fused_latent():
+            # the decoded-mode pass of a latent surrogate, hand-scheduled on one stream (no autograd, no autotune)
+            out = self.module._latent_training_step((self.states, self.actions))
+            self.used_latent = out is not None
+            if out is not None:
+                return _detached(out)
         if self.pipelined and self._fused():
             # forward, loss, backward and gradient reduction hand-scheduled with the TBPTT chunks pipelined (no autograd)
             out = self.module._pipelined_training_step((self.states, self.actions))
@@ -230,7 +244,7 @@ class GraphedTBPTTStep:
                 finally:
                     self.pipelined = self.used_pipelined = True
             packs = getattr(self.module.surrogate, "_fused_packs", None)
-            if packs is not None and self._fused() and not self.distributed:
+            if packs is not None and (self._fused() or self.used_latent) and not self.distributed:
                 # fused kernels, single GPU: the flush launches take the Adam step.  The descriptors (the surrogate's
                 # ONE set of moments / step counter / device learning rate) are lent to the packs only while a graph is
                 # being captured: the captured launches carry them by value, and any other backward pass through the

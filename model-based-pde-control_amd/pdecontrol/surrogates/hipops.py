@@ -110,6 +110,10 @@ SYMBOLS = (
                                 ctypes.c_long, ctypes.c_long]),
     ("sur_val_loss", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                           ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # the decoded-mode loss of the latent rollout and the rollout's deltas (csrc/sur_decoded.hip)
+    ("sur_tbptt_decoded_loss", _i, [_fp, _fp, ctypes.c_long, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                    ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    ("sur_latent_deltas", _i, [_fp, _fp, ctypes.c_long, _fp, _i, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _fp]),
     # the fully-connected LSTM baselines (csrc/sur_fclstm.hip; autograd node: pdecontrol/surrogates/fclstm_hip.py)
     ("sur_fc_param_count", _i, []),
     ("sur_fc_supported", _i, [_i] * 8),
@@ -658,7 +662,9 @@ def fused_supported(surrogate):
 def fused_latent_supported(surrogate):
     """True when ``surrogate`` is a LatentAutoRegPDESurrogate with the KSLatentConvolutionalLSTM layout (the same modules as
     KSAutoRegConvolutionalLSTM): ``fused_latent_rollout`` runs it.  ``fused_supported`` stays False for it, so no
-    autoreg-only path (fused TBPTT, captured steps, PackAdam, the world env's device path) ever sees one."""
+    autoreg-only path (the fused TBPTT autograd node, the split-graph step, PackAdam) ever sees one; the captured step
+    (``fused_latent_tbptt_train``), the kernel tier of the surrogate-update phase and the world env's device path ask this
+    predicate."""
     from pdecontrol.surrogates.surrogate import LatentAutoRegPDESurrogate
     return isinstance(surrogate, LatentAutoRegPDESurrogate) and _conv_lstm_layout(surrogate)
 
@@ -1035,6 +1041,33 @@ class _LatentChunkFn(torch.autograd.Function):
         return dxlat, dlst, dh0, dc0, None, None, None, None
 
 
+def latent_scale_constants(surrogate):
+    """(mean, std) such that ``surrogate.dscaling.Inverse(x) == (x - mean) / std`` -- what the latent rollout applies to the
+    differences of its decoded outputs -- for the two forms the controller builds (identity, the inverse of a Normalize with
+    scalar statistics); None for anything else."""
+    try:
+        mul, add = _dscale_constants(surrogate.dscaling)
+    except SurrogateHipError:
+        return None
+    return add, mul
+
+
+def _latent_deltas(surrogate, states, out_all):
+    """The deltas of a latent rollout as ONE launch (``sur_latent_deltas``) into time-major storage, returned as its
+    [B, K, 1, N] view; None when ``dscaling`` is no scalar affine map or the tensors are not fp32 (then torch computes them)."""
+    consts = latent_scale_constants(surrogate)
+    if consts is None or states.dtype != torch.float32 or out_all.dtype != torch.float32 or states.shape[2] != 1:
+        return None
+    k, b, _, n = out_all.shape
+    first = states[:, 0]
+    if first.stride(-1) != 1 or first.stride(0) < n:
+        first = first.contiguous()
+    d_all = torch.empty_like(out_all)
+    _check(load().sur_latent_deltas(_stream(), _ptr(first), first.stride(0), _ptr(out_all), k, b, n, float(surrogate.delta),
+                                    float(consts[0]), float(consts[1]), _ptr(d_all)))
+    return d_all.transpose(0, 1)
+
+
 def fused_latent_rollout(surrogate, states, actions, times, targets, hidden):
     """GPU rollout of LatentAutoRegPDESurrogate (same outputs as surrogate.py, and as the reference's surrogate.py:159-206):
     two encoder launches + one latent chunk.  ``deltas`` cover ALL internal steps (not picked by the targets) and
@@ -1058,7 +1091,9 @@ def fused_latent_rollout(surrogate, states, actions, times, targets, hidden):
     h_all, c_all, z_all, out_all = _LatentChunkFn.apply(lactions_t, lstates_t, hidden[0], hidden[1], owner.anchor, owner.chunk,
                                                         owner, torch.is_grad_enabled())
     outputs = out_all.transpose(0, 1)                                                   # [B, K, 1, N]
-    deltas = surrogate.dscaling.Inverse(torch.diff(torch.cat((states[:, :1], outputs), dim=1), dim=1) / surrogate.delta)
+    deltas = None if torch.is_grad_enabled() else _latent_deltas(surrogate, states, out_all)
+    if deltas is None:
+        deltas = surrogate.dscaling.Inverse(torch.diff(torch.cat((states[:, :1], outputs), dim=1), dim=1) / surrogate.delta)
     inlatents_t = torch.cat((lstates_t, z_all[s_used - 1:n_steps - 1]), dim=0)          # [K, B, cs, hq]
     pick = tidx.tolist()
     by_batch = lambda t: take_steps(t.transpose(0, 1), pick)
@@ -1336,12 +1371,20 @@ def _tbptt_backward(owner, bounds, dims, saved_state, unified, dd_all):
             forks.append(fork)
         for fork in forks:
             fork.join()
-    # every encoder backward of the step in launches of up to three jobs: all their workgroups are dispatched
-    # together (as separate launches the long action-encoder job queued behind a state-encoder job), longest first
-    jobs = [(owner.action_enc, actions_t, dxlat_all, t_total * b, 0, min(ENCODER_ROWS, owner.action_enc.c.rows), asaved)]
+    _encoders_backward(owner, actions_t, dxlat_all, asaved, seeds, dlsts, ssaved, enc_rows)
+
+
+def _encoders_backward(owner, actions_t, dxlat_all, asaved, seeds, dlsts, ssaved, enc_rows):
+    """Every encoder backward of a TBPTT pass in launches of up to three jobs: all their workgroups are dispatched
+    together (as separate launches the long action-encoder job queued behind a state-encoder job), longest first.  The
+    action encoder's one job over all T steps, then the state encoder's job of every chunk (its seed states, the gradient
+    of their latents) on ``enc_rows[c]`` partial rows of its own; marks the packs dirty."""
+    lib = load()
+    m_act = actions_t.shape[0] * actions_t.shape[1]
+    jobs = [(owner.action_enc, actions_t, dxlat_all, m_act, 0, min(ENCODER_ROWS, owner.action_enc.c.rows), asaved)]
     row0 = 0
-    for c in range(nchunks):
-        jobs.append((owner.state_enc, seeds[c], dlsts[c], lstates[c].shape[0] * b, row0, enc_rows[c], ssaved[c]))
+    for c, seed in enumerate(seeds):
+        jobs.append((owner.state_enc, seed, dlsts[c], seed.shape[0] * seed.shape[1], row0, enc_rows[c], ssaved[c]))
         row0 += enc_rows[c]
     for j0 in range(0, len(jobs), 3):
         _encoder_backward_multi(lib, jobs[j0:j0 + 3])
@@ -1538,6 +1581,91 @@ def fused_tbptt_backward(st, accumulate=False):
     _tbptt_backward(st.owner, st.bounds, (st.b, st.t_total, st.n, st.nchunks), saved, (st.h_all_u, st.c_all_u, st.saved_u),
                     st.dd_all if dd is None else dd)
     st.owner.flush_into_flat(accumulate)
+
+
+def fused_latent_tbptt_train(surrogate, states, actions, tau, tbtt, delta, mean, stdv):
+    """One whole TBPTT training pass of a LatentAutoRegPDESurrogate (``fused_latent_supported``) WITHOUT autograd, the
+    decoded-mode counterpart of ``fused_tbptt_train``: both encoders, per chunk ``sur_latent_chunk_forward`` into ONE
+    time-major ``out_all`` (chunk c > 0 is seeded from the re-encoded last output of chunk c - 1 and its last hidden state,
+    gradients cut: training.py:71-98), ``sur_tbptt_decoded_loss`` over the whole sequence, per chunk
+    ``sur_latent_chunk_backward`` on its rows of d loss / d out_all, every encoder backward, and the flush tail (the gradient
+    reduction; with lent descriptors also the clip and the Adam step).  One schedule, everything on the current stream:
+    the chunks' launches follow each other, so they share their partial-gradient rows.
+
+    The gradient scale is fixed at d loss = 1 (the captured step, ``GraphedTBPTTStep``).  Returns what
+    ``fused_tbptt_train`` returns -- (outputs [B,T,1,N], outdeltas, (H, C), loss, hsteploss, stats [4], true deltas
+    [B,T-1,1,N]) -- with ``outdeltas`` already cut to the [B,T-1,1,N] the loss section reports and ``hsteploss`` [T]."""
+    b, t_total, _, n = actions.shape
+    if t_total < 2:
+        raise SurrogateHipError("fused_latent_tbptt_train needs at least two time steps")
+    owner = packs_for(surrogate, n, b)
+    lib = load()
+    dev = actions.device
+    cs, hq, ca = owner.chunk.c.cs, owner.chunk.c.hq, owner.chunk.c.ca
+    s_lat = cs * hq
+    bounds = [(k0, min(k0 + tbtt, t_total)) for k0 in range(0, t_total, tbtt)]
+    if states.stride(3) != 1:
+        states = states.contiguous()
+    # partial-gradient rows, reserved before the first launch (growing a buffer re-points the packs)
+    rows = max(b, CHUNK_ROWS)
+    enc_rows = [min(ENCODER_ROWS, (tau if c == 0 else 1) * b) for c in range(len(bounds))]
+    owner.chunk.ensure_rows(rows)
+    owner.state_enc.ensure_rows(sum(enc_rows))
+    owner.refresh_partials()
+    new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+
+    def encode(pack, x, m, z):
+        saved = _encoder_saved_buffer(pack, m, dev)
+        _check(lib.sur_encoder_forward(_stream(), ctypes.byref(pack.c), _ptr(x), m, _ptr(z), _ptr(saved)))
+        return saved
+
+    actions_t = actions.transpose(0, 1).contiguous()                    # [T, B, 1, N]
+    lactions_t = new(t_total, b, ca, hq)
+    asaved = encode(owner.action_enc, actions_t, t_total * b, lactions_t)
+    tm = surrogate.transition_model
+    h0, c0 = tm.H0.detach().contiguous(), tm.C0.detach().contiguous()   # one [cs, hq] state shared by the batch
+    h_all, c_all, z_all = new(t_total, b, cs, hq), new(t_total, b, cs, hq), new(t_total, b, cs, hq)
+    out_all = new(t_total, b, 1, n)
+    saved = _saved_buffer(owner.chunk, t_total, b, dev)
+    seeds, lstates, ssaved, hidden = [], [], [], []
+    for c, (k0, k1) in enumerate(bounds):
+        # chunk 0 warms up on the first tau true states; a later chunk restarts from the previous chunk's last prediction
+        seed = states[:, :tau].transpose(0, 1).contiguous() if c == 0 else out_all[k0 - 1:k0]
+        lst = new(seed.shape[0], b, cs, hq)
+        ssaved.append(encode(owner.state_enc, seed, seed.shape[0] * b, lst))
+        seeds.append(seed)
+        lstates.append(lst)
+        hidden.append((h0, c0, 0) if c == 0 else (h_all[k0 - 1], c_all[k0 - 1], s_lat))
+        hc = hidden[c]
+        _check(lib.sur_latent_chunk_forward(_stream(), ctypes.byref(owner.chunk.c), _ptr(lactions_t[k0:k1]), _ptr(lst), _ptr(hc[0]),
+                                            _ptr(hc[1]), hc[2], k1 - k0, min(seed.shape[0], k1 - k0), b, _ptr(h_all[k0:k1]),
+                                            _ptr(c_all[k0:k1]), _ptr(z_all[k0:k1]), _ptr(out_all[k0:k1]), _ptr(saved[k0:k1])))
+
+    outdeltas, deltas = new(b, t_total - 1, 1, n), new(b, t_total - 1, 1, n)
+    hstep, loss, stats = new(t_total), new(), new(4)
+    dout_all = new(t_total, b, 1, n)
+    scratch = owner.loss_scratch.get(("decoded", t_total))
+    if scratch is None:
+        scratch = owner.loss_scratch[("decoded", t_total)] = (torch.empty(40 * t_total, device=dev, dtype=torch.float64),
+                                                              torch.zeros(1, device=dev, dtype=torch.int32))
+    _check(lib.sur_tbptt_decoded_loss(_stream(), _ptr(states), states.stride(0), states.stride(1), _ptr(out_all), b, t_total, n,
+                                      float(delta), float(mean), float(stdv), _ptr(outdeltas), _ptr(deltas), _ptr(dout_all),
+                                      _ptr(hstep), _ptr(loss), _ptr(stats), _ptr(scratch[0]), _ptr(scratch[1])))
+
+    dxlat_all = torch.empty_like(lactions_t)
+    work = new(lib.sur_latent_workspace_floats(ctypes.byref(owner.chunk.c), max(k1 - k0 for k0, k1 in bounds), b))
+    dlsts = []
+    for c, (k0, k1) in enumerate(bounds):
+        dlst = torch.zeros_like(lstates[c])      # d loss / d z_{-1} is ADDED to row 0 (include/surrogate_hip.h)
+        hc = hidden[c]
+        _check(lib.sur_latent_chunk_backward(_stream(), ctypes.byref(owner.chunk.c), _ptr(lactions_t[k0:k1]), _ptr(lstates[c]),
+                                             _ptr(hc[0]), _ptr(hc[1]), hc[2], _ptr(h_all[k0:k1]), _ptr(c_all[k0:k1]),
+                                             _ptr(dout_all[k0:k1]), None, None, None, k1 - k0, min(seeds[c].shape[0], k1 - k0), b,
+                                             _ptr(dxlat_all[k0:k1]), _ptr(dlst), None, None, 0, rows, _ptr(saved[k0:k1]), _ptr(work)))
+        dlsts.append(dlst)
+    _encoders_backward(owner, actions_t, dxlat_all, asaved, seeds, dlsts, ssaved, enc_rows)
+    owner.flush()
+    return out_all.transpose(0, 1), outdeltas, (h_all[-1], c_all[-1]), loss, hstep, stats, deltas
 
 
 # ---------------------------------------------------------------------------------------------

@@ -168,6 +168,48 @@ class PDETrainingModule(pl.LightningModule):
         return {"loss": loss, "hsteploss": hsteploss, "outputs": outputs, "actions": actions.detach(),
                 "states": states.detach(), "outdeltas": outdeltas[:, :-1], "deltas": deltas}
 
+    def _latent_constants(self):
+        """(mean, std) of the decoded-mode kernels (``sur_tbptt_decoded_loss``, ``sur_latent_deltas``) when the configuration
+        is the controller's for a latent surrogate: decoded mode, MSELoss(reduction="none"), and ``undscaling`` and the
+        surrogate's ``dscaling.Inverse`` reducing to the SAME scalar constants (both wrap one Normalize, mbrl.py:168-171; the
+        kernels apply one pair to the true and to the predicted deltas).  None otherwise."""
+        if not isinstance(self.surrogate, LatentAutoRegPDESurrogate) or self.training_mode != "decoded":
+            return None
+        if not (isinstance(self.loss, torch.nn.MSELoss) and self.loss.reduction == "none"):
+            return None
+        from pdecontrol.surrogates import hipops
+        consts = hipops.undscale_constants(self.undscaling)
+        if consts is None or consts != hipops.latent_scale_constants(self.surrogate):
+            return None
+        return consts
+
+    def _latent_training_step(self, batch):
+        """``_pipelined_training_step`` for a latent surrogate on the fused kernels (``hipops.fused_latent_tbptt_train``): the
+        whole decoded-mode pass -- forward, ``sur_tbptt_decoded_loss``, backward, gradient reduction (+ clip and Adam when the
+        captured step lent its descriptors) -- without autograd and with d loss = 1, so for the captured step only
+        (``GraphedTBPTTStep``).  None when ``_latent_constants`` is, the surrogate does not run on the latent kernels or the
+        batch is not fp32 [B, T >= 2, 1, N]: then today's route runs."""
+        from pdecontrol.surrogates import ops
+        states, actions, *_ = batch
+        consts = self._latent_constants()
+        if consts is None or not (states.is_cuda and ops.use_fused_latent_for(self.surrogate, states)):
+            return None
+        if states.dtype != torch.float32 or states.shape[2] != 1 or actions.shape[1] < 2 or states.shape[1] != actions.shape[1]:
+            return None
+        from pdecontrol.surrogates import hipops
+        with torch.no_grad():
+            outputs, outdeltas, _hidden, loss, hsteploss, stats, deltas = hipops.fused_latent_tbptt_train(
+                self.surrogate, states, actions, self.tau, self.tbtt, self.delta, *consts)
+        logged = {"Train Loss": loss, "Train Mean Delta Output": stats[0], "Train Std. Delta Output": stats[1],
+                  "Train Mean Delta": stats[2], "Train Std. Delta": stats[3]}
+        if torch.cuda.is_current_stream_capturing():
+            self.__dict__["_graph_logged"] = logged
+        else:
+            for name, value in logged.items():
+                self.log(name, value, on_step=False, on_epoch=True)
+        return {"loss": loss, "hsteploss": hsteploss, "outputs": outputs, "actions": actions.detach(),
+                "states": states.detach(), "outdeltas": outdeltas, "deltas": deltas}
+
     def training_step(self, batch, bidx):
         states = batch[0]
         if self.graphed and states.is_cuda:
@@ -346,13 +388,18 @@ class PDETrainingModule(pl.LightningModule):
         ``_fused_delta_loss`` plus a recognised ``stransf.otransf.Inverse``; None otherwise (then the torch ops run).
         ``accum`` / ``outputs``: the epoch accumulator and the switch of ``hipops.fused_val_loss`` (the surrogate-update
         phase keeps an epoch's sums on the device and needs neither ``deltas`` nor the decoded outputs)."""
-        from pdecontrol.surrogates import ops
-        if not (isinstance(self.surrogate, AutoRegPDESurrogate) and states.is_cuda and ops.use_fused_for(self.surrogate, states)):
-            return None
-        if self.training_mode != "delta" or not (isinstance(self.loss, torch.nn.MSELoss) and self.loss.reduction == "none"):
-            return None
-        from pdecontrol.surrogates import hipops
-        consts = hipops.undscale_constants(self.undscaling)
+        from pdecontrol.surrogates import hipops, ops
+        if isinstance(self.surrogate, LatentAutoRegPDESurrogate):
+            # the latent rollout under no_grad hands out its deltas as a view of time-major storage (sur_latent_deltas)
+            consts = self._latent_constants()
+            if consts is None or not (states.is_cuda and ops.use_fused_latent_for(self.surrogate, states)):
+                return None
+        else:
+            if not (isinstance(self.surrogate, AutoRegPDESurrogate) and states.is_cuda and ops.use_fused_for(self.surrogate, states)):
+                return None
+            if self.training_mode != "delta" or not (isinstance(self.loss, torch.nn.MSELoss) and self.loss.reduction == "none"):
+                return None
+            consts = hipops.undscale_constants(self.undscaling)
         if consts is None or states.dtype != torch.float32 or states.shape[2] != 1 or states.shape[1] < 2:
             return None
         if tuple(out.outputs.shape) != tuple(states.shape) or tuple(out.deltas.shape) != tuple(states.shape):
