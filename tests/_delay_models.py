@@ -117,6 +117,87 @@ def elu_preactivations(module, run):
     return torch.cat(seen)
 
 
+class EluByExp(torch.autograd.Function):
+    """An emulated fault: exp(x) - 1 rounded in fp32 where a kernel has expm1f; the slope from the output, y + 1."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = torch.where(x > 0, x, torch.exp(x) - 1)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        return g * torch.where(y > 0, torch.ones_like(y), y + 1)
+
+
+class EluFlooredSlope(torch.autograd.Function):
+    """An emulated fault: the ELU slope y + 1 floored at 1e-3: bit-identical wherever the pre-activation is above
+    log(1e-3) = -6.9."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = torch.nn.functional.elu(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        return g * torch.where(y > 0, torch.ones_like(y), torch.clamp(y + 1, min=1e-3))
+
+
+class TanhAbsSlope(torch.autograd.Function):
+    """An emulated fault: the tanh slope taken as 1 - |y| where a kernel has 1 - y*y."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = torch.tanh(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        return g * (1 - y.abs())
+
+
+class TanhFlooredSlope(torch.autograd.Function):
+    """An emulated fault: the tanh slope 1 - y*y floored at 1e-3, a "safety" clamp: bit-identical wherever |y| < 0.9995."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = torch.tanh(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        return g * torch.clamp(1 - y * y, min=1e-3)
+
+
+class Act(torch.nn.Module):
+    """An activation module around an autograd Function."""
+
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+    def forward(self, x):
+        return self.fn.apply(x)
+
+
+def swap_activation(sur, cls, fn):
+    """Replace every activation module of exactly type ``cls`` in ``sur`` by ``Act(fn)``."""
+    for m in list(sur.modules()):
+        for name, child in list(m.named_children()):
+            if type(child) is cls:
+                setattr(m, name, Act(fn))
+    return sur
+
+
 def small_states(B, S, amp, seed):
     """[B, S, 1, 64] fp64 smooth fields amp * (sin(x + phi) + 0.5 cos(2 x + psi)) about zero, random phases per field: the
     state near the fixed point the dissipation controller drives to."""
@@ -283,12 +364,13 @@ def tensor_errors(got, ref):
     return {n: _rel(np.asarray(got[n]), np.asarray(ref[n])) for n in ref}
 
 
-def slice_errors(got, ref):
-    """{name: worst over its non-zero slices of max |g - g_ref| / max |g_ref| over the SLICE}."""
+def slice_errors(got, ref, slices=grad_slices):
+    """{name: worst over its non-zero slices of max |g - g_ref| / max |g_ref| over the SLICE}; ``slices``: the splitting
+    rule (``grad_slices`` here, tests/_fclstm_models.py has its own)."""
     out = {}
     for n in ref:
         g, r = np.asarray(got[n]), np.asarray(ref[n])
-        errs = [_rel(g[idx], r[idx]) for _, idx in grad_slices(n, r) if np.any(r[idx])]
+        errs = [_rel(g[idx], r[idx]) for _, idx in slices(n, r) if np.any(r[idx])]
         out[n] = max(errs) if errs else 0.0
     return out
 
@@ -301,12 +383,14 @@ def bars(yardstick, ref, floor):
             {n: max(floor, 4 * e) for n, e in slice_errors(yardstick, ref).items()})
 
 
-def check_slices(label, got, ref, tol):
-    """Every slice (``grad_slices``) of every gradient in ``ref``: one whose fp64 reference is non-zero lies within ``tol``
+def check_slices(label, got, ref, tol, slices=grad_slices, zero_tol=None):
+    """Every slice (``slices``) of every gradient in ``ref``: one whose fp64 reference is non-zero lies within ``tol``
     (a number or {name: number}) of that SLICE's own maximum; one whose reference is identically zero (context slot 0,
-    the d_states rows su..S, whatever the loss does not reach) is at most GRAD_TOL x the reference tensor's scale, which
-    is exactly zero where the whole tensor is.  No slice is left out.  Returns (worst error, "name[slice]")."""
+    the d_states rows su..S, whatever the loss does not reach) is at most ``zero_tol`` (GRAD_TOL when None; 0 admits
+    only exact zeros) x the reference tensor's scale, which is exactly zero where the whole tensor is.  No slice is left
+    out.  Returns (worst error, "name[slice]")."""
     from conftest import GRAD_TOL
+    zero_tol = GRAD_TOL if zero_tol is None else zero_tol
     assert set(got) == set(ref), (label, sorted(set(got) ^ set(ref)))
     worst, bad = (0.0, None), []
     for n in ref:
@@ -314,7 +398,7 @@ def check_slices(label, got, ref, tol):
         assert g.shape == r.shape, (label, n, g.shape, r.shape)
         t = tol[n] if isinstance(tol, dict) else tol
         covered = np.zeros(r.shape, dtype=bool)
-        for tag, idx in grad_slices(n, r):
+        for tag, idx in slices(n, r):
             covered[idx] = True
             if np.any(r[idx]):
                 err = _rel(g[idx], r[idx])
@@ -323,7 +407,7 @@ def check_slices(label, got, ref, tol):
                 if not err <= t:
                     bad.append(f"{n}[{tag}] off by {err:.3e} of the slice's scale (tolerance {t:.1e})")
             else:
-                stray, bound = float(np.abs(g[idx]).max()), GRAD_TOL * float(np.abs(r).max())
+                stray, bound = float(np.abs(g[idx]).max()), zero_tol * float(np.abs(r).max())
                 if not stray <= bound:
                     bad.append(f"{n}[{tag}] is zero in fp64 but reaches {stray:.3e} (at most {bound:.1e})")
         assert covered.all(), (label, n)
@@ -336,17 +420,17 @@ def scale_error(got, ref):
     return float(np.abs(got - ref).max()) / max(1.0, float(np.abs(ref).max()))
 
 
-def observed_path():
+def observed_path(name="delay_regimes"):
     from conftest import GRAD_LOG
-    return os.path.join(os.path.dirname(GRAD_LOG), "delay_regimes_observed.jsonl")
+    return os.path.join(os.path.dirname(GRAD_LOG), f"{name}_observed.jsonl")
 
 
-def observe(rec):
-    """Append one record to delay_regimes_observed.jsonl next to the gradient parity log."""
-    print("delay regimes", json.dumps(rec))
+def observe(rec, name="delay_regimes"):
+    """Append one record to ``name``_observed.jsonl next to the gradient parity log."""
+    print(name.replace("_", " "), json.dumps(rec))
     try:
-        os.makedirs(os.path.dirname(observed_path()), exist_ok=True)
-        with open(observed_path(), "a") as f:
+        os.makedirs(os.path.dirname(observed_path(name)), exist_ok=True)
+        with open(observed_path(name), "a") as f:
             f.write(json.dumps(rec) + "\n")
     except OSError:
         pass
@@ -357,12 +441,12 @@ def worst_of(errors):
     return {"name": name, "err": errors[name]}
 
 
-def worst_slice(got, ref):
+def worst_slice(got, ref, slices=grad_slices):
     """{"name": "tensor[slice]", "err": ...} of the worst non-zero slice; judges nothing."""
     table = {}
     for n in ref:
         g, r = np.asarray(got[n]), np.asarray(ref[n])
-        table.update({f"{n}[{tag}]": _rel(g[idx], r[idx]) for tag, idx in grad_slices(n, r) if np.any(r[idx])})
+        table.update({f"{n}[{tag}]": _rel(g[idx], r[idx]) for tag, idx in slices(n, r) if np.any(r[idx])})
     return worst_of(table)
 
 

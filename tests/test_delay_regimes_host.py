@@ -179,81 +179,10 @@ def test_zero_rule_cases_have_the_zero_slices_they_are_there_for():
 # ---------------------------------------------------------------------------------------------------------------------
 # mutations
 # ---------------------------------------------------------------------------------------------------------------------
-class _EluByExp(torch.autograd.Function):
-    """(b): exp(x) - 1 rounded in fp32 where the kernel has expm1f; the slope from the output, y + 1, as act_slope."""
-
-    @staticmethod
-    def forward(ctx, x):
-        y = torch.where(x > 0, x, torch.exp(x) - 1)
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        y, = ctx.saved_tensors
-        return g * torch.where(y > 0, torch.ones_like(y), y + 1)
-
-
-class _EluFlooredSlope(torch.autograd.Function):
-    """(b'): the ELU slope y + 1 floored at 1e-3: bit-identical wherever the pre-activation is above log(1e-3) = -6.9."""
-
-    @staticmethod
-    def forward(ctx, x):
-        y = torch.nn.functional.elu(x)
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        y, = ctx.saved_tensors
-        return g * torch.where(y > 0, torch.ones_like(y), torch.clamp(y + 1, min=1e-3))
-
-
-class _TanhAbsSlope(torch.autograd.Function):
-    """(c): the tanh slope taken as 1 - |y| where the kernel has 1 - y*y."""
-
-    @staticmethod
-    def forward(ctx, x):
-        y = torch.tanh(x)
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        y, = ctx.saved_tensors
-        return g * (1 - y.abs())
-
-
-class _TanhFlooredSlope(torch.autograd.Function):
-    """(c'): the tanh slope 1 - y*y floored at 1e-3, a "safety" clamp: bit-identical wherever |y| < 0.9995."""
-
-    @staticmethod
-    def forward(ctx, x):
-        y = torch.tanh(x)
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        y, = ctx.saved_tensors
-        return g * torch.clamp(1 - y * y, min=1e-3)
-
-
-class _Act(torch.nn.Module):
-    def __init__(self, fn):
-        super().__init__()
-        self.fn = fn
-
-    def forward(self, x):
-        return self.fn.apply(x)
-
-
-def _swap(sur, cls, fn):
-    for m in list(sur.modules()):
-        for name, child in list(m.named_children()):
-            if type(child) is cls:
-                setattr(m, name, _Act(fn))
-    return sur
+# (b) exp(x) - 1 for expm1f, (b') the ELU slope floored at 1e-3, (c) the tanh slope as 1 - |y|, (c') the tanh slope floored
+# at 1e-3: the emulations tests/test_fclstm_regimes_host.py shares (tests/_delay_models.py)
+_EluByExp, _EluFlooredSlope, _TanhAbsSlope, _TanhFlooredSlope = dm.EluByExp, dm.EluFlooredSlope, dm.TanhAbsSlope, dm.TanhFlooredSlope
+_swap = dm.swap_activation
 
 
 def _layernorm_eps(sur, eps):
