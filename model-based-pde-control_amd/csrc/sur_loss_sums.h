@@ -1,5 +1,6 @@
 // sur_loss_sums.h -- the `partial` / `ticket` convention of the one-launch losses of libsurrogate_hip.so, spelled once:
-// sur_kernels.hip (delta loss, validation loss) and sur_decoded.hip (decoded loss) both end their workgroups with it.
+// sur_loss.h (delta loss, validation loss: a part of sur_kernels.hip) and sur_decoded.hip (decoded loss) both end their
+// workgroups with it.
 //
 // Every workgroup of a loss adds its terms in fp64 per thread, reduces them here in a fixed order and stores the sums in
 // its own slot of the caller's `partial` scratch with plain stores; then it fences and takes a ticket.  The workgroup

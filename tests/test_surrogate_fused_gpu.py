@@ -212,7 +212,7 @@ def test_ensemble_parallel_step_equals_member_by_member(dev):
 def test_encoder_saved_activations_backward_matches_recompute(dev, N, monkeypatch):
     """Encoder backward fed with the forward's saved intermediates (one residual block per launch) against the
     whole-encoder kernel that recomputes them: same forward, gradients equal up to summation grouping.  For the 1-2-4-4
-    action encoder this is also the one-wave-per-sample VALU blocks (csrc/sur_kernels.hip ``nr_*``: the per-block launches
+    action encoder this is also the one-wave-per-sample VALU blocks (csrc/sur_narrow.h ``nr_*``: the per-block launches
     route it there) against the MFMA gather-GEMM blocks of the whole-encoder kernel, at three widths."""
     from pdecontrol.surrogates import hipops, ops
     g = torch.Generator().manual_seed(3)

@@ -314,7 +314,7 @@ def test_adam_apply_skips_a_pack_without_a_descriptor():
 
 def test_adam_apply_and_flush_agree_bit_for_bit_from_equal_inputs():
     """sur_adam_apply and the flush from the same parameters, moments and (the flush's own) gradient, three updates.  Both
-    launches run the one adam_update of sur_kernels.hip, so p', m' and v' agree bit for bit on every update; the outcome
+    launches run the one adam_update of csrc/sur_tail.h, so p', m' and v' agree bit for bit on every update; the outcome
     (and, should they ever part, the largest difference in units) is recorded as well."""
     names = ("wide", "odd", "tiny")
     a, b = _packs(names, [FLUSH_ROWS] * 3), _packs(names, [FLUSH_ROWS] * 3)
