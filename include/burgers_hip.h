@@ -31,6 +31,36 @@ extern "C" {
 int bg_step(void* stream, float* u, const float* actions, const float* F, int n_act, int n_envs, int N, float dx, float dt,
             float nu, long n_substeps, float* obs, double* ssq_sum, int* status);
 
+/* T successive bg_step launches in one: step t takes row t of actions [T,E,n_act] (never NULL here), advances u by
+ * n_substeps sub-steps and stores the state to traj[t+1] (traj [T+1,E,N]; slot 0 is not touched), ssq[t] and status[t]
+ * (ssq fp64 [T,E], status int [T,E]; either may be NULL).  The state stays in registers between the steps and u is stored
+ * once, after the last.  Every output byte equals what
+ *   for t: bg_step(stream, u, actions + t*E*n_act, F, ..., obs = traj + (t+1)*E*N, ssq + t*E, status + t*E)
+ * leaves: the same operations in the same order, the same reduction.  Refused on the host before any HIP call, with a
+ * message that starts with "bg_step_span:": NULL u / actions / F / traj, T < 1, n_envs < 1, n_act outside 1 ... 16, an N
+ * bg_step refuses, n_substeps < 0, dx or dt not positive, nu negative. */
+int bg_step_span(void* stream, float* u, const float* actions, const float* F, int n_act, int n_envs, int N, int T, float dx,
+                 float dt, float nu, long n_substeps, float* traj, double* ssq, int* status);
+
+/* The T * E transitions of T consecutive steps without a truncation, read where bg_step / bg_step_span left them and
+ * written as rows of a device-resident replay: the counterpart of ks_record_device (include/kspde.h) without a handle.
+ * bg_slabs is a HOST struct of DEVICE pointers with the layout of ks_record: obs / nxtobs fp32 [rows,N], actions fp32
+ * [rows,A], rewards fp32 [rows], terminated / truncated bytes [rows], steps int [rows].  Transition (t, e) writes row
+ * d_dst[t][e] (a negative entry writes nothing): obs = traj[t][e], nxtobs = traj[t+1][e], the action and steps of (t, e),
+ * terminated = truncated = 0 and rewards = (float)(ssq[t][e] * c), c = -(1.0 / (double)N) / (double)max(n_substeps, 1):
+ * BurgersBatchedVecEnv.step_torch's reward, one fp64 product, cast to fp32.  dst_host is d_dst on the host: every refusal
+ * (NULL pointers, T < 1, n_envs < 1, N < 1, A outside 1 ... 16, n_substeps < 0, slabs without rows, an entry >= rows, a row
+ * named twice) is made from it before any HIP call, with a message that starts with "bg_record:".  One launch; it does not
+ * synchronise and does not allocate device memory. */
+typedef struct bg_slabs {
+    float* obs; float* actions; float* nxtobs; float* rewards;
+    unsigned char* terminated; unsigned char* truncated; int* steps; long rows;
+} bg_slabs;
+
+int bg_record(void* stream, const float* d_traj /* [T+1][E][N] */, const float* d_actions /* [T][E][A] */, int n_envs, int N,
+              int A, const double* d_ssq /* [T][E] */, const int* d_steps /* [T][E] */, int T, long n_substeps,
+              const long* d_dst /* [T][E] */, const long* dst_host, const bg_slabs* out);
+
 /* test hook: out [n_rows,N] = nu * laplace(u) - u * grad(u) + phi (phi may be NULL) */
 int bg_residual(void* stream, const float* u, const float* phi, int n_rows, int N, float dx, float nu, float* out);
 

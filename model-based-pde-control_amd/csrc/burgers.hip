@@ -13,12 +13,17 @@
 // Built with -ffp-contract=off: every device operation below is one rounded fp32 operation or one explicit fmaf, in the
 // order oracle/burgers_oracle.c restates as flat loops.  tests/test_burgers_gpu.py holds bg_step (scalar, packed and
 // pair-native forms), bg_phyloss_forward and bg_residual to that twin bit for bit.
+//
+// The collection phase's two entries (pdecontrol/mbrl/collection_phase.py): bg_step_span, T steps in one launch with the
+// state held in VGPRs between them, and bg_record, a segment's transitions into the slabs of the device-resident replay.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <vector>
 
 #include "../../include/burgers_hip.h"
 #include "capi_error.h"
+#include "row_ops.h"
 
 namespace {
 
@@ -222,6 +227,178 @@ __global__ void __launch_bounds__(256) bg_step_kernel(const Args a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The three parts of a step, as bg_step_span_kernel takes them.  They restate bg_step_kernel's body operation for
+// operation; that kernel keeps its own inline spelling (called through these its schedule moves by a few instructions,
+// and its code object is held to what it was).  tests/test_burgers_span_gpu.py holds the two to each other bit for bit.
+//
+// phi = act @ F at the lane's P points: one rounded product, then one fmaf per further actuator, in index order
+template <int P>
+__device__ __forceinline__ void forcing(const float* act, const Args& a, int lane, float (&phi)[P]) {
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int i = lane * P + j;
+        float acc = act[0] * a.F[i];
+        for (int k = 1; k < a.n_act; ++k) acc = fmaf(act[k], a.F[(size_t)k * a.N + i], acc);
+        phi[j] = acc;
+    }
+}
+
+// a.n_substeps midpoint sub-steps of the lane's P points with phi held; racc += the reward term of every sub-step
+template <int P>
+__device__ __forceinline__ void advance(float (&u)[P], const float (&phi)[P], const Args& a, double& racc) {
+    if constexpr (P >= 4) {
+        constexpr int H = P / 2;
+        f32x2 U[H], PH[H];
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+            U[k] = f32x2{u[2 * k], u[2 * k + 1]};
+            PH[k] = f32x2{phi[2 * k], phi[2 * k + 1]};
+        }
+        const f32x2 hdt2 = {a.hdt, a.hdt}, dt2 = {a.dt, a.dt};
+        for (long s = 0; s < a.n_substeps; ++s) {
+            float q = 0.0f;
+#pragma unroll
+            for (int k = 0; k < H; ++k) {            // same order as the scalar form: u[0], u[1], ...
+                q = fmaf(U[k][0], U[k][0], q);
+                q = fmaf(U[k][1], U[k][1], q);
+            }
+            racc += (double)q;
+            f32x2 R[H], UT[H];
+            residual_pairs<H>(U, PH, a, R);
+#pragma unroll
+            for (int k = 0; k < H; ++k) UT[k] = __builtin_elementwise_fma(hdt2, R[k], U[k]);
+            residual_pairs<H>(UT, PH, a, R);
+#pragma unroll
+            for (int k = 0; k < H; ++k) U[k] = __builtin_elementwise_fma(dt2, R[k], U[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+            u[2 * k] = U[k][0];
+            u[2 * k + 1] = U[k][1];
+        }
+    } else
+    for (long s = 0; s < a.n_substeps; ++s) {
+        float w[P + 4], r[P], ut[P];
+        float q = 0.0f;
+#pragma unroll
+        for (int j = 0; j < P; ++j) q = fmaf(u[j], u[j], q);
+        racc += (double)q;                       // reward term of this sub-step, before the update
+        window<P>(u, w);
+        residual<P>(w, phi, a, r);
+#pragma unroll
+        for (int j = 0; j < P; ++j) ut[j] = fmaf(a.hdt, r[j], u[j]);
+        window<P>(ut, w);
+        residual<P>(w, phi, a, r);
+#pragma unroll
+        for (int j = 0; j < P; ++j) u[j] = fmaf(a.dt, r[j], u[j]);
+    }
+}
+
+// the wave's reward sum and non-finite flag, by xor shuffles: every lane ends with both
+template <int P>
+__device__ __forceinline__ int settle(const float (&u)[P], double& racc) {
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < P; ++j) bad |= !__builtin_isfinite(u[j]);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        racc += __shfl_xor(racc, m, 64);
+        bad |= __shfl_xor(bad, m, 64);
+    }
+    return bad;
+}
+
+// bg_step_span: T env steps of one launch.  The layout and every operation of a step are bg_step_kernel's (forcing,
+// advance, settle), so a step's bytes are those of a bg_step launch; what the span saves is T - 1 launches and the
+// round trip of u through HBM between them.  Step t reads row t of the action table [T][E][A], stores the
+// state to traj slot t + 1 and, by lane 0, ssq[t][e] and status[t][e]; u is stored once, after the last step.  F is
+// re-read per step (A x P values per lane from L2 against n_substeps sub-steps of arithmetic): held in registers it would
+// not fit at A = 16, P = 16.
+struct SpanArgs {
+    Args s;                    // u, F, n_act, n_envs, N, n_substeps, coefficients; actions = the table; obs/ssq_sum/status unused
+    float* traj;               // [T + 1][E][N], slot 0 is not touched
+    double* ssq;               // [T][E] or null
+    int* status;               // [T][E] or null
+    int T;
+};
+
+template <int P>
+__global__ void __launch_bounds__(256) bg_step_span_kernel(const SpanArgs a) {
+    const Args& s = a.s;
+    const int lane = threadIdx.x & 63;
+    const int slot = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const bool active = slot < s.n_envs;
+    const int env = active ? slot : s.n_envs - 1;   // tail waves redo the last env (their lanes must still rotate)
+    const size_t off = (size_t)env * s.N + (size_t)lane * P;
+    const size_t slab = (size_t)s.n_envs * s.N;
+
+    float u[P], phi[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) u[j] = s.u[off + j];
+    for (int t = 0; t < a.T; ++t) {
+        const size_t cell = (size_t)t * s.n_envs + env;
+        forcing<P>(s.actions + cell * s.n_act, s, lane, phi);
+        double racc = 0.0;
+        advance<P>(u, phi, s, racc);
+        const int bad = settle<P>(u, racc);
+        if (active) {
+            float* out = a.traj + (size_t)(t + 1) * slab + off;
+#pragma unroll
+            for (int j = 0; j < P; ++j) out[j] = u[j];
+            if (lane == 0) {
+                if (a.ssq) a.ssq[cell] = racc;
+                if (a.status) a.status[cell] = bad;
+            }
+        }
+    }
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) s.u[off + j] = u[j];
+    }
+}
+
+// bg_record: transition w = t * E + e of a segment goes to replay row dst[w].  A wave owns a transition, lanes run along
+// the columns (ks_record_kernel's shape, csrc/ks_record.hip).  The reward is (float)(ssq * c) with c formed on the host:
+// BurgersBatchedVecEnv.step_torch's one fp64 product, cast as the replay casts it.  Plain vector stores only.
+struct RecordArgs {
+    const float* traj;         // [T + 1][E][N]
+    const float* actions;      // [T][E][A]
+    const double* ssq;         // [T][E]
+    const int* steps;          // [T][E]
+    const long* dst;           // [T][E]
+    bg_slabs out;
+    long n;                    // T * E
+    int E, N, A;
+    int vec_obs, vec_act;
+    double c;                  // -(1.0 / N) / max(n_substeps, 1)
+};
+
+__device__ __forceinline__ void place_row(const float* __restrict__ in, float* __restrict__ out, int n, bool vec, int lane) {
+    if (vec) {
+        for (int j = 4 * lane; j < n; j += 4 * WAVE) *reinterpret_cast<f4*>(out + j) = *reinterpret_cast<const f4*>(in + j);
+    } else {
+        for (int j = lane; j < n; j += WAVE) out[j] = in[j];
+    }
+}
+
+__global__ void __launch_bounds__(NT) bg_record_kernel(const RecordArgs a) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (w >= a.n) return;
+    const long r = a.dst[w];
+    if (r < 0 || r >= a.out.rows) return;            // negative: skipped by contract; beyond the slab: never written
+    place_row(a.traj + w * a.N, a.out.obs + r * a.N, a.N, a.vec_obs, lane);
+    place_row(a.traj + (w + a.E) * a.N, a.out.nxtobs + r * a.N, a.N, a.vec_obs, lane);
+    place_row(a.actions + w * a.A, a.out.actions + r * a.A, a.A, a.vec_act, lane);
+    if (lane == 0) {
+        a.out.rewards[r] = __double2float_rn(__dmul_rn(a.ssq[w], a.c));
+        a.out.steps[r] = a.steps[w];
+        a.out.terminated[r] = 0;
+        a.out.truncated[r] = 0;
+    }
+}
+
 __global__ void bg_residual_kernel(const float* __restrict__ u, const float* __restrict__ phi, int n_rows, int N, float half_inv_dx,
                                    float l0, float l1, float l2, float* __restrict__ out) {
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -242,6 +419,14 @@ int launch(const Args& a, hipStream_t st) {
     const int grid = (a.n_envs + waves_per_block - 1) / waves_per_block;
     hipLaunchKernelGGL(bg_step_kernel<P>, dim3(grid), dim3(64 * waves_per_block), 0, st, a);
     return launch_status(-2, "bg_step");
+}
+
+template <int P>
+int launch_span(const SpanArgs& a, hipStream_t st) {
+    const int waves_per_block = 4;
+    const int grid = (a.s.n_envs + waves_per_block - 1) / waves_per_block;
+    hipLaunchKernelGGL(bg_step_span_kernel<P>, dim3(grid), dim3(64 * waves_per_block), 0, st, a);
+    return launch_status(-2, "bg_step_span");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -442,6 +627,64 @@ int bg_step(void* stream, float* u, const float* actions, const float* F, int n_
         case 16: return launch<16>(a, (hipStream_t)stream);
         default: return fail(-4, "bg_step: N = %d: supported sizes are 64, 128, 256, 512, 1024", N);
     }
+}
+
+int bg_step_span(void* stream, float* u, const float* actions, const float* F, int n_act, int n_envs, int N, int T, float dx,
+                 float dt, float nu, long n_substeps, float* traj, double* ssq, int* status) {
+    // everything is refused here, before any HIP call
+    if (!u || !actions || !F || !traj) return fail(-1, "bg_step_span: NULL u, actions, F or traj");
+    if (T < 1) return fail(-1, "bg_step_span: %d steps (at least 1)", T);
+    if (n_envs < 1) return fail(-1, "bg_step_span: %d envs (at least 1)", n_envs);
+    if (n_act < 1 || n_act > 16) return fail(-1, "bg_step_span: %d actuators (1 ... 16 are supported)", n_act);
+    if (n_substeps < 0) return fail(-1, "bg_step_span: n_substeps = %ld is negative", n_substeps);
+    if (!(dx > 0.0f) || !(dt > 0.0f) || !(nu >= 0.0f)) return fail(-1, "bg_step_span: dx, dt must be positive, nu non-negative");
+    if (N <= 0 || N % 64) return fail(-4, "bg_step_span: N = %d is not a positive multiple of 64", N);
+    SpanArgs a{};
+    a.s.u = u; a.s.actions = actions; a.s.F = F;
+    a.s.n_act = n_act; a.s.n_envs = n_envs; a.s.N = N; a.s.n_substeps = n_substeps;
+    a.traj = traj; a.ssq = ssq; a.status = status; a.T = T;
+    set_coefficients(a.s, dx, dt, nu);
+    switch (N / 64) {
+        case 1: return launch_span<1>(a, (hipStream_t)stream);
+        case 2: return launch_span<2>(a, (hipStream_t)stream);
+        case 4: return launch_span<4>(a, (hipStream_t)stream);
+        case 8: return launch_span<8>(a, (hipStream_t)stream);
+        case 16: return launch_span<16>(a, (hipStream_t)stream);
+        default: return fail(-4, "bg_step_span: N = %d: supported sizes are 64, 128, 256, 512, 1024", N);
+    }
+}
+
+int bg_record(void* stream, const float* d_traj, const float* d_actions, int n_envs, int N, int A, const double* d_ssq,
+              const int* d_steps, int T, long n_substeps, const long* d_dst, const long* dst_host, const bg_slabs* out) {
+    // everything is refused here, before any HIP call
+    if (!d_traj || !d_actions || !d_ssq || !d_steps || !d_dst || !dst_host || !out)
+        return fail(-1, "bg_record: NULL traj, actions, ssq, steps, dst, dst_host or out");
+    if (!out->obs || !out->actions || !out->nxtobs || !out->rewards || !out->terminated || !out->truncated || !out->steps)
+        return fail(-1, "bg_record: the slabs have a NULL field pointer");
+    if (T < 1) return fail(-1, "bg_record: %d steps (at least 1)", T);
+    if (n_envs < 1) return fail(-1, "bg_record: %d envs (at least 1)", n_envs);
+    if (N < 1) return fail(-1, "bg_record: rows of %d columns (at least 1)", N);
+    if (A < 1 || A > 16) return fail(-1, "bg_record: action width %d (1 ... 16 are supported)", A);
+    if (n_substeps < 0) return fail(-1, "bg_record: n_substeps = %ld is negative", n_substeps);
+    if (out->rows < 1) return fail(-1, "bg_record: slabs of %ld rows (at least 1)", out->rows);
+    const long n = (long)T * n_envs;
+    std::vector<bool> seen(static_cast<size_t>(out->rows), false);
+    for (long i = 0; i < n; ++i) {
+        const long r = dst_host[i];
+        if (r < 0) continue;
+        if (r >= out->rows) return fail(-1, "bg_record: dst[%ld] = %ld is beyond the slabs' %ld rows", i, r, out->rows);
+        if (seen[r]) return fail(-1, "bg_record: row %ld is named twice (again at dst[%ld])", r, i);
+        seen[r] = true;
+    }
+    RecordArgs a{};
+    a.traj = d_traj; a.actions = d_actions; a.ssq = d_ssq; a.steps = d_steps; a.dst = d_dst;
+    a.out = *out;
+    a.n = n; a.E = n_envs; a.N = N; a.A = A;
+    a.vec_obs = N % 4 == 0 && aligned16(d_traj) && aligned16(out->obs) && aligned16(out->nxtobs);
+    a.vec_act = A % 4 == 0 && aligned16(d_actions) && aligned16(out->actions);
+    a.c = -(1.0 / (double)N) / (double)(n_substeps > 1 ? n_substeps : 1);
+    hipLaunchKernelGGL(bg_record_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(NT), 0, (hipStream_t)stream, a);
+    return launch_status(-2, "bg_record");
 }
 
 int bg_residual(void* stream, const float* u, const float* phi, int n_rows, int N, float dx, float nu, float* out) {

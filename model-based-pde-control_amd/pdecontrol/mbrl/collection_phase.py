@@ -47,6 +47,14 @@ same stream: the rewards are formed on the device, only what the write-back need
 observation row, the last action row, the policy's observation, the bounds and the status), and no host replay is built.
 A truncation step's ``Sample`` is packed, uploaded and placed like a host replay's rows.  On the loop tier the loop's host
 replay is staged through ``_stage_host``.
+
+A stack over a ``BurgersBatchedVecEnv`` (pdegym/burgers/burgers.py) runs on the same tiers through the env's
+``BurgersStepper``: the SAC tier's step is ``... -> co_act -> bg_step -> co_observe``, a scripted segment is
+    co_act_span -> bg_step_span -> co_observe_span
+(include/burgers_hip.h: all ``T`` steps in one launch, the state held in registers between them; 4 launches with an
+updating scaling, 2 without), a sink's segment is placed by one ``bg_record`` launch, and the host rewards are the env's
+``ssq * reward_scale()``.  Truncation steps are host steps of the stack, so the env's per-env ``RandomState`` autoreset
+exists once.
 """
 import gc
 from collections import deque
@@ -76,14 +84,15 @@ SEGMENT_BYTES = 256 << 20
 # ----------------------------------------------------------------------------------------------------------------------
 @dataclass
 class RealStackGeometry:
-    """What a recognised real-env stack does between the agent and the KS stepper.
+    """What a recognised real-env stack does between the agent and the stepper.
 
-    ``env``         the ``KSBatchedVecEnv`` at the bottom
+    ``env``         the ``KSBatchedVecEnv`` or ``BurgersBatchedVecEnv`` at the bottom
     ``action``      the scaling of the agent's action columns (identity sensor; ``coef`` None: identity)
     ``record_raw``  the action store sits on top of the scaling: it holds the raw action, else the env-side one
     ``scaling``     the observation ``ScaleTransform`` (scalar bounds) or None
     ``update``      1 when a step joins the block's extrema with the scaling's running bounds first
     ``agent_obs``   the agent sensor over the state columns
+    ``kind``        "ks" or "burgers": which of the two steppers ``env`` drives
     """
     env: Any
     action: FieldMap
@@ -91,6 +100,7 @@ class RealStackGeometry:
     scaling: Optional[tr.ScaleTransform]
     update: int
     agent_obs: FieldMap
+    kind: str = "ks"
 
 
 def _bare_scale(t):
@@ -105,8 +115,9 @@ def recognize_real_stack(stack):
     ``stack.astore`` under or on top of them; ``TransformObsWrapper``s and the pass-through ``BaseWorldVecEnvWrapper`` in
     any order, holding sensors and at most one ``ScaleTransform`` with scalar bounds (``aggregate`` and ``batched``), which,
     where it updates, sits directly above the observation store; the one-step ``StoreNObsVecWrapper`` that is
-    ``stack.ostore``; a ``KSBatchedVecEnv``."""
+    ``stack.ostore``; a ``KSBatchedVecEnv`` or a ``BurgersBatchedVecEnv``."""
     from pdecontrol.mbrl.world.wrappers import BaseWorldVecEnvWrapper
+    from pdegym.burgers.burgers import BurgersBatchedVecEnv
     from pdegym.kuramoto.batched import KSBatchedVecEnv
     env = stack.envs
     above, below, astore = [], [], None
@@ -133,7 +144,7 @@ def recognize_real_stack(stack):
             chains.append((flatten(env.transform), bool(env.frozen), _bare_scale(env.transform)))
         env = env.env
     ks = observation_store(env, stack)
-    if type(ks) is not KSBatchedVecEnv:
+    if type(ks) not in (KSBatchedVecEnv, BurgersBatchedVecEnv):
         raise Unrecognized(f"a {type(ks).__name__} in place of the KSBatchedVecEnv")
     N, A = one_channel_each(ks, "an env")
 
@@ -167,7 +178,8 @@ def recognize_real_stack(stack):
                     raise Unrecognized("a sensor under the running scaling")
                 update = 1
     agent_obs = field_map(tr.Operation([tr.SensorTransform(r) for r in strides]), N)
-    return RealStackGeometry(ks, action, record_raw, scaling, update, agent_obs)
+    return RealStackGeometry(ks, action, record_raw, scaling, update, agent_obs,
+                             "burgers" if type(ks) is BurgersBatchedVecEnv else "ks")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -580,6 +592,18 @@ def _host_step(worker, agent, deterministic):
     return Sample(obs, actions, nxtobs, rewards, terminated, truncated, infos["step"])
 
 
+def _bind(geo, current):
+    """The stepper on torch's current stream ``current`` (returned), as ``KSBatchedVecEnv.step_torch`` binds it, with the
+    env's step objective.  A Burgers stepper has neither setting: it launches on the current stream by itself."""
+    env = geo.env
+    if geo.kind == "ks":
+        if getattr(env, "_stream_handle", None) != current.cuda_stream:
+            env.stepper.set_stream(current.cuda_stream)
+            env._stream_handle = current.cuda_stream
+        env._set_objective(env.proto.step_objective)
+    return current
+
+
 def _run_segment(worker, agent, fused, geo, buf, T, steps, phase=None):
     """``T`` steps without a truncation in HBM, from the state the worker and the stack hold, written back to them.
     Returns the segment's replay piece, or, with a ``_SinkPhase``, records the transitions in the sink and returns None."""
@@ -604,11 +628,7 @@ def _run_segment(worker, agent, fused, geo, buf, T, steps, phase=None):
     obs_args = co.observe_args(traj, pobs, None if scaling is None else bounds,
                                0.0 if scaling is None else float(scaling.lower), 0.0 if scaling is None else float(scaling.upper),
                                geo.update, buf.workspace)
-    current = torch.cuda.current_stream(buf.device)
-    if getattr(env, "_stream_handle", None) != current.cuda_stream:     # as ``KSBatchedVecEnv.step_torch`` binds it
-        env.stepper.set_stream(current.cuda_stream)
-        env._stream_handle = current.cuda_stream
-    env._set_objective(env.proto.step_objective)
+    current = _bind(geo, torch.cuda.current_stream(buf.device))
     fused.refresh_current()
     stream, forward = co.stream(), fused.forward_launcher(E, pobs, buf.noise, buf.action)
     d_env_action, substeps = buf.env_action.data_ptr(), env.cfg_steps
@@ -668,18 +688,17 @@ def _run_span(worker, agent, geo, buf, T, steps, deterministic, phase=None):
     if geo.action.coef is not None:
         buf.coef.copy_(geo.action.coef)
         coef = buf.coef
-    current = torch.cuda.current_stream(buf.device)
-    if getattr(env, "_stream_handle", None) != current.cuda_stream:     # as ``KSBatchedVecEnv.step_torch`` binds it
-        env.stepper.set_stream(current.cuda_stream)
-        env._stream_handle = current.cuda_stream
-    env._set_objective(env.proto.step_objective)
+    current = _bind(geo, torch.cuda.current_stream(buf.device))
     stream = co.stream()
     co.act_span(stream, geometry, co.act_span_args(table, coef, env_actions, actions, geo.record_raw))
     substeps, row, slot = env.cfg_steps, E * N * 4, traj.data_ptr()
     d_env_actions, d_ssq, d_status = env_actions.data_ptr(), ssq.data_ptr(), status.data_ptr()
-    for t in range(T):                                    # eager launches, no host synchronisation
-        env.stepper.step_device(d_actions=d_env_actions + t * E * A * 4, n_substeps=substeps, d_obs=slot + (t + 1) * row,
-                                d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)
+    if geo.kind == "burgers":                             # the whole segment in one launch, the state held in registers
+        env.stepper.step_span(d_env_actions, T, substeps, slot, d_ssq, d_status)
+    else:
+        for t in range(T):                                # eager launches, no host synchronisation
+            env.stepper.step_device(d_actions=d_env_actions + t * E * A * 4, n_substeps=substeps, d_obs=slot + (t + 1) * row,
+                                    d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)
     co.observe_span(stream, geometry, co.observe_args(
         traj, pobs, None if scaling is None else bounds, 0.0 if scaling is None else float(scaling.lower),
         0.0 if scaling is None else float(scaling.upper), geo.update, workspace))
@@ -710,7 +729,10 @@ def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, 
     env = geo.env
     _restore(worker, geo, T, traj[T], actions[T - 1], policy_obs, bounds, status, cell)
     traj, actions = traj.copy(), actions.copy()
-    rewards = (-1.0) * (1 / env.N) * ssq / env.cfg_steps  # ``KSBatchedVecEnv._finish_step``, every step at once
+    if geo.kind == "burgers":
+        rewards = ssq * env.reward_scale()                # ``BurgersBatchedVecEnv.step_torch``, every step at once
+    else:
+        rewards = (-1.0) * (1 / env.N) * ssq / env.cfg_steps  # ``KSBatchedVecEnv._finish_step``, every step at once
     return traj, actions, rewards, steps
 
 

@@ -8,8 +8,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "lib", "libburgers_hip.so"))
 
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+
+
+class Slabs(ctypes.Structure):
+    """``bg_slabs`` of include/burgers_hip.h: the seven slab pointers of a device-resident replay and their row count,
+    field for field ``kspde.ks_record``."""
+    _fields_ = [("obs", _p), ("actions", _p), ("nxtobs", _p), ("rewards", _p), ("terminated", _p), ("truncated", _p),
+                ("steps", _p), ("rows", ctypes.c_long)]
+
+
 SYMBOLS = (
     ("bg_step", _i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, ctypes.c_long, _p, _p, _p]),
+    ("bg_step_span", _i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, ctypes.c_long, _p, _p, _p]),
+    ("bg_record", _i, [_p, _p, _p, _i, _i, _i, _p, _p, _i, ctypes.c_long, _p, _p, ctypes.POINTER(Slabs)]),
     ("bg_residual", _i, [_p, _p, _p, _i, _i, _f, _f, _p]),
     ("bg_phyloss_forward", _i, [_p, _p, _i, _i, _i, _f, _f, _f, _i, _p, _p, _p, ctypes.c_long]),
     ("bg_phyloss_backward", _i, [_p, _p, _p, _p, _p, ctypes.c_long, _i, _i, _i, _f, _f, _f, _i, _p]),

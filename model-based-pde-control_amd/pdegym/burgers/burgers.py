@@ -28,6 +28,54 @@ def _stream(dev):
     return _hip.ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else 0))
 
 
+class BurgersStepper:
+    """The stepper face of a ``BurgersBatchedVecEnv`` as the collection phase talks to it (what it uses of
+    ``kspde.KSStepper``): raw device pointers (ints, 0 = NULL), every launch asynchronous on torch's current stream of the
+    env's device, on the env's live state ``env.u`` and forcing matrix."""
+
+    def __init__(self, env):
+        self._env, self._lib = env, env._lib
+        self.device, self.num_envs, self.N, self.n_act = env.device.index, env.num_envs, env.N, len(env.Xi)
+
+    def _step_args(self):
+        env = self._env
+        return _stream(env.device), _ptr(env.u), _ptr(env._F)
+
+    def step_device(self, d_actions=0, n_substeps=50, d_obs=0, d_ssq=0, d_status=0):
+        """One ``bg_step`` launch: ``d_actions`` [E, A] (0: no forcing), ``d_obs`` [E, N], ``d_ssq`` fp64 [E], ``d_status`` [E]."""
+        env, vp = self._env, _void_p
+        stream, u, F = self._step_args()
+        _hip.check(self._lib.bg_step(stream, u, vp(d_actions), F, self.n_act, self.num_envs, self.N, env.dx, env.dt, env.nu,
+                                     int(n_substeps), vp(d_obs), vp(d_ssq), vp(d_status)))
+
+    def step_span(self, d_actions, T, n_substeps, d_traj, d_ssq=0, d_status=0):
+        """``T`` steps in one ``bg_step_span`` launch: ``d_actions`` [T, E, A], ``d_traj`` [T + 1, E, N] (slots 1 ... T are
+        written), ``d_ssq`` fp64 [T, E], ``d_status`` [T, E]."""
+        env, vp = self._env, _void_p
+        stream, u, F = self._step_args()
+        _hip.check(self._lib.bg_step_span(stream, u, vp(d_actions), F, self.n_act, self.num_envs, self.N, int(T), env.dx,
+                                          env.dt, env.nu, int(n_substeps), vp(d_traj), vp(d_ssq), vp(d_status)))
+
+    def record_device(self, d_traj, d_actions, A, d_ssq, d_steps, T, n_substeps, d_dst, dst_host, slabs):
+        """The ``T * num_envs`` transitions of ``T`` steps without a truncation into replay rows; see ``bg_record``.
+        ``dst_host`` a C-contiguous int64 array [T, num_envs]; ``slabs`` a ``_hip.Slabs`` or a ``kspde.ks_record`` (the
+        same eight fields)."""
+        vp = _void_p
+        if dst_host is not None:
+            assert dst_host.dtype == np.int64 and dst_host.flags["C_CONTIGUOUS"] and dst_host.size == int(T) * self.num_envs, \
+                (dst_host.dtype, dst_host.shape, T, self.num_envs)
+        if slabs is not None and not isinstance(slabs, _hip.Slabs):
+            slabs = _hip.Slabs.from_buffer_copy(slabs)
+        _hip.check(self._lib.bg_record(_stream(self._env.device), vp(d_traj), vp(d_actions), self.num_envs, self.N, int(A),
+                                       vp(d_ssq), vp(d_steps), int(T), int(n_substeps), vp(d_dst),
+                                       None if dst_host is None else dst_host.ctypes.data_as(_hip.ctypes.c_void_p),
+                                       None if slabs is None else _hip.ctypes.byref(slabs)))
+
+
+def _void_p(x):
+    return _hip.ctypes.c_void_p(int(x)) if x else None
+
+
 class BurgersBatchedVecEnv(gym.vector.VectorEnv):
     Xi = [0, 0.25, 0.5, 0.75]
 
@@ -52,6 +100,7 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
         self.timestep = np.zeros(num_envs, dtype=np.int64)
         self._rngs = [np.random.RandomState() for _ in range(num_envs)]
         self._actions = None
+        self.stepper = BurgersStepper(self)
 
     @property
     def scenario(self):
@@ -90,7 +139,17 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
         a = None if actions is None else actions.reshape(self.num_envs, -1).contiguous()
         _hip.check(self._lib.bg_step(_stream(self.device), _ptr(self.u), _ptr(a), _ptr(self._F), len(self.Xi), self.num_envs,
                                      self.N, self.dx, self.dt, self.nu, n, None, _ptr(self._ssq), _ptr(self._status)))
-        return self.u, self._ssq * (-(1.0 / self.N) / max(n, 1))
+        return self.u, self._ssq * self.reward_scale(n)
+
+    def reward_scale(self, n_substeps: Optional[int] = None):
+        """The fp64 factor ``c`` of a step's reward ``ssq * c``: minus the mean square, averaged over the sub-steps."""
+        n = self.cfg_steps if n_substeps is None else int(n_substeps)
+        return -(1.0 / self.N) / max(n, 1)
+
+    def _raise_on(self, status):
+        """``status`` [E] of one step: the ``FloatingPointError`` of ``step_wait`` when any env's state is non-finite."""
+        if np.any(status):
+            raise FloatingPointError(f"non-finite Burgers state in envs {np.nonzero(status)[0].tolist()}")
 
     def residual(self, u, phi=None):
         """nu u_xx - u u_x (+ phi) of fp32 rows [M, N] on the device (test hook of the kernel's stencils)."""
@@ -129,8 +188,7 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
         obs = u.cpu().numpy().reshape(self.num_envs, 1, self.N)
         rewards = rewards.cpu().numpy()
         if bool(self._status.any()):
-            bad = np.nonzero(self._status.cpu().numpy())[0].tolist()
-            raise FloatingPointError(f"non-finite Burgers state in envs {bad}")
+            self._raise_on(self._status.cpu().numpy())
         self.timestep += 1
         truncated = self.timestep >= self.max_episode_steps
         infos = {"step": self.timestep.copy()}
