@@ -1,5 +1,5 @@
 // fno.hip -- one launch per FNO model evaluation (forward) and one per evaluation (backward) for gfx950; part of
-// libspectral_hip.so (C ABI: include/spectral_hip.h, fno_*).
+// libspectral_hip.so (C ABI: include/spectral_hip.h, fno_*, and, for fno_forward_select, include/spectral/forward_select.h).
 //
 // The FNO-style surrogate of BASELINE configs[4] (pdecontrol/architectures/fno.py: lift -> 4 x [spectral convolution +
 // pointwise convolution, GELU] -> project) has no counterpart in the reference (parity unpinned); what IS fixed
@@ -28,6 +28,7 @@
 #include <mutex>
 #include <utility>
 
+#include "../../include/spectral/forward_select.h"
 #include "../../include/spectral_hip.h"
 #include "capi_error.h"
 
@@ -394,6 +395,129 @@ __global__ void __launch_bounds__(TPB) fno_forward_kernel(const FwdArgs a) {
         }
     }
     STAMP(20);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// forward of ONE ensemble member per env (fno_forward_select)
+// ------------------------------------------------------------------------------------------------------------------
+// The FNO surrogate carries no hidden state, so an imagined step of an ensemble needs, for env b, the evaluation of the
+// member the elite pick takes and no other.  Every member's weight pointers travel in the kernel arguments; a workgroup
+// reads its member index (wave uniform) and from then on the arguments of that member at a uniform offset: scalar loads,
+// no private copy of a struct, no scratch.
+//
+// The walk below is fno_forward_kernel<false>'s, statement for statement, on the shared device functions, so a row is the
+// byte-for-byte row of fno_forward with that member's weights (tests/test_fno_select_gpu.py).  It has its own spelling
+// and the older kernels keep theirs: called through one inline function of the whole walk, fno_forward_kernel<false> and
+// <true> come out 4 and 1 instructions longer with 6 more SGPRs each, and their code is held to what it was, instruction
+// for instruction (profiles/fno_select_kernel_resources.txt).
+struct SelectArgs {
+    Weights w[FNO_MAX_MEMBERS];
+    float cscale[FNO_MAX_MEMBERS], cshift[FNO_MAX_MEMBERS];
+    const int* chosen;      // [T][nb] or nullptr (member 0)
+    const int* step;        // rollout_hip.h's counter: step[0] is read; nullptr: slot 0
+    const float* u;         // [nb][N]
+    const float* act;       // [nb][N]
+    float* out;             // [nb][N]
+    const float* tabg;      // [32][N] twiddle matrix (global, per device and N)
+    int members, T, n, nb;
+};
+
+__global__ void __launch_bounds__(TPB) fno_forward_select_kernel(const SelectArgs a) {
+    extern __shared__ __align__(16) float lds_raw[];
+    const int N = a.n;
+    const int b = blockIdx.x;
+    const int t = a.step ? __builtin_amdgcn_readfirstlane(a.step[0]) : 0;
+    if (t < 0 || t >= a.T) return;                                   // the whole workgroup leaves: nothing is written
+    const int pick = a.chosen ? __builtin_amdgcn_readfirstlane(a.chosen[(long)t * a.nb + b]) : 0;
+    float* out = a.out + (size_t)b * N;
+    if (pick < 0 || pick >= a.members) {                             // poison, as ro_settle: no weight is read
+        for (int n = threadIdx.x; n < N; n += blockDim.x) out[n] = NAN;
+        return;
+    }
+    const Weights& w = a.w[pick];
+    const float cscale = a.cscale[pick], cshift = a.cshift[pick];
+    const Lds L(lds_raw, N);
+    const int NP = L.NP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int r = lane & 15, q = lane >> 4;
+    const float* u = a.u + (size_t)b * N;
+    const float* act = a.act + (size_t)b * N;
+
+    lift_into(L.xs, u, act, w, N, NP);
+    load_table(L.tb, a.tabg, N, NP);
+    __syncthreads();
+
+    const float s0 = 1.0f / (float)N, s1 = 2.0f / (float)N;
+    for (int l = 0; l < LAYERS; ++l) {
+        // ---- A: truncated DFT of the layer input; the pointwise weights ride along -----------------------------
+        MixRegs mw;
+        mix_load<false>(w.wr[l], w.wi[l], mw);
+        contract_n(L.xs, L.tb, L.S, N, NP);
+        load_mat(L.wps, w.pw[l]);
+        if (threadIdx.x < C) L.misc[threadIdx.x] = w.pb[l][threadIdx.x];
+        __syncthreads();
+        // ---- B: complex mode mixing ----------------------------------------------------------------------------
+        mix_compute<false>(mw, L.S, L.Z, s0, s1);
+        __syncthreads();
+        // ---- C: pre = iDFT(Z) + Wp x + b, position tile by position tile, in place ------------------------------
+        for (int ct = wave; ct < (N >> 4); ct += nwaves) {
+            const int pos = 16 * ct + r;
+            f32x4 acc[2][2];
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                acc[rt][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                acc[rt][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                const float* zrow = L.Z + (16 * rt + r) * KP;
+                const float* wrow = L.wps + (16 * rt + r) * KP;
+#pragma unroll
+                for (int k0 = 0; k0 < K2; k0 += 4) {
+                    acc[rt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(zrow[k0 + q], L.tb[(k0 + q) * NP + pos], acc[rt][0], 0, 0, 0);
+                    acc[rt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[k0 + q], L.xs[(k0 + q) * NP + pos], acc[rt][1], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int row = 16 * rt + 4 * q + j;
+                    const float v = (acc[rt][0][j] + acc[rt][1][j]) + L.misc[row];
+                    L.xs[row * NP + pos] = l + 1 < LAYERS ? gelu(v) : v;
+                }
+        }
+        __syncthreads();
+    }
+
+    // ---- project: delta = p2 . gelu(p1 h + b1) + b2;  out = u + cscale * delta + cshift ---------------------------
+    load_mat(L.wps, w.p1_w);
+    if (threadIdx.x < C) {
+        L.misc[threadIdx.x] = w.p1_b[threadIdx.x];
+        L.misc[C + threadIdx.x] = w.p2_w[threadIdx.x];
+    }
+    __syncthreads();
+    const float b2 = w.p2_b[0];
+    for (int ct = wave; ct < (N >> 4); ct += nwaves) {
+        const int pos = 16 * ct + r;
+        float part = 0.0f;
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            const float* wrow = L.wps + (16 * rt + r) * KP;
+#pragma unroll
+            for (int k0 = 0; k0 < C; k0 += 4)
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[k0 + q], L.xs[(k0 + q) * NP + pos], acc, 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int row = 16 * rt + 4 * q + j;
+                part = fmaf(L.misc[C + row], gelu(acc[j] + L.misc[row]), part);
+            }
+        }
+        part += __shfl_xor(part, 16, 64);
+        part += __shfl_xor(part, 32, 64);
+        if (q == 0) {
+            const float d = part + b2;
+            out[pos] = fmaf(cscale, d, u[pos]) + cshift;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -849,6 +973,39 @@ int fno_forward(void* stream, const fno_weights* w, int width, int modes, int la
     a.cshift = cshift;
     return pre ? launch(fno_forward_kernel<true>, "fno_forward", stream, pairs, n, a)
                : launch(fno_forward_kernel<false>, "fno_forward", stream, pairs, n, a);
+}
+
+int fno_forward_select(void* stream, int width, int modes, int layers, int n, int nb, const fno_select_args* a) {
+    const char* who = "fno_forward_select";
+    if (!a || !a->w || !a->cscale || !a->cshift || !a->u || !a->act || !a->out)
+        return fail(-1, "%s: NULL argument, weights, cscale, cshift, state, action or output pointer", who);
+    if (a->members < 1 || a->members > FNO_MAX_MEMBERS)
+        return fail(-1, "%s: %d ensemble members (1 ... %d are supported)", who, a->members, FNO_MAX_MEMBERS);
+    for (int m = 0; m < a->members; ++m)
+        if (!complete(&a->w[m])) return fail(-1, "%s: member %d has an incomplete set of weights", who, m);
+    if (a->members > 1 && !a->chosen) return fail(-1, "%s: %d members without a chosen-member array", who, a->members);
+    if (a->T < 1) return fail(-1, "%s: %d slots of chosen members (at least 1)", who, a->T);
+    if (a->out == a->u) return fail(-1, "%s: the output must not alias the state", who);
+    if (int rc = check(who, n, nb, nb, width, modes, layers)) return rc;
+    SelectArgs k = {};
+    for (int m = 0; m < a->members; ++m) {
+        k.w[m] = weights_of(&a->w[m]);
+        k.cscale[m] = a->cscale[m];
+        k.cshift[m] = a->cshift[m];
+    }
+    k.chosen = a->chosen;
+    k.step = a->step;
+    k.u = a->u;
+    k.act = a->act;
+    k.out = a->out;
+    k.members = a->members;
+    k.T = a->T;
+    k.n = n;
+    k.nb = nb;
+    int trc = 0;
+    k.tabg = twiddle_table(who, n, (hipStream_t)stream, &trc);
+    if (!k.tabg) return trc;
+    return launch(fno_forward_select_kernel, who, stream, nb, n, k);
 }
 
 int fno_backward(void* stream, const fno_weights* w, int width, int modes, int layers, int n, int nb, int pairs, const float* u,

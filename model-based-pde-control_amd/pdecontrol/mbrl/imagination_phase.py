@@ -16,7 +16,9 @@ kernel tier   the closed loop stays in HBM for a whole round (one reset plus the
               step is ``noise.normal_()`` plus one hipGraph replay of
                   sac_policy_forward -> ro_act_chain -> every member's fused one-step rollout -> ro_settle
               (csrc/rollout.hip; under the KS env's dissipation objective the last launch is ro_settle_dissipation,
-              which recomputes the forcing of the recorded action for the reward's u * phi term); the per-step elite
+              which recomputes the forcing of the recorded action for the reward's u * phi term; an ensemble of FNO
+              members, which carry no hidden state, is stepped as ro_act_chain -> fno_forward_select -> ro_settle over
+              the one buffer of picked rows: one evaluation per env in place of one per member and env); the per-step elite
               draws are made on the host in the loop's order and uploaded once per round; one D2H copy and one
               synchronisation per round bring the trajectory block back, and the replay is built from it with one deque
               per episode and field.
@@ -36,6 +38,7 @@ every episode.  With ``sink=`` (a ``DeviceExperienceReplay``, pdecontrol/mbrl/de
 writes the samples into the sink's slabs instead, one ``rp_append`` launch per round, and returns the ``StagedRollout`` that
 ``sink.extend`` commits: nothing is copied back and nothing is built on the host.
 """
+import os
 import time
 from collections import deque
 from dataclasses import dataclass
@@ -65,7 +68,8 @@ class StackGeometry:
     ``act_out``     sensor and scaling of the forcing columns: the world's action row
     ``agent_obs``   the agent sensor over the world's observation columns
     ``reward``      the rescaling of the world's observation before the reward
-    ``objective``   the KS env's reward, "l2control" or "dissipation" (``KuramotoSivashinskyEnv.step_objective``)
+    ``objective``   the reward owner's objective: the KS env's "l2control" or "dissipation"
+                    (``KuramotoSivashinskyEnv.step_objective``), the Burgers env's "l2control" (its ``scenario``)
     ``dx``          the env's grid spacing L / N (read by the dissipation reward)
     """
     world: object
@@ -84,8 +88,10 @@ def recognize_stack(stack, objectives=("l2control",)):
     one ``GaussianForcing``, at most one scaling and sensors; ``TransformObsWrapper``s holding only sensors over a
     ``StoreNObsVecWrapper``; a ``WorldVecEnv`` whose observation connector is a stride-1 sensor and at most one scaling
     and whose batched reward is a ``KuramotoSivashinskyEnv``'s, under one of ``objectives`` (the kernel tier passes
-    both; the dissipation reward reads the forcing at every grid point, so its forcing must be as wide as the state)."""
+    both; the dissipation reward reads the forcing at every grid point, so its forcing must be as wide as the state), or a
+    ``BurgersBatchedVecEnv``'s (what ``BurgersEnv.batched_reward_func`` forwards to), whose scenario names l2control."""
     from pdecontrol.mbrl.world.world import WorldVecEnv
+    from pdegym.burgers.burgers import BurgersBatchedVecEnv
     from pdegym.kuramoto import KuramotoSivashinskyEnv
     env = stack.envs
     action_store(env, stack, f"a {type(env).__name__} in place of the action store on top of the stack")
@@ -118,9 +124,16 @@ def recognize_stack(stack, objectives=("l2control",)):
     if (reward.start, reward.stride) != (0, 1):
         raise Unrecognized("a world whose observation connector carries a sensor of stride above 1")
     owner = getattr(world.batched_reward_func, "__self__", None)
-    if not isinstance(owner, KuramotoSivashinskyEnv):
+    if isinstance(owner, BurgersBatchedVecEnv):
+        # its batched reward is the l2control expression -(1/N) * |obs|^2 that ro_settle forms; the scenario names it
+        objective = owner.scenario["objective"]
+        if objective != "l2control":
+            raise Unrecognized(f"a BurgersBatchedVecEnv whose scenario names the {objective} objective (its batched reward "
+                               f"is l2control's)")
+    elif not isinstance(owner, KuramotoSivashinskyEnv):
         raise Unrecognized("a world without the batched reward of a KuramotoSivashinskyEnv")
-    objective = owner.step_objective
+    else:
+        objective = owner.step_objective
     if objective not in objectives:
         raise Unrecognized(f"the {objective} objective")
     if owner.N != N:
@@ -160,11 +173,18 @@ def _same_coef(a, b):
     return (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and torch.equal(a, b))
 
 
+def _select_wanted():
+    """``PDECONTROL_FNO_SELECT=0`` keeps the generic member loop for an ensemble of FNO members (every member's one-step
+    rollout, then ``ro_settle`` over all outputs): the A/B partner of the select kernel, and its fallback."""
+    return os.environ.get("PDECONTROL_FNO_SELECT", "1") != "0"
+
+
 class _CapturedStep:
     """Static buffers and the hipGraph of one imagined step for one (world state, agent, stack geometry, horizon)."""
 
     def __init__(self, agent, fused, geo):
         from pdecontrol.mbrl import rollout_hip as ro
+        from pdecontrol.surrogates import fno_hip
         from pdecontrol.surrogates.graph_step import capture_graph
         from pdecontrol.surrogates.hipops import pooled_streams
         world = geo.world
@@ -205,25 +225,42 @@ class _CapturedStep:
         act_args = ro.act_args(self.action, self.actions, self.coefs[0], self.forcing, self.coefs[1], dev.act, self.step)
         self.keep = []
         tstep = world.tstep
+        # An ensemble of FNO members is stateless: env b needs the evaluation of member chosen[t][b] alone, which
+        # fno_forward_select makes in one launch for all envs; ro_settle then sees that buffer as its single member.
+        # The world's action row must span the state row (the FNO reads the action field at every grid point).
+        self.select_wanted = _select_wanted()
+        self.select = (self.select_wanted and geo.act_out.width == N
+                       and all(fno_hip.world_supported(m, N) for m in dev.members))
+        settle_geometry, sel_args = self.geometry, None
+        if self.select:
+            settle_geometry = ro.Geometry(B, T, N, A, L, geo.act_out.start, geo.act_out.stride, geo.agent_obs.start,
+                                          geo.agent_obs.stride, 1)
+            self.picked = f32(B, N)
+            sel_args = fno_hip.select_args(dev.members, self.chosen if len(dev.members) > 1 else None, self.step, T,
+                                           dev.state, dev.act, self.picked)
 
         def step():
             fused.forward_launcher(B, self.policy_obs, self.noise, self.action)()
             stream = ro.stream()
             ro.act_chain(stream, self.geometry, act_args)
-            outs = []
-            for sur, hid in zip(dev.members, dev.hidden):
-                r = sur.rollout(states=dev.state, actions=dev.act, times=0.0, targets=tstep, hidden=hid)
-                outs.append(r.outputs.reshape(B, N).contiguous())
-                for h, new in zip(hid, r.hidden):
-                    h.copy_(new)
+            if self.select:
+                fno_hip.forward_select(stream, N, B, sel_args)
+                outs = [self.picked]
+            else:
+                outs = []
+                for sur, hid in zip(dev.members, dev.hidden):
+                    r = sur.rollout(states=dev.state, actions=dev.act, times=0.0, targets=tstep, hidden=hid)
+                    outs.append(r.outputs.reshape(B, N).contiguous())
+                    for h, new in zip(hid, r.hidden):
+                        h.copy_(new)
             self.keep = outs
             settle_args = ro.settle_args(outs, self.chosen if len(outs) > 1 else None, dev.state, self.traj, self.policy_obs,
                                          self.steps0, self.steps, self.rewards, self.coefs[2], self.step)
             if self.objective == "dissipation":
-                ro.settle_dissipation(stream, self.geometry, settle_args,
+                ro.settle_dissipation(stream, settle_geometry, settle_args,
                                       ro.dissipation_args(self.actions, self.coefs[0], self.forcing, self.dx))
             else:
-                ro.settle(stream, self.geometry, settle_args)
+                ro.settle(stream, settle_geometry, settle_args)
 
         saved = (dev.state.clone(), [tuple(h.clone() for h in hid) for hid in dev.hidden])
         (stream,) = pooled_streams(device, 1, "capture")
@@ -250,7 +287,8 @@ class _CapturedStep:
         into the tensors the graph reads (the controller's observation scaling keeps learning between iterations)."""
         world = geo.world
         if (world._dev is not self.dev or not self.dev.valid() or fused is not self.fused or fused.version != self.version
-                or max(int(world.horizon), 1) != self.T or geo.objective != self.objective or float(geo.dx) != self.dx):
+                or max(int(world.horizon), 1) != self.T or geo.objective != self.objective or float(geo.dx) != self.dx
+                or _select_wanted() != self.select_wanted):
             return False
         now = (geo.act_in, geo.act_out, geo.agent_obs, geo.reward)
         if any((a.start, a.stride, a.width, a.coef is None) != (b.start, b.stride, b.width, b.coef is None)

@@ -296,9 +296,13 @@ class WorldVecEnv(BaseWorldVecEnv):
             dev = _surrogate_device(self.surrogate)
             from pdecontrol.surrogates import hipops
             members = _members(self.surrogate)[0]
-            # one kernel family for the whole ensemble: every member the autoregressive layout, or every member the latent one
+            # one kernel family for the whole ensemble: every member the autoregressive layout, every member the latent one,
+            # or every member an FNO of the whole-network kernels' geometry at the world's state width
+            from pdecontrol.surrogates import fno_hip
+            width = int(self.single_observation_space.shape[-1])
             same_layout = (all(hipops.fused_supported(m) for m in members)
-                           or all(hipops.fused_latent_supported(m) for m in members))
+                           or all(hipops.fused_latent_supported(m) for m in members)
+                           or all(fno_hip.world_supported(m, width) for m in members))
             self.device_resident = bool(dev.type == "cuda" and ops.fused_enabled() and self.batched_reward_func is not None
                                         and same_layout)
         return self.device_resident

@@ -1,5 +1,6 @@
-"""Whole-network FNO kernels behind ``FNOAutoRegSurrogate.rollout`` (C ABI: include/spectral_hip.h ``fno_*``; kernels:
-csrc/fno.hip) -- SURVEY 8(f) row f4, BASELINE configs[4].
+"""Whole-network FNO kernels behind ``FNOAutoRegSurrogate.rollout`` (C ABI: include/spectral_hip.h ``fno_*`` and, for the
+member-select forward of the imagined step, include/spectral/forward_select.h; kernels: csrc/fno.hip) -- SURVEY 8(f) row f4,
+BASELINE configs[4].
 
 The rollout contract is the reference's (pdecontrol/surrogates/surrogate.py:79-133): teacher forced on the given states,
 free running afterwards, ``next = prev + delta * dscaling(model(prev, action))``.  Here a rollout of K steps is
@@ -41,6 +42,20 @@ SYMBOLS = (
     ("fno_spec_wgrad", _i, [_p, _p, _p, _i, _p * 4, _p * 4]),
     ("fno_last_error", ctypes.c_char_p, []),
 )
+MAX_MEMBERS = 8
+
+
+class FnoSelectArgs(ctypes.Structure):
+    """``fno_select_args`` of include/spectral/forward_select.h"""
+    _fields_ = [("w", _WP), ("cscale", ctypes.POINTER(_f)), ("cshift", ctypes.POINTER(_f)), ("members", _i), ("chosen", _p),
+                ("step", _p), ("T", _i), ("u", _p), ("act", _p), ("out", _p)]
+
+
+# include/spectral/forward_select.h, the same library (tests/test_fno_select_host.py holds that header, this table and the
+# library to each other as tests/test_capi_symbols.py does for SYMBOLS)
+SELECT_SYMBOLS = (
+    ("fno_forward_select", _i, [_p, _i, _i, _i, _i, _i, ctypes.POINTER(FnoSelectArgs)]),
+)
 _lib = None
 
 
@@ -51,7 +66,8 @@ class FnoHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.type_symbols(spectral.load(), SYMBOLS)   # same shared library; raises when it has not been built
+        # same shared library; raises when it has not been built
+        _lib = hipbind.type_symbols(spectral.load(), SYMBOLS + SELECT_SYMBOLS)
     return _lib
 
 
@@ -100,6 +116,41 @@ def affine_of(dscaling):
     except hipops.SurrogateHipError:
         return None
     return float(mul), float(add)
+
+
+def world_supported(surrogate, n):
+    """True when ``surrogate`` can be a member of a device-resident world of state width ``n``: an ``FNOAutoRegSurrogate``
+    whose model has the kernels' geometry and whose ``dscaling`` is affine."""
+    from pdecontrol.architectures.fno import FNOAutoRegSurrogate
+    return (isinstance(surrogate, FNOAutoRegSurrogate) and supported(surrogate.model, int(n))
+            and affine_of(surrogate.dscaling) is not None)
+
+
+def select_args(surrogates, chosen, step, T, u, act, out):
+    """``fno_select_args`` for the ensemble ``surrogates`` (each ``world_supported``) from device tensors: ``chosen`` int32
+    [T, B] (None with one member), ``step`` the int32[2] counter of rollout_hip (None: slot 0), ``u`` / ``act`` / ``out``
+    contiguous fp32 [B, N].  The weights' addresses and the per-member ``delta * dscaling`` constants are read NOW and travel
+    by value: the result is good for as long as the members keep their parameters' storage and their ``dscaling``.  The
+    returned struct keeps its host arrays alive."""
+    assert 1 <= len(surrogates) <= MAX_MEMBERS
+    M = len(surrogates)
+    ws, keep, cscale, cshift = (FnoWeights * M)(), [], (_f * M)(), (_f * M)()
+    for m, sur in enumerate(surrogates):
+        w, ps = _weights_struct(parameters_of(sur.model))
+        ws[m] = w
+        keep.append(ps)
+        scale, shift = affine_of(sur.dscaling)
+        cscale[m], cshift[m] = float(sur.delta) * scale, float(sur.delta) * shift
+    a = FnoSelectArgs(ws, cscale, cshift, M, *(None if t is None else t.data_ptr() for t in (chosen, step)), int(T),
+                      u.data_ptr(), act.data_ptr(), out.data_ptr())
+    a._keep = (ws, cscale, cshift, keep)
+    return a
+
+
+def forward_select(stream, n, nb, args):
+    """One ``fno_forward_select`` launch on ``stream`` (a raw hipStream_t): row b of ``args.out`` becomes the one-step
+    prediction of member ``chosen[step[0]][b]``."""
+    _check(load().fno_forward_select(stream, WIDTH, MODES, LAYERS, int(n), int(nb), ctypes.byref(args)))
 
 
 def _launch_groups(n_given, K):

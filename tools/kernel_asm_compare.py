@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Whether a change left a translation unit's existing kernels instruction for instruction what they were: compiles one
+source of csrc/ for gfx950 from two trees (hipcc -S --cuda-device-only, the library's flags) and compares every kernel's
+assembly with comments and the function-local label numbers dropped.  Prints one line per kernel: the instruction lines of
+both builds, IDENTICAL / DIFFERENT / NEW / GONE and a hash of the new body.
+
+usage: tools/kernel_asm_compare.py fno.hip --parent /path/to/the/parent/checkout [-- extra hipcc flags]
+       (e.g. `git worktree add /tmp/parent HEAD~1` gives such a checkout)
+"""
+import argparse
+import hashlib
+import os
+import re
+import subprocess
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join("model-based-pde-control_amd", "csrc")
+
+
+def bodies(root, source, flags):
+    with tempfile.TemporaryDirectory() as tmp:
+        asm = os.path.join(tmp, "k.s")
+        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm,
+                        os.path.join(root, CSRC, source)] + flags, check=True, capture_output=True)
+        text = open(asm).read()
+    out = {}
+    for m in re.finditer(r"^(_Z\S+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
+        body = re.sub(r"\.LBB\d+_", ".LBB_", m.group(2))
+        lines = [line.split(";")[0].rstrip() for line in body.splitlines()]
+        out[m.group(1)] = [line for line in lines if line.strip()]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("source")
+    ap.add_argument("--parent", required=True)
+    ap.add_argument("flags", nargs="*")
+    args = ap.parse_args()
+    old, new = bodies(args.parent, args.source, args.flags), bodies(ROOT, args.source, args.flags)
+    names = subprocess.run(["c++filt"] + sorted(set(old) | set(new)), capture_output=True, text=True).stdout.splitlines()
+    print("%-70s %8s %8s  %-9s %s" % ("kernel of " + args.source, "parent", "new", "", "sha256[:16] of the new body"))
+    for raw, name in zip(sorted(set(old) | set(new)), names):
+        name = re.sub(r"\(anonymous namespace\)::", "", name)
+        name = re.sub(r"\(.*$", "", name)
+        a, b = old.get(raw), new.get(raw)
+        verdict = "NEW" if a is None else "GONE" if b is None else "IDENTICAL" if a == b else "DIFFERENT"
+        digest = "" if b is None else hashlib.sha256("\n".join(b).encode()).hexdigest()[:16]
+        print("%-70s %8s %8s  %-9s %s" % (name[:70], "-" if a is None else len(a), "-" if b is None else len(b), verdict, digest))
+
+
+if __name__ == "__main__":
+    main()
