@@ -21,6 +21,8 @@
 #ifndef BURGERS_HIP_H
 #define BURGERS_HIP_H
 
+#include "replay/slabs.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -44,7 +46,7 @@ int bg_step_span(void* stream, float* u, const float* actions, const float* F, i
 
 /* The T * E transitions of T consecutive steps without a truncation, read where bg_step / bg_step_span left them and
  * written as rows of a device-resident replay: the counterpart of ks_record_device (include/kspde.h) without a handle.
- * bg_slabs is a HOST struct of DEVICE pointers with the layout of ks_record: obs / nxtobs fp32 [rows,N], actions fp32
+ * bg_slabs is a HOST struct of DEVICE pointers, the one struct ks_record is: obs / nxtobs fp32 [rows,N], actions fp32
  * [rows,A], rewards fp32 [rows], terminated / truncated bytes [rows], steps int [rows].  Transition (t, e) writes row
  * d_dst[t][e] (a negative entry writes nothing): obs = traj[t][e], nxtobs = traj[t+1][e], the action and steps of (t, e),
  * terminated = truncated = 0 and rewards = (float)(ssq[t][e] * c), c = -(1.0 / (double)N) / (double)max(n_substeps, 1):
@@ -52,10 +54,7 @@ int bg_step_span(void* stream, float* u, const float* actions, const float* F, i
  * (NULL pointers, T < 1, n_envs < 1, N < 1, A outside 1 ... 16, n_substeps < 0, slabs without rows, an entry >= rows, a row
  * named twice) is made from it before any HIP call, with a message that starts with "bg_record:".  One launch; it does not
  * synchronise and does not allocate device memory. */
-typedef struct bg_slabs {
-    float* obs; float* actions; float* nxtobs; float* rewards;
-    unsigned char* terminated; unsigned char* truncated; int* steps; long rows;
-} bg_slabs;
+typedef replay_slabs bg_slabs;                  /* replay/slabs.h */
 
 int bg_record(void* stream, const float* d_traj /* [T+1][E][N] */, const float* d_actions /* [T][E][A] */, int n_envs, int N,
               int A, const double* d_ssq /* [T][E] */, const int* d_steps /* [T][E] */, int T, long n_substeps,

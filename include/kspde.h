@@ -28,6 +28,8 @@
 #ifndef KSPDE_H
 #define KSPDE_H
 
+#include "replay/slabs.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -180,10 +182,7 @@ int ks_reward_rows_device(ks_handle* h, int objective, const float* d_obs, const
  * pointers, T < 1, A outside 1 ... 16, n_substeps < 1, slabs without rows, an entry >= rows, a row named twice) is made
  * from it before any HIP call.  Enqueued on the handle's stream; it does not synchronise and does not allocate device
  * memory.  On the CPU twin host pointers, synchronous. */
-typedef struct ks_record {
-    float* obs; float* actions; float* nxtobs; float* rewards;
-    unsigned char* terminated; unsigned char* truncated; int* steps; long rows;
-} ks_record;
+typedef replay_slabs ks_record;                 /* replay/slabs.h */
 
 int ks_record_device(ks_handle* h, const float* d_traj /* [T+1][E][N] */, const float* d_actions /* [T][E][A] */, int A,
                      const double* d_ssq /* [T][E] */, const int* d_steps /* [T][E] */, int T, long n_substeps,

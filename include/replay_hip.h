@@ -28,6 +28,8 @@
 #ifndef REPLAY_HIP_H
 #define REPLAY_HIP_H
 
+#include "replay/slabs.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -60,18 +62,8 @@ int rp_supported(int nsrc, const rp_source* srcs, int B);
 int rp_gather(void* stream, int nsrc, const rp_source* srcs, int B, const long* rows, float* obs, float* actions,
               float* nxtobs, float* rewards, float* terminated);
 
-/* The slabs of a DeviceExperienceReplay: one tensor per field in DeviceSubSeqStore.tensors dtypes, `rows` rows each.
- * A HOST struct of DEVICE pointers, read during the call. */
-typedef struct rp_slab {
-    float* obs;                      /* [rows][N] */
-    float* actions;                  /* [rows][A] */
-    float* nxtobs;                   /* [rows][N] */
-    float* rewards;                  /* [rows] */
-    unsigned char* terminated;       /* [rows] */
-    unsigned char* truncated;        /* [rows] */
-    int* steps;                      /* [rows] */
-    long rows;
-} rp_slab;
+/* The slabs of a DeviceExperienceReplay (replay/slabs.h): a HOST struct of DEVICE pointers, read during the call. */
+typedef replay_slabs rp_slab;
 
 /* Places one rollout round into the slabs in ONE launch.  `block` is the round block of the imagined-rollout phase as it
  * lies in HBM, laid out for T_cap steps: traj [T_cap + 1][B][N] | actions [T_cap][B][A] | rewards [T_cap][B] | steps

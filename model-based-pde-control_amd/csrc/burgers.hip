@@ -19,10 +19,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
-#include <vector>
 
 #include "../../include/burgers_hip.h"
 #include "capi_error.h"
+#include "place_rows.h"
 #include "row_ops.h"
 
 namespace {
@@ -374,14 +374,6 @@ struct RecordArgs {
     double c;                  // -(1.0 / N) / max(n_substeps, 1)
 };
 
-__device__ __forceinline__ void place_row(const float* __restrict__ in, float* __restrict__ out, int n, bool vec, int lane) {
-    if (vec) {
-        for (int j = 4 * lane; j < n; j += 4 * WAVE) *reinterpret_cast<f4*>(out + j) = *reinterpret_cast<const f4*>(in + j);
-    } else {
-        for (int j = lane; j < n; j += WAVE) out[j] = in[j];
-    }
-}
-
 __global__ void __launch_bounds__(NT) bg_record_kernel(const RecordArgs a) {
     const int lane = threadIdx.x & (WAVE - 1);
     const long w = (long)blockIdx.x * WAVES + (threadIdx.x >> 6);
@@ -659,8 +651,8 @@ int bg_record(void* stream, const float* d_traj, const float* d_actions, int n_e
     // everything is refused here, before any HIP call
     if (!d_traj || !d_actions || !d_ssq || !d_steps || !d_dst || !dst_host || !out)
         return fail(-1, "bg_record: NULL traj, actions, ssq, steps, dst, dst_host or out");
-    if (!out->obs || !out->actions || !out->nxtobs || !out->rewards || !out->terminated || !out->truncated || !out->steps)
-        return fail(-1, "bg_record: the slabs have a NULL field pointer");
+    const PlaceRefusals refusals = {"bg_record", true, -1, -1, -1};
+    if (const int rc = check_slab_fields(refusals, out)) return rc;
     if (T < 1) return fail(-1, "bg_record: %d steps (at least 1)", T);
     if (n_envs < 1) return fail(-1, "bg_record: %d envs (at least 1)", n_envs);
     if (N < 1) return fail(-1, "bg_record: rows of %d columns (at least 1)", N);
@@ -668,14 +660,7 @@ int bg_record(void* stream, const float* d_traj, const float* d_actions, int n_e
     if (n_substeps < 0) return fail(-1, "bg_record: n_substeps = %ld is negative", n_substeps);
     if (out->rows < 1) return fail(-1, "bg_record: slabs of %ld rows (at least 1)", out->rows);
     const long n = (long)T * n_envs;
-    std::vector<bool> seen(static_cast<size_t>(out->rows), false);
-    for (long i = 0; i < n; ++i) {
-        const long r = dst_host[i];
-        if (r < 0) continue;
-        if (r >= out->rows) return fail(-1, "bg_record: dst[%ld] = %ld is beyond the slabs' %ld rows", i, r, out->rows);
-        if (seen[r]) return fail(-1, "bg_record: row %ld is named twice (again at dst[%ld])", r, i);
-        seen[r] = true;
-    }
+    if (const int rc = check_dst_rows(refusals, dst_host, n, out->rows)) return rc;
     RecordArgs a{};
     a.traj = d_traj; a.actions = d_actions; a.ssq = d_ssq; a.steps = d_steps; a.dst = d_dst;
     a.out = *out;

@@ -10,13 +10,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <vector>
 
 #include "../../include/kspde.h"
 #include "capi_error.h"
 #include "ks_cpu.h"
 #include "ks_eval.h"
 #include "ks_internal.h"
+#include "place_rows.h"
 
 namespace {
 
@@ -645,23 +645,15 @@ int ks_record_device(ks_handle* h, const float* d_traj, const float* d_actions, 
     if (!h) return fail(KS_ERR_INVALID, "ks_record_device: NULL handle");
     if (!d_traj || !d_actions || !d_ssq || !d_steps || !d_dst || !dst_host || !out)
         return fail(KS_ERR_INVALID, "ks_record_device: NULL traj, actions, ssq, steps, dst, dst_host or out");
-    if (!out->obs || !out->actions || !out->nxtobs || !out->rewards || !out->terminated || !out->truncated || !out->steps)
-        return fail(KS_ERR_INVALID, "ks_record_device: the slabs have a NULL field pointer");
+    const PlaceRefusals refusals = {"ks_record_device", true, KS_ERR_INVALID, KS_ERR_INVALID, KS_ERR_INVALID};
+    if (const int rc = check_slab_fields(refusals, out)) return rc;
     if (T < 1) return fail(KS_ERR_INVALID, "ks_record_device: %d steps (at least 1)", T);
     if (A < 1 || A > 16) return fail(KS_ERR_INVALID, "ks_record_device: action width %d (1 ... 16 are supported)", A);
     if (n_substeps < 1) return fail(KS_ERR_INVALID, "ks_record_device: n_substeps %ld (at least 1)", n_substeps);
     if (out->rows < 1) return fail(KS_ERR_INVALID, "ks_record_device: slabs of %ld rows (at least 1)", out->rows);
     if (h->pending) return fail(KS_ERR_INVALID, "ks_record_device: a step is in flight (ks_step_begin without ks_step_end)");
     const long n = (long)T * h->E;
-    std::vector<bool> seen(static_cast<size_t>(out->rows), false);
-    for (long i = 0; i < n; ++i) {
-        const long r = dst_host[i];
-        if (r < 0) continue;
-        if (r >= out->rows)
-            return fail(KS_ERR_INVALID, "ks_record_device: dst[%ld] = %ld is beyond the slabs' %ld rows", i, r, out->rows);
-        if (seen[r]) return fail(KS_ERR_INVALID, "ks_record_device: row %ld is named twice (again at dst[%ld])", r, i);
-        seen[r] = true;
-    }
+    if (const int rc = check_dst_rows(refusals, dst_host, n, out->rows)) return rc;
     const double scale = -1.0 * (1.0 / (double)h->N);
     if (h->cpu) {
         kscpu::record(h->E, h->N, A, n, d_traj, d_actions, d_ssq, d_steps, d_dst, scale, (double)n_substeps, out->obs,

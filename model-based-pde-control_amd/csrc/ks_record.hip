@@ -2,7 +2,7 @@
 // own outputs into the slabs of the device-resident replay.  The device form of KSBatchedVecEnv._finish_step plus
 // Sample.split for T steps without a truncation.
 //
-// A wave owns a transition (t, e), lanes run along the columns (rp_append's shape, csrc/replay.hip): obs = traj[t][e],
+// A wave owns a transition (t, e), lanes run along the columns (place_rows.h, rp_append's shape): obs = traj[t][e],
 // nxtobs = traj[t + 1][e], the action row, and by lane 0 the reward, the steps and the two zero flags.  The reward is
 // (float)((scale * ssq) / substeps): one fp64 multiply, one correctly rounded fp64 division, one round-to-nearest-even
 // conversion -- numpy's  (-1.0) * (1 / N) * ssq / cfg_steps  cast to fp32, bit for bit (the library is built
@@ -10,18 +10,9 @@
 #include <hip/hip_runtime.h>
 
 #include "ks_internal.h"
-#include "row_ops.h"
+#include "place_rows.h"
 
 namespace {
-
-__device__ __forceinline__ void place_row(const float* __restrict__ in, float* __restrict__ out, int n, bool vec, int lane)
-{
-    if (vec) {
-        for (int j = 4 * lane; j < n; j += 4 * WAVE) *reinterpret_cast<f4*>(out + j) = *reinterpret_cast<const f4*>(in + j);
-    } else {
-        for (int j = lane; j < n; j += WAVE) out[j] = in[j];
-    }
-}
 
 __global__ __launch_bounds__(NT) void ks_record_kernel(const ks::RecordArgs a)
 {

@@ -19,11 +19,11 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
-#include <vector>
 
 #include "../../include/replay/fit.h"
 #include "../../include/replay_hip.h"
 #include "capi_error.h"
+#include "place_rows.h"
 #include "row_ops.h"
 
 namespace {
@@ -99,15 +99,6 @@ struct AppendArgs {
     int T, B, N, A;
     int vec_obs, vec_act;
 };
-
-__device__ __forceinline__ void place_row(const float* __restrict__ in, float* __restrict__ out, int n, bool vec, int lane)
-{
-    if (vec) {
-        for (int j = 4 * lane; j < n; j += 4 * WAVE) *reinterpret_cast<f4*>(out + j) = *reinterpret_cast<const f4*>(in + j);
-    } else {
-        for (int j = lane; j < n; j += WAVE) out[j] = in[j];
-    }
-}
 
 __global__ __launch_bounds__(NT) void rp_append_kernel(const AppendArgs a)
 {
@@ -554,22 +545,15 @@ int rp_append(void* stream, const float* block, int T, int T_cap, int B, int N, 
               const rp_slab* slab)
 {
     if (!block || !dst || !dst_host || !slab) return fail(-30, "rp_append: NULL block, dst, dst_host or slab");
-    if (!slab->obs || !slab->actions || !slab->nxtobs || !slab->rewards || !slab->terminated || !slab->truncated || !slab->steps)
-        return fail(-30, "rp_append: the slab has a NULL field pointer");
+    const PlaceRefusals refusals = {"rp_append", false, -30, -36, -37};
+    if (const int rc = check_slab_fields(refusals, slab)) return rc;
     if (T < 1 || T > T_cap) return fail(-31, "rp_append: %d steps of a block laid out for %d (1 ... %d)", T, T_cap, T_cap);
     if (B < 1) return fail(-32, "rp_append: %d envs (at least 1)", B);
     if (N < 1 || N > RP_MAX_OBS_DIM) return fail(-33, "rp_append: observation width %d (1 ... %d are supported)", N, RP_MAX_OBS_DIM);
     if (A < 1 || A > RP_MAX_ACT_DIM) return fail(-34, "rp_append: action width %d (1 ... %d are supported)", A, RP_MAX_ACT_DIM);
     if (slab->rows < 1) return fail(-35, "rp_append: a slab of %ld rows (at least 1)", slab->rows);
     const long n = (long)T * B;
-    std::vector<bool> seen(static_cast<size_t>(slab->rows), false);
-    for (long i = 0; i < n; ++i) {
-        const long r = dst_host[i];
-        if (r < 0) continue;
-        if (r >= slab->rows) return fail(-36, "rp_append: dst[%ld] = %ld is beyond the slab's %ld rows", i, r, slab->rows);
-        if (seen[r]) return fail(-37, "rp_append: row %ld is named twice (again at dst[%ld])", r, i);
-        seen[r] = true;
-    }
+    if (const int rc = check_dst_rows(refusals, dst_host, n, slab->rows)) return rc;
     AppendArgs a = {};
     a.traj = block;
     a.actions = a.traj + (long)(T_cap + 1) * B * N;

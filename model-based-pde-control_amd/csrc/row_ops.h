@@ -1,7 +1,8 @@
 // row_ops.h -- the arithmetic of the wrapper stack that the controller-loop kernels share: inline device and host helpers
 // only, no kernels, no C ABI.  Includers: replay.hip (affine map, row copy), rollout.hip (affine map, forcing chain),
-// collect.hip (affine map), sur_windows.hip (affine map, row copy, forcing chain); ks_record.hip takes the wave /
-// workgroup constants and aligned16 alone.  In all of them a wave owns a row and lanes run along its columns.
+// collect.hip (affine map), sur_windows.hip (affine map, row copy, forcing chain); place_rows.h (the row placement of
+// replay.hip, ks_record.hip and burgers.hip) takes f4, the wave / workgroup constants and, for its includers' launches,
+// aligned16.  In all of them a wave owns a row and lanes run along its columns.
 //
 // The affine map is ScaleTransform._affine's  out = ((v - a) / (b - a)) * (d - c) + c  as four separately rounded fp32
 // operations (__fsub_rn, __fdiv_rn, __fmul_rn, __fadd_rn), so a kernel's result equals the host transform's bit for bit.

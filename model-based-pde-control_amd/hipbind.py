@@ -9,6 +9,16 @@ torch is imported when the first library is opened, never at import time.
 import ctypes
 import os
 
+
+
+class Slabs(ctypes.Structure):
+    """``replay_slabs`` of include/replay/slabs.h: the seven slab pointers of a device-resident replay and their row
+    count.  The C headers alias it as ``rp_slab``, ``ks_record`` and ``bg_slabs``; the bindings as ``replay_hip.Slab``,
+    ``kspde.ks_record`` and ``pdegym.burgers._hip.Slabs``."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "actions", "nxtobs", "rewards", "terminated", "truncated", "steps")] \
+        + [("rows", ctypes.c_long)]
+
+
 _torch = None       # the torch module, once open_library has imported it (nothing launches before a library is open)
 
 

@@ -27,12 +27,7 @@ VARIANT_NAME = {v: k for k, v in VARIANT.items()}
 _c = ctypes
 _H = _c.c_void_p
 _dp, _fp, _ip = _c.POINTER(_c.c_double), _c.POINTER(_c.c_float), _c.POINTER(_c.c_int)
-
-
-class ks_record(_c.Structure):
-    """``ks_record``: a host struct of the seven slab pointers of a device-resident replay and their rows."""
-    _fields_ = [("obs", _c.c_void_p), ("actions", _c.c_void_p), ("nxtobs", _c.c_void_p), ("rewards", _c.c_void_p),
-                ("terminated", _c.c_void_p), ("truncated", _c.c_void_p), ("steps", _c.c_void_p), ("rows", _c.c_long)]
+ks_record = hipbind.Slabs     # ``ks_record``: the seven slab pointers of a device-resident replay and their rows
 
 
 class ks_eval_batch(_c.Structure):
@@ -249,6 +244,16 @@ class KSStepper:
         vp = lambda x: ctypes.c_void_p(int(x)) if x else None
         _check(self._lib.ks_step_device(self._h, vp(d_phi), vp(d_actions), vp(d_env_ids), int(n_rows),
                                         int(n_substeps), vp(d_obs), vp(d_ssq), vp(d_status)))
+
+    def step_span(self, d_actions, T, n_substeps, d_traj, d_ssq=0, d_status=0):
+        """``T`` steps as ``T`` ``step_device`` launches (``BurgersStepper.step_span``'s signature): step t takes row t of
+        ``d_actions`` [T, E, n_act] and writes slot t + 1 of ``d_traj`` [T + 1, E, N], ``d_ssq`` fp64 [T, E] and
+        ``d_status`` [T, E] (either 0: not written)."""
+        E = self.num_envs
+        row, act_row = E * self.N * 4, E * self.n_act * 4
+        for t in range(T):                                # eager launches, no host synchronisation
+            self.step_device(d_actions=d_actions + t * act_row, n_substeps=n_substeps, d_obs=d_traj + (t + 1) * row,
+                             d_ssq=d_ssq and d_ssq + t * E * 8, d_status=d_status and d_status + t * E * 4)
 
     def reward_rows_device(self, objective, d_obs, d_phi, n_rows, d_reward):
         """Per-row reward of fp32 obs [n_rows, N] with fp32 phi [n_rows, N] (0 = NULL: phi = 0) into fp64 [n_rows],

@@ -35,6 +35,14 @@ scripted tier the kernel tier for an agent whose class IS ``pdecontrol.mbrl.util
               Plan, segments, truncation steps, replay build, sink and write-back are the kernel tier's; the result
               carries ``tier = "kernel"``.
 
+There is one segment path.  ``_Segment`` writes slot 0 and the running bounds to the pinned block, uploads them and the
+action coefficients and binds the stepper (``env.bind_stream``); a tier's runner (``_run_segment`` for a SAC, ``_run_span``
+for a scripted agent) enqueues its launch sequence; ``_Segment.finish`` ends in ``_write_back`` (the whole block comes
+back, the rewards are the env's ``rewards_of`` of the fp64 sums) or, with a sink, in ``record_device`` and ``_restore``.
+The two steppers (``kspde.KSStepper``, ``pdegym.burgers.burgers.BurgersStepper``) have one face: ``step_device``,
+``step_span`` and ``record_device`` on raw device pointers.  What an env knows about itself -- how it binds a stream, how
+a reward is formed -- is a method of the env, and nothing here branches on which env it is.
+
 In both tiers everything the loop mutates ends where the loop leaves it: the worker's two observations, the stores, the
 scaling's bounds, ``env.timestep``, the stepper's state, the env's MT19937 streams, numpy's and torch's generators, and
 the calls to ``callback.on_rollout_end``.  The worker is not reset between calls: consecutive ``collect`` calls continue
@@ -42,8 +50,8 @@ the running episodes as consecutive ``rollout`` calls do.
 
 ``collect(..., sink=replay)`` (``replay`` a ``DeviceExperienceReplay``) returns a ``StagedRollout`` that
 ``replay.extend(staged)`` commits, in place of the host ``ExperienceReplay``.  On the kernel tier a segment's transitions
-go from the block into the sink's slabs with one ``ks_record_device`` launch (csrc/ks_record.hip) after its T steps, on the
-same stream: the rewards are formed on the device, only what the write-back needs comes back to the host (the last
+go from the block into the sink's slabs (``sink.slab()``: include/replay/slabs.h) with one ``ks_record_device`` launch
+(csrc/ks_record.hip) after its T steps, on the same stream: the rewards are formed on the device, only what the write-back needs comes back to the host (the last
 observation row, the last action row, the policy's observation, the bounds and the status), and no host replay is built.
 A truncation step's ``Sample`` is packed, uploaded and placed like a host replay's rows.  On the loop tier the loop's host
 replay is staged through ``_stage_host``.
@@ -51,9 +59,9 @@ replay is staged through ``_stage_host``.
 A stack over a ``BurgersBatchedVecEnv`` (pdegym/burgers/burgers.py) runs on the same tiers through the env's
 ``BurgersStepper``: the SAC tier's step is ``... -> co_act -> bg_step -> co_observe``, a scripted segment is
     co_act_span -> bg_step_span -> co_observe_span
-(include/burgers_hip.h: all ``T`` steps in one launch, the state held in registers between them; 4 launches with an
-updating scaling, 2 without), a sink's segment is placed by one ``bg_record`` launch, and the host rewards are the env's
-``ssq * reward_scale()``.  Truncation steps are host steps of the stack, so the env's per-env ``RandomState`` autoreset
+(include/burgers_hip.h: its ``step_span`` is all ``T`` steps in one launch, the state held in registers between them; 4
+launches with an updating scaling, 2 without), a sink's segment is placed by one ``bg_record`` launch, and the host rewards
+are the env's ``ssq * reward_scale()``.  Truncation steps are host steps of the stack, so the env's per-env ``RandomState`` autoreset
 exists once.
 """
 import gc
@@ -343,14 +351,23 @@ def _scripted_refusal(agent, E, A, steps):
     return None
 
 
-def _scripted_tier(worker, agent, stop):
-    """(RealStackGeometry, None, None) when this phase of a scripted agent runs on the span kernels (co_act_span, the
-    stepper, co_observe_span: include/collect/span.h), else (None, None, reason).  The SAC tier's conditions minus the
-    agent's; the device is the env's."""
+def _kernel_tier(worker, agent, stop=None):
+    """(RealStackGeometry, FusedSAC, None) when this phase runs on the kernels (FusedSAC is None for a scripted agent,
+    which needs ``stop`` to be recognised and runs on the span kernels, include/collect/span.h), else (None, None, reason).
+    One chain of checks for both agent families: the scripted one skips the agent's own (the device is the env's) and
+    adds, before anything is drawn, the shape of what it will draw."""
+    from pdecontrol.sac.sac import SAC
+
     def loop(reason, expected=False):
         _notice(reason, expected)
         return None, None, reason
 
+    scripted = stop is not None and _is_scripted(agent)
+    if not scripted:
+        if not isinstance(agent, SAC):
+            return loop(f"a {type(agent).__name__} agent (not a SAC)", True)
+        if agent.device.type != "cuda":
+            return loop("a SAC agent on the CPU", True)
     if not ops.fused_enabled():
         return loop("PDECONTROL_FUSED=0", True)
     try:
@@ -359,90 +376,68 @@ def _scripted_tier(worker, agent, stop):
         return loop(str(e))
     env = geo.env
     E, A = env.num_envs, geo.action.width
+    if scripted:
+        def steps():                                      # the phase's length, from host integers (a fresh worker resets first)
+            start = env.timestep if worker._last_obs is not None else np.zeros(E, dtype=np.int64)
+            return plan_phase(start, env.max_episode_steps, E, stop).K
 
-    def steps():                                          # the phase's length, from host integers (a fresh worker resets first)
-        start = env.timestep if worker._last_obs is not None else np.zeros(E, dtype=np.int64)
-        return plan_phase(start, env.max_episode_steps, E, stop).K
-
-    reason = _scripted_refusal(agent, E, A, steps)
-    if reason is not None:
-        return loop(reason)
+        reason = _scripted_refusal(agent, E, A, steps)
+        if reason is not None:
+            return loop(reason)
     if env.stepper.device < 0:
         return loop("the CPU twin of the KS stepper")
+    if not scripted and not same_device(torch.device("cuda", env.stepper.device), agent.device):
+        return loop("an agent and an env on different devices")
     from pdecontrol.mbrl import collect_hip as co
     if env.stepper.n_act != A:
         return loop(f"a stepper with {env.stepper.n_act} actuators under {A} action columns")
     reason = co.supported(co.Geometry(E, 1, env.N, A, geo.agent_obs.start, geo.agent_obs.stride))
     if reason is not None:
         return loop(reason)
-    return geo, None, None
-
-
-def _kernel_tier(worker, agent, stop=None):
-    """(RealStackGeometry, FusedSAC, None) when this phase runs on the kernels (FusedSAC is None for a scripted agent,
-    which needs ``stop`` to be recognised), else (None, None, reason)."""
-    from pdecontrol.sac.sac import SAC
-
-    def loop(reason, expected=False):
-        _notice(reason, expected)
-        return None, None, reason
-
-    if stop is not None and _is_scripted(agent):
-        return _scripted_tier(worker, agent, stop)
-    if not isinstance(agent, SAC):
-        return loop(f"a {type(agent).__name__} agent (not a SAC)", True)
-    if agent.device.type != "cuda":
-        return loop("a SAC agent on the CPU", True)
-    if not ops.fused_enabled():
-        return loop("PDECONTROL_FUSED=0", True)
-    try:
-        geo = recognize_real_stack(worker.stack)
-    except Unrecognized as e:
-        return loop(str(e))
-    env = geo.env
-    if env.stepper.device < 0:
-        return loop("the CPU twin of the KS stepper")
-    if not same_device(torch.device("cuda", env.stepper.device), agent.device):
-        return loop("an agent and an env on different devices")
-    from pdecontrol.mbrl import collect_hip as co
+    if scripted:
+        return geo, None, None
     from pdecontrol.sac import sac_hip
-    if env.stepper.n_act != geo.action.width:
-        return loop(f"a stepper with {env.stepper.n_act} actuators under {geo.action.width} action columns")
-    reason = co.supported(co.Geometry(env.num_envs, 1, env.N, geo.action.width, geo.agent_obs.start, geo.agent_obs.stride))
-    if reason is not None:
-        return loop(reason)
-    obs = torch.empty((env.num_envs, 1, geo.agent_obs.width), dtype=torch.float32, device=agent.device)
+    obs = torch.empty((E, 1, geo.agent_obs.width), dtype=torch.float32, device=agent.device)
     if not sac_hip.use_kernels(agent, obs):                 # announces its own reason
         return loop("a SAC geometry the fused kernels refuse")
     return geo, agent._fused_for(obs), None
 
 
-class _Buffers:
-    """Device and pinned host memory of the kernel tier, kept on the worker between phases: the segment block (grown on
-    demand), the agent-side buffers and the workspace."""
+def _built_for(geo, agent):
+    """What a ``_Buffers`` is built for: the device (a scripted agent, ``agent`` None, stands on the env's) and the key
+    ((E, N, A, O, sensor), the shape of the policy's noise or None)."""
+    env, obs = geo.env, geo.agent_obs
+    shape = (env.num_envs, env.N, geo.action.width, obs.width, (obs.start, obs.stride))
+    if agent is None:
+        return torch.device("cuda", env.stepper.device), (shape, None)
+    return agent.device, (shape, (agent.policy.achannels, agent.policy.aheight))
 
-    def __init__(self, agent, geo):
-        from pdecontrol.mbrl import collect_hip as co
-        env = geo.env
-        self.device = torch.empty(0, device=agent.device).device
-        self.E, self.N, self.A, self.O = env.num_envs, env.N, geo.action.width, geo.agent_obs.width
-        self.sensor = (geo.agent_obs.start, geo.agent_obs.stride)
+
+class _Buffers:
+    """Device and pinned host memory of the kernel tier, kept on the worker between phases: the segment block and a
+    sink's index block (both grown on demand) and the action coefficients; built for a SAC (``agent``), the agent-side
+    buffers and the per-step workspace; for a scripted agent (``agent`` None), the segment's action table and the span
+    workspace, grown on demand by ``span``."""
+
+    def __init__(self, geo, agent=None):
+        device, self.key = _built_for(geo, agent)
+        self.device = torch.empty(0, device=device).device
+        (self.E, self.N, self.A, self.O, self.sensor), policy = self.key
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
-        self.noise = f32(self.E, agent.policy.achannels, agent.policy.aheight)
-        self.action, self.env_action = f32(self.E, self.A), f32(self.E, self.A)
-        probe = co.Geometry(self.E, 1, self.N, self.A, *self.sensor)
-        self.workspace = f32(co.workspace_floats(probe))
         self.coef = f32(4, self.A)
         self.block = self.block_host = None
         self.capacity = 0
         self.index = self.index_host = None               # a sink's [dst int64 TE | steps int32 TE], grown on demand
+        self.table = self.table_host = self.env_actions = self.span_workspace = None
+        if agent is not None:
+            from pdecontrol.mbrl import collect_hip as co
+            self.noise = f32(self.E, *policy)
+            self.action, self.env_action = f32(self.E, self.A), f32(self.E, self.A)
+            self.workspace = f32(co.workspace_floats(co.Geometry(self.E, 1, self.N, self.A, *self.sensor)))
 
-    def matches(self, agent, geo):
-        env = geo.env
-        return (same_device(self.device, agent.device)
-                and (self.E, self.N, self.A, self.O, self.sensor) ==
-                (env.num_envs, env.N, geo.action.width, geo.agent_obs.width, (geo.agent_obs.start, geo.agent_obs.stride))
-                and tuple(self.noise.shape[1:]) == (agent.policy.achannels, agent.policy.aheight))
+    def matches(self, geo, agent=None):
+        device, key = _built_for(geo, agent)
+        return same_device(self.device, device) and self.key == key
 
     def layout(self, T):
         """Offsets (in floats) of [traj (T+1)EN | actions TEA | policy_obs EO | bounds 4 | pad | ssq TE fp64 | status TE]."""
@@ -468,7 +463,6 @@ class _Buffers:
 
         return cut(self.block), cut(self.block_host), int(off[-1])
 
-
     def index_views(self, T):
         """(device, pinned host) pairs of a segment's ``dst`` (int64 [T, E]) and ``steps`` (int32 [T, E]): one block, so
         that one copy uploads both."""
@@ -480,28 +474,6 @@ class _Buffers:
         cut = lambda block: (block[:n].view(T, self.E), block[n:words].view(torch.int32)[:n].view(T, self.E))
         return cut(self.index), cut(self.index_host), words
 
-
-class _SpanBuffers(_Buffers):
-    """``_Buffers`` of the scripted tier: no agent-side buffers, the segment's action table (pinned host and device) and
-    the stepper's action rows ``[T, E, A]``, and the span workspace (grown on demand)."""
-
-    def __init__(self, geo):
-        env = geo.env
-        self.device = torch.device("cuda", env.stepper.device)
-        self.E, self.N, self.A, self.O = env.num_envs, env.N, geo.action.width, geo.agent_obs.width
-        self.sensor = (geo.agent_obs.start, geo.agent_obs.stride)
-        self.coef = torch.zeros((4, self.A), dtype=torch.float32, device=self.device)
-        self.block = self.block_host = None
-        self.capacity = 0
-        self.index = self.index_host = None
-        self.table = self.table_host = self.env_actions = self.workspace = None
-
-    def matches(self, geo):
-        env = geo.env
-        return (same_device(self.device, torch.device("cuda", env.stepper.device))
-                and (self.E, self.N, self.A, self.O, self.sensor) ==
-                (env.num_envs, env.N, geo.action.width, geo.agent_obs.width, (geo.agent_obs.start, geo.agent_obs.stride)))
-
     def span(self, T):
         """(device table, pinned host table, stepper action rows) of ``[T, E, A]`` and the workspace of a ``T``-step span."""
         from pdecontrol.mbrl import collect_hip as co
@@ -511,10 +483,11 @@ class _SpanBuffers(_Buffers):
             self.env_actions = torch.empty(n, dtype=torch.float32, device=self.device)
             self.table_host = torch.empty(n, dtype=torch.float32).pin_memory()
         floats = co.span_workspace_floats(co.Geometry(self.E, T, self.N, self.A, *self.sensor))
-        if self.workspace is None or self.workspace.numel() < floats:
-            self.workspace = torch.empty(co.SPAN_MAX_PARTS * 2, dtype=torch.float32, device=self.device)
+        if self.span_workspace is None or self.span_workspace.numel() < floats:
+            self.span_workspace = torch.empty(co.SPAN_MAX_PARTS * 2, dtype=torch.float32, device=self.device)
         shape = (T, self.E, self.A)
-        return self.table[:n].view(shape), self.table_host[:n].view(shape), self.env_actions[:n].view(shape), self.workspace
+        return (self.table[:n].view(shape), self.table_host[:n].view(shape), self.env_actions[:n].view(shape),
+                self.span_workspace)
 
 
 class _SinkPhase:
@@ -549,10 +522,8 @@ class _SinkPhase:
         return np.ascontiguousarray(_rows_of(extents).reshape(self.E, T).T)
 
     def slabs(self):
-        """``ks_record`` of the sink's slabs as they stand (after the segment's reservation: a reservation may grow them)."""
-        import kspde
-        t = self.sink.tensors
-        return kspde.ks_record(*(x.data_ptr() for x in t), self.sink.rows)
+        """The sink's slabs as they stand (after the segment's reservation: a reservation may grow them)."""
+        return self.sink.slab()
 
     def host_step(self, sample):
         """One host step's ``Sample`` of E rows, packed, uploaded and placed with ``index_copy_`` (``_stage_host``'s
@@ -592,47 +563,90 @@ def _host_step(worker, agent, deterministic):
     return Sample(obs, actions, nxtobs, rewards, terminated, truncated, infos["step"])
 
 
-def _bind(geo, current):
-    """The stepper on torch's current stream ``current`` (returned), as ``KSBatchedVecEnv.step_torch`` binds it, with the
-    env's step objective.  A Burgers stepper has neither setting: it launches on the current stream by itself."""
-    env = geo.env
-    if geo.kind == "ks":
-        if getattr(env, "_stream_handle", None) != current.cuda_stream:
-            env.stepper.set_stream(current.cuda_stream)
-            env._stream_handle = current.cuda_stream
-        env._set_objective(env.proto.step_objective)
-    return current
+class _Segment:
+    """``T`` steps without a truncation, from the state the worker and the stack hold: the shared prologue (``__init__``)
+    and the shared finish around a tier's launch sequence.  ``dev`` and ``host`` are the block's device and pinned views
+    (traj, actions, policy_obs, bounds, ssq, status), ``coef`` the action coefficients on the device or None,
+    ``current`` torch's current stream, which the stepper is bound to."""
+
+    def __init__(self, worker, geo, buf, T, policy_obs):
+        """Slot 0 and the running bounds (``policy_obs``: and the policy's observation) written to the pinned block and
+        uploaded, the action coefficients uploaded, the stepper bound."""
+        from pdecontrol.mbrl import collect_hip as co
+        scaling, E, N = geo.scaling, buf.E, buf.N
+        self.worker, self.geo, self.buf, self.T = worker, geo, buf, T
+        self.dev, self.host, self.used = buf.views(T)
+        (traj, _, pobs, bounds, _, _), (h_traj, _, h_pobs, h_bounds, _, _) = self.dev, self.host
+        h_traj[0].copy_(torch.from_numpy(np.ascontiguousarray(worker._last_stored_obs, dtype=np.float32).reshape(E, N)))
+        uploads = [(traj[0], h_traj[0])]
+        if policy_obs:
+            h_pobs.copy_(torch.from_numpy(np.ascontiguousarray(worker._last_obs, dtype=np.float32).reshape(h_pobs.shape)))
+            uploads.append((pobs, h_pobs))
+        if scaling is not None:
+            h_bounds[0] = h_bounds[2] = float(scaling.vmin)
+            h_bounds[1] = h_bounds[3] = float(scaling.vmax)
+        uploads.append((bounds, h_bounds))
+        for dst, src in uploads:
+            dst.copy_(src, non_blocking=True)
+        self.geometry = co.Geometry(E, T, N, buf.A, *buf.sensor)
+        self.coef = None
+        if geo.action.coef is not None:
+            buf.coef.copy_(geo.action.coef)
+            self.coef = buf.coef
+        self.current = torch.cuda.current_stream(buf.device)
+        geo.env.bind_stream(self.current)
+
+    def observe_args(self, workspace):
+        from pdecontrol.mbrl import collect_hip as co
+        scaling, (traj, _, pobs, bounds, _, _) = self.geo.scaling, self.dev
+        if scaling is None:
+            return co.observe_args(traj, pobs, None, 0.0, 0.0, self.geo.update, workspace)
+        return co.observe_args(traj, pobs, bounds, float(scaling.lower), float(scaling.upper), self.geo.update, workspace)
+
+    def finish(self, steps, phase, cell=None):
+        """The segment's replay piece after its one synchronisation, the worker and the stack written back; with a
+        ``_SinkPhase``, the transitions recorded in the sink by one launch instead, and None.  ``cell``: ``_restore``'s."""
+        worker, geo, buf, T = self.worker, self.geo, self.buf, self.T
+        (traj, actions, _, _, ssq, _), (h_traj, h_actions, h_pobs, h_bounds, h_ssq, h_status) = self.dev, self.host
+        if phase is None:
+            buf.block_host[:self.used].copy_(buf.block[:self.used], non_blocking=True)
+            self.current.synchronize()                    # the segment's one synchronisation
+            return _write_back(worker, geo, T, h_traj.numpy(), h_actions.numpy(), h_pobs.numpy(), h_bounds.numpy(),
+                               h_ssq.numpy(), h_status.numpy(), steps, cell)
+        E, N, A = buf.E, buf.N, buf.A
+        dst = phase.reserve(T)
+        (d_dst, d_steps), (h_dst, h_steps), words = buf.index_views(T)
+        h_dst.copy_(torch.from_numpy(dst))
+        h_steps.copy_(torch.from_numpy(np.asarray(steps, dtype=np.int32)))
+        buf.index[:words].copy_(buf.index_host[:words], non_blocking=True)
+        geo.env.stepper.record_device(traj.data_ptr(), actions.data_ptr(), A, ssq.data_ptr(), d_steps.data_ptr(), T,
+                                      geo.env.cfg_steps, d_dst.data_ptr(), dst, phase.slabs())
+        # what the write-back needs, nothing else: the last observation row, the last action row, the policy's
+        # observation with the bounds behind it, the status
+        off = buf.layout(T)
+        for a, b in ((off[0] + T * E * N, off[1]), (off[1] + (T - 1) * E * A, off[2]), (off[2], off[4]), (off[6], off[7])):
+            buf.block_host[int(a):int(b)].copy_(buf.block[int(a):int(b)], non_blocking=True)
+        self.current.synchronize()                        # the segment's one synchronisation
+        _restore(worker, geo, T, h_traj[T].numpy(), h_actions[T - 1].numpy(), h_pobs.numpy(), h_bounds.numpy(),
+                 h_status.numpy(), cell)
+        return None
 
 
 def _run_segment(worker, agent, fused, geo, buf, T, steps, phase=None):
-    """``T`` steps without a truncation in HBM, from the state the worker and the stack hold, written back to them.
+    """A segment of the SAC tier: per step, eagerly on torch's current stream,
+    noise.normal_() -> sac_policy_forward -> co_act -> the stepper -> co_observe  (5 T launches).
     Returns the segment's replay piece, or, with a ``_SinkPhase``, records the transitions in the sink and returns None."""
     from pdecontrol.mbrl import collect_hip as co
-    env, scaling = geo.env, geo.scaling
-    E, N = buf.E, buf.N
-    (traj, actions, pobs, bounds, ssq, status), (h_traj, h_actions, h_pobs, h_bounds, h_ssq, h_status), used = buf.views(T)
-    # slot 0, the policy's observation and the running bounds: written to the pinned block, uploaded once
-    h_traj[0].copy_(torch.from_numpy(np.ascontiguousarray(worker._last_stored_obs, dtype=np.float32).reshape(E, N)))
-    h_pobs.copy_(torch.from_numpy(np.ascontiguousarray(worker._last_obs, dtype=np.float32).reshape(h_pobs.shape)))
-    if scaling is not None:
-        h_bounds[0] = h_bounds[2] = float(scaling.vmin)
-        h_bounds[1] = h_bounds[3] = float(scaling.vmax)
-    for dst, src in ((traj[0], h_traj[0]), (pobs, h_pobs), (bounds, h_bounds)):
-        dst.copy_(src, non_blocking=True)
-    geometry = co.Geometry(E, T, N, buf.A, *buf.sensor)
-    coef = None
-    if geo.action.coef is not None:
-        buf.coef.copy_(geo.action.coef)
-        coef = buf.coef
-    act_args = co.act_args(buf.action, coef, buf.env_action, actions, geo.record_raw)
-    obs_args = co.observe_args(traj, pobs, None if scaling is None else bounds,
-                               0.0 if scaling is None else float(scaling.lower), 0.0 if scaling is None else float(scaling.upper),
-                               geo.update, buf.workspace)
-    current = _bind(geo, torch.cuda.current_stream(buf.device))
+    env, E = geo.env, buf.E
+    seg = _Segment(worker, geo, buf, T, policy_obs=True)
+    traj, actions, pobs, _, ssq, status = seg.dev
+    geometry = seg.geometry
+    act_args = co.act_args(buf.action, seg.coef, buf.env_action, actions, geo.record_raw)
+    obs_args = seg.observe_args(buf.workspace)
     fused.refresh_current()
     stream, forward = co.stream(), fused.forward_launcher(E, pobs, buf.noise, buf.action)
     d_env_action, substeps = buf.env_action.data_ptr(), env.cfg_steps
-    row, slot = E * N * 4, traj.data_ptr()
+    row, slot = E * buf.N * 4, traj.data_ptr()
     d_ssq, d_status = ssq.data_ptr(), status.data_ptr()
     for t in range(T):                                    # eager launches, ``t`` by value, no host synchronisation
         buf.noise.normal_()                               # the draw of ``SAC.act``: same call, shape and device
@@ -641,86 +655,26 @@ def _run_segment(worker, agent, fused, geo, buf, T, steps, phase=None):
         env.stepper.step_device(d_actions=d_env_action, n_substeps=substeps, d_obs=slot + (t + 1) * row,
                                 d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)
         co.observe(stream, geometry, obs_args, t)
-    if phase is not None:
-        A = buf.A
-        dst = phase.reserve(T)
-        (d_dst, d_steps), (h_dst, h_steps), words = buf.index_views(T)
-        h_dst.copy_(torch.from_numpy(dst))
-        h_steps.copy_(torch.from_numpy(np.asarray(steps, dtype=np.int32)))
-        buf.index[:words].copy_(buf.index_host[:words], non_blocking=True)
-        env.stepper.record_device(traj.data_ptr(), actions.data_ptr(), A, d_ssq, d_steps.data_ptr(), T, substeps,
-                                  d_dst.data_ptr(), dst, phase.slabs())
-        # what the write-back needs, nothing else: the last observation row, the last action row, the policy's
-        # observation with the bounds behind it, the status
-        off = buf.layout(T)
-        for a, b in ((off[0] + T * E * N, off[1]), (off[1] + (T - 1) * E * A, off[2]), (off[2], off[4]), (off[6], off[7])):
-            buf.block_host[int(a):int(b)].copy_(buf.block[int(a):int(b)], non_blocking=True)
-        current.synchronize()                             # the segment's one synchronisation
-        _restore(worker, geo, T, h_traj[T].numpy(), h_actions[T - 1].numpy(), h_pobs.numpy(), h_bounds.numpy(),
-                 h_status.numpy())
-        return None
-    buf.block_host[:used].copy_(buf.block[:used], non_blocking=True)
-    current.synchronize()                                 # the segment's one synchronisation
-    return _write_back(worker, geo, T, h_traj.numpy(), h_actions.numpy(), h_pobs.numpy(), h_bounds.numpy(), h_ssq.numpy(),
-                       h_status.numpy(), steps)
+    return seg.finish(steps, phase)
 
 
 def _run_span(worker, agent, geo, buf, T, steps, deterministic, phase=None):
-    """``_run_segment`` for a scripted agent: the agent's ``T`` actions are drawn on the host first, in order, and uploaded
-    once; then  co_act_span -> T x ks_step_device -> co_observe_span  (T + 3 launches, T + 1 with a frozen or absent
-    scaling), the sink's record launch and the same write-back, with the bounds taken from cell 1."""
+    """A segment of the scripted tier: the agent's ``T`` actions are drawn on the host first, in the loop's order, and
+    uploaded once; then  co_act_span -> the stepper's ``step_span`` -> co_observe_span  (KS: T step launches, T + 3 in
+    all, T + 1 with a frozen or absent scaling; Burgers: one), with the bounds taken from cell 2."""
     from pdecontrol.mbrl import collect_hip as co
-    env, scaling = geo.env, geo.scaling
-    E, N, A = buf.E, buf.N, buf.A
-    (traj, actions, pobs, bounds, ssq, status), (h_traj, h_actions, h_pobs, h_bounds, h_ssq, h_status), used = buf.views(T)
     table, h_table, env_actions, workspace = buf.span(T)
     for t in range(T):                                    # the loop's draws, in the loop's order
         drawn = agent.select_action(worker._last_obs, deterministic=deterministic)
-        h_table[t].copy_(torch.from_numpy(np.ascontiguousarray(drawn, dtype=np.float32).reshape(E, A)))
-    h_traj[0].copy_(torch.from_numpy(np.ascontiguousarray(worker._last_stored_obs, dtype=np.float32).reshape(E, N)))
-    if scaling is not None:
-        h_bounds[0] = h_bounds[2] = float(scaling.vmin)
-        h_bounds[1] = h_bounds[3] = float(scaling.vmax)
-    for dst, src in ((traj[0], h_traj[0]), (bounds, h_bounds), (table, h_table)):
-        dst.copy_(src, non_blocking=True)
-    geometry = co.Geometry(E, T, N, A, *buf.sensor)
-    coef = None
-    if geo.action.coef is not None:
-        buf.coef.copy_(geo.action.coef)
-        coef = buf.coef
-    current = _bind(geo, torch.cuda.current_stream(buf.device))
+        h_table[t].copy_(torch.from_numpy(np.ascontiguousarray(drawn, dtype=np.float32).reshape(buf.E, buf.A)))
+    seg = _Segment(worker, geo, buf, T, policy_obs=False)
+    traj, actions, _, _, ssq, status = seg.dev
+    table.copy_(h_table, non_blocking=True)
     stream = co.stream()
-    co.act_span(stream, geometry, co.act_span_args(table, coef, env_actions, actions, geo.record_raw))
-    substeps, row, slot = env.cfg_steps, E * N * 4, traj.data_ptr()
-    d_env_actions, d_ssq, d_status = env_actions.data_ptr(), ssq.data_ptr(), status.data_ptr()
-    if geo.kind == "burgers":                             # the whole segment in one launch, the state held in registers
-        env.stepper.step_span(d_env_actions, T, substeps, slot, d_ssq, d_status)
-    else:
-        for t in range(T):                                # eager launches, no host synchronisation
-            env.stepper.step_device(d_actions=d_env_actions + t * E * A * 4, n_substeps=substeps, d_obs=slot + (t + 1) * row,
-                                    d_ssq=d_ssq + t * E * 8, d_status=d_status + t * E * 4)
-    co.observe_span(stream, geometry, co.observe_args(
-        traj, pobs, None if scaling is None else bounds, 0.0 if scaling is None else float(scaling.lower),
-        0.0 if scaling is None else float(scaling.upper), geo.update, workspace))
-    if phase is not None:
-        dst = phase.reserve(T)
-        (d_dst, d_steps), (h_dst, h_steps), words = buf.index_views(T)
-        h_dst.copy_(torch.from_numpy(dst))
-        h_steps.copy_(torch.from_numpy(np.asarray(steps, dtype=np.int32)))
-        buf.index[:words].copy_(buf.index_host[:words], non_blocking=True)
-        env.stepper.record_device(traj.data_ptr(), actions.data_ptr(), A, d_ssq, d_steps.data_ptr(), T, substeps,
-                                  d_dst.data_ptr(), dst, phase.slabs())
-        off = buf.layout(T)
-        for a, b in ((off[0] + T * E * N, off[1]), (off[1] + (T - 1) * E * A, off[2]), (off[2], off[4]), (off[6], off[7])):
-            buf.block_host[int(a):int(b)].copy_(buf.block[int(a):int(b)], non_blocking=True)
-        current.synchronize()                             # the segment's one synchronisation
-        _restore(worker, geo, T, h_traj[T].numpy(), h_actions[T - 1].numpy(), h_pobs.numpy(), h_bounds.numpy(),
-                 h_status.numpy(), cell=2)
-        return None
-    buf.block_host[:used].copy_(buf.block[:used], non_blocking=True)
-    current.synchronize()                                 # the segment's one synchronisation
-    return _write_back(worker, geo, T, h_traj.numpy(), h_actions.numpy(), h_pobs.numpy(), h_bounds.numpy(), h_ssq.numpy(),
-                       h_status.numpy(), steps, cell=2)
+    co.act_span(stream, seg.geometry, co.act_span_args(table, seg.coef, env_actions, actions, geo.record_raw))
+    geo.env.stepper.step_span(env_actions.data_ptr(), T, geo.env.cfg_steps, traj.data_ptr(), ssq.data_ptr(), status.data_ptr())
+    co.observe_span(stream, seg.geometry, seg.observe_args(workspace))
+    return seg.finish(steps, phase, cell=2)
 
 
 def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, steps, cell=None):
@@ -729,11 +683,7 @@ def _write_back(worker, geo, T, traj, actions, policy_obs, bounds, ssq, status, 
     env = geo.env
     _restore(worker, geo, T, traj[T], actions[T - 1], policy_obs, bounds, status, cell)
     traj, actions = traj.copy(), actions.copy()
-    if geo.kind == "burgers":
-        rewards = ssq * env.reward_scale()                # ``BurgersBatchedVecEnv.step_torch``, every step at once
-    else:
-        rewards = (-1.0) * (1 / env.N) * ssq / env.cfg_steps  # ``KSBatchedVecEnv._finish_step``, every step at once
-    return traj, actions, rewards, steps
+    return traj, actions, env.rewards_of(ssq), steps      # the env's own reward expression, every step at once
 
 
 def _restore(worker, geo, T, last_obs, last_actions, policy_obs, bounds, status, cell=None):
@@ -805,33 +755,28 @@ def collect(worker, agent, stop, deterministic=False, sink=None):
             worker._last_obs = worker.stack.envs.reset()
             worker._last_stored_obs = _stored(worker.stack.ostore, worker.stack.ostore.obs)
         plan = plan_phase(env.timestep, env.max_episode_steps, E, stop)
-        if scripted:
-            buf = getattr(worker, "_span_buffers", None)
-            if buf is None or not buf.matches(geo):
-                buf = worker._span_buffers = _SpanBuffers(geo)
-        else:
-            buf = getattr(worker, "_collect_buffers", None)
-            if buf is None or not buf.matches(agent, geo):
-                buf = worker._collect_buffers = _Buffers(agent, geo)
+        # one ``_Buffers`` per agent family on the worker: warm-up, collection and evaluation alternate between them
+        sac, slot = (None, "_span_buffers") if scripted else (agent, "_collect_buffers")
+        buf = getattr(worker, slot, None)
+        if buf is None or not buf.matches(geo, sac):
+            buf = _Buffers(geo, sac)
+            setattr(worker, slot, buf)
         pieces, host_steps = [], 0
         phase = None if sink is None else _SinkPhase(sink, E, env.N, buf.A, plan.K * E)
         try:
             for kind, first, n in segments(plan, segment_steps(E, env.N, buf.A)):
+                steps = plan.steps[first:first + n]
                 if kind == "host":
-                    sample = _host_step(worker, agent, deterministic)
+                    piece = _host_step(worker, agent, deterministic)
                     host_steps += 1
-                    if phase is None:
-                        pieces.append(sample)
-                    else:
-                        phase.host_step(sample)
+                    if phase is not None:
+                        phase.host_step(piece)
                 elif scripted:
-                    piece = _run_span(worker, agent, geo, buf, n, plan.steps[first:first + n], deterministic, phase)
-                    if phase is None:
-                        pieces.append(piece)
+                    piece = _run_span(worker, agent, geo, buf, n, steps, deterministic, phase)
                 else:
-                    piece = _run_segment(worker, agent, fused, geo, buf, n, plan.steps[first:first + n], phase)
-                    if phase is None:
-                        pieces.append(piece)
+                    piece = _run_segment(worker, agent, fused, geo, buf, n, steps, phase)
+                if phase is None:
+                    pieces.append(piece)
         except BaseException:
             if phase is not None and phase.staged.state == "open":
                 sink.discard(phase.staged)                # the rows of a phase that raised are never committed

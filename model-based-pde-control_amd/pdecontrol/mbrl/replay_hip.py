@@ -22,11 +22,7 @@ class Source(ctypes.Structure):
                 ("obs_coef", _p), ("act_coef", _p)]
 
 
-class Slab(ctypes.Structure):
-    """``rp_slab`` of include/replay_hip.h"""
-    _fields_ = [("obs", _p), ("actions", _p), ("nxtobs", _p), ("rewards", _p), ("terminated", _p), ("truncated", _p),
-                ("steps", _p), ("rows", _l)]
-
+Slab = hipbind.Slabs     # ``rp_slab`` of include/replay_hip.h
 
 _src = ctypes.POINTER(Source)
 SYMBOLS = (

@@ -8,14 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "lib", "libburgers_hip.so"))
 
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-
-
-class Slabs(ctypes.Structure):
-    """``bg_slabs`` of include/burgers_hip.h: the seven slab pointers of a device-resident replay and their row count,
-    field for field ``kspde.ks_record``."""
-    _fields_ = [("obs", _p), ("actions", _p), ("nxtobs", _p), ("rewards", _p), ("terminated", _p), ("truncated", _p),
-                ("steps", _p), ("rows", ctypes.c_long)]
-
+Slabs = hipbind.Slabs     # ``bg_slabs`` of include/burgers_hip.h
 
 SYMBOLS = (
     ("bg_step", _i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, ctypes.c_long, _p, _p, _p]),

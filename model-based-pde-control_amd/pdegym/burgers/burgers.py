@@ -58,14 +58,11 @@ class BurgersStepper:
 
     def record_device(self, d_traj, d_actions, A, d_ssq, d_steps, T, n_substeps, d_dst, dst_host, slabs):
         """The ``T * num_envs`` transitions of ``T`` steps without a truncation into replay rows; see ``bg_record``.
-        ``dst_host`` a C-contiguous int64 array [T, num_envs]; ``slabs`` a ``_hip.Slabs`` or a ``kspde.ks_record`` (the
-        same eight fields)."""
+        ``dst_host`` a C-contiguous int64 array [T, num_envs]; ``slabs`` a ``hipbind.Slabs`` (``_hip.Slabs``)."""
         vp = _void_p
         if dst_host is not None:
             assert dst_host.dtype == np.int64 and dst_host.flags["C_CONTIGUOUS"] and dst_host.size == int(T) * self.num_envs, \
                 (dst_host.dtype, dst_host.shape, T, self.num_envs)
-        if slabs is not None and not isinstance(slabs, _hip.Slabs):
-            slabs = _hip.Slabs.from_buffer_copy(slabs)
         _hip.check(self._lib.bg_record(_stream(self._env.device), vp(d_traj), vp(d_actions), self.num_envs, self.N, int(A),
                                        vp(d_ssq), vp(d_steps), int(T), int(n_substeps), vp(d_dst),
                                        None if dst_host is None else dst_host.ctypes.data_as(_hip.ctypes.c_void_p),
@@ -145,6 +142,13 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
         """The fp64 factor ``c`` of a step's reward ``ssq * c``: minus the mean square, averaged over the sub-steps."""
         n = self.cfg_steps if n_substeps is None else int(n_substeps)
         return -(1.0 / self.N) / max(n, 1)
+
+    def rewards_of(self, ssq):
+        """The rewards of steps of ``cfg_steps`` sub-steps from their fp64 sums ``ssq`` on the host (any shape)."""
+        return ssq * self.reward_scale()
+
+    def bind_stream(self, stream):
+        """Nothing to bind: every launch takes torch's current stream by itself, and the objective is fixed."""
 
     def _raise_on(self, status):
         """``status`` [E] of one step: the ``FloatingPointError`` of ``step_wait`` when any env's state is non-finite."""

@@ -140,10 +140,23 @@ class KSBatchedVecEnv(gym.vector.VectorEnv):
         self._actions = None
         return self._finish_step(obs, ssq, status)
 
+    def rewards_of(self, ssq):
+        """The rewards of steps of ``cfg_steps`` sub-steps from their fp64 sums ``ssq`` on the host (any shape).  The order
+        of the operations is the bits: ``ks_record_device`` forms the same three roundings on the device."""
+        return (-1.0) * (1 / self.N) * ssq / self.cfg_steps
+
+    def bind_stream(self, stream):
+        """The stepper on the torch stream ``stream`` (``set_stream`` only when the handle changed) and on the env's step
+        objective: what precedes ``step_device`` launches that are to run in order with torch's work on ``stream``."""
+        if getattr(self, "_stream_handle", None) != stream.cuda_stream:
+            self.stepper.set_stream(stream.cuda_stream)
+            self._stream_handle = stream.cuda_stream
+        self._set_objective(self.proto.step_objective)
+
     def _finish_step(self, obs, ssq, status):
         """Rewards, episode bookkeeping and autoreset from the raw outputs of one step of every env."""
         self._raise_on(status)
-        rewards = (-1.0) * (1 / self.N) * ssq / self.cfg_steps
+        rewards = self.rewards_of(ssq)
         self.timestep += 1
         truncated = self.timestep >= self.max_episode_steps
         terminated = np.zeros(self.num_envs, dtype=bool)
@@ -173,12 +186,8 @@ class KSBatchedVecEnv(gym.vector.VectorEnv):
             self._dev_out = (torch.empty((self.num_envs, 1, self.N), dtype=torch.float32, device=dev),
                              torch.empty(self.num_envs, dtype=torch.float64, device=dev),
                              torch.zeros(self.num_envs, dtype=torch.int32, device=dev))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if getattr(self, "_stream_handle", None) != stream:
-            self.stepper.set_stream(stream)
-            self._stream_handle = stream
+        self.bind_stream(torch.cuda.current_stream(dev))
         obs, ssq, status = self._dev_out
-        self._set_objective(self.proto.step_objective)
         self.stepper.step_device(d_actions=a.data_ptr(), n_substeps=self.cfg_steps, d_obs=obs.data_ptr(),
                                  d_ssq=ssq.data_ptr(), d_status=status.data_ptr())
         rewards = ssq * (-(1.0 / self.N) / self.cfg_steps)

@@ -202,3 +202,37 @@ def test_a_scripted_segment_is_three_span_calls(monkeypatch):
     torch.cuda.synchronize()
     assert got.tier == "kernel" and got.host_steps == 0
     assert counts == {"act_span": 1, "step_span": 1, "observe_span": 1, "record_device": 1}, counts
+
+
+def test_a_sac_segment_is_t_times_act_step_observe(monkeypatch):
+    """One segment of three steps of the SAC tier: three ``co_act``, three ``bg_step`` and three ``co_observe`` calls and no
+    span call; through a sink, one ``bg_record`` call more."""
+    from pdecontrol.mbrl import collect_hip as co
+    from pdecontrol.mbrl import collection_phase as cp
+    from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
+    E, Tn = 5, 3
+    s = build(E, 64, 1, 12)
+    sc.seed()
+    sc.prime(s.worker, 11, stagger=False)
+    counts = {}
+
+    def counted(name, fn):
+        def call(*args, **kwargs):
+            counts[name] = counts.get(name, 0) + 1
+            return fn(*args, **kwargs)
+        return call
+
+    for name in ("act", "observe", "act_span", "observe_span"):
+        monkeypatch.setattr(co, name, counted(name, getattr(co, name)))
+    stepper = s.env.stepper
+    for name in ("step_device", "step_span", "record_device"):
+        monkeypatch.setattr(stepper, name, counted(name, getattr(stepper, name)))
+    got = cp.collect(s.worker, s.agent, lambda ts, ep: ts >= Tn * E)
+    torch.cuda.synchronize()
+    assert got.tier == "kernel" and got.host_steps == 0 and got.ntimesteps == Tn * E
+    assert counts == {"act": Tn, "step_device": Tn, "observe": Tn}, counts
+    counts.clear()
+    got = cp.collect(s.worker, s.agent, lambda ts, ep: ts >= Tn * E, sink=DeviceExperienceReplay(device=DEV))
+    torch.cuda.synchronize()
+    assert got.tier == "kernel" and got.host_steps == 0
+    assert counts == {"act": Tn, "step_device": Tn, "observe": Tn, "record_device": 1}, counts

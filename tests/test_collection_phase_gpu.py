@@ -227,3 +227,41 @@ def test_a_two_step_observation_store_runs_the_loop():
     kernel, _ = _run("collect", 5, 64, 1, **kwargs)
     assert len(kernel) == 1 and kernel[0][0].ntimesteps == 15
     _compare(loop, kernel, "loop", "an observation store of 2 steps")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# launches
+# ----------------------------------------------------------------------------------------------------------------------
+def test_a_sac_segment_is_t_times_act_step_observe(monkeypatch):
+    """One segment of three steps: three ``co_act``, three ``ks_step_device`` and three ``co_observe`` calls and no span
+    call; through a sink, one ``ks_record_device`` call more."""
+    from pdecontrol.mbrl import collect_hip as co
+    from pdecontrol.mbrl import collection_phase as cp
+    from pdecontrol.mbrl.device_replay import DeviceExperienceReplay
+    E, Tn = 5, 3
+    s = sc.build(E=E, N=64, device=0, agent_device="cuda:0", tmax=3.0)
+    sc.seed()
+    sc.prime(s.worker, 11, stagger=False)
+    counts = {}
+
+    def counted(name, fn):
+        def call(*args, **kwargs):
+            counts[name] = counts.get(name, 0) + 1
+            return fn(*args, **kwargs)
+        return call
+
+    for name in ("act", "observe", "act_span", "observe_span"):
+        monkeypatch.setattr(co, name, counted(name, getattr(co, name)))
+    stepper = s.env.stepper
+    for name in ("step_device", "step_span", "record_device"):
+        if hasattr(stepper, name):
+            monkeypatch.setattr(stepper, name, counted(name, getattr(stepper, name)))
+    got = cp.collect(s.worker, s.agent, lambda ts, ep: ts >= Tn * E)
+    torch.cuda.synchronize()
+    assert got.tier == "kernel" and got.host_steps == 0 and got.ntimesteps == Tn * E
+    assert counts == {"act": Tn, "step_device": Tn, "observe": Tn}, counts
+    counts.clear()
+    got = cp.collect(s.worker, s.agent, lambda ts, ep: ts >= Tn * E, sink=DeviceExperienceReplay(device=torch.device("cuda", 0)))
+    torch.cuda.synchronize()
+    assert got.tier == "kernel" and got.host_steps == 0
+    assert counts == {"act": Tn, "step_device": Tn, "observe": Tn, "record_device": 1}, counts

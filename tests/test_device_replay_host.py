@@ -284,13 +284,16 @@ def test_imagine_with_a_sink_on_the_loop_tier_returns_the_host_replay():
 # header, binding and the host-side refusals
 # ---------------------------------------------------------------------------------------------------------------------
 def test_slab_header_binding_and_library_agree():
-    """The slab entries are declared beside the gather's, and the header's struct is the binding's (that the binding's
+    """The slab entries are declared beside the gather's, and the header's struct -- ``replay_slabs`` of
+    include/replay/slabs.h, which replay_hip.h includes and names ``rp_slab`` -- is the binding's (that the binding's
     table holds exactly these names and the library exports them: tests/test_capi_symbols.py)."""
     from pdecontrol.mbrl import replay_hip
     assert declared_functions("replay_hip.h", "rp") == ["rp_append", "rp_episode_returns", "rp_gather", "rp_last_error",
                                                         "rp_supported"]
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "replay_hip.h")).read(), flags=re.S)
-    fields = re.search(r"typedef struct rp_slab \{(.*?)\} rp_slab;", text, re.S).group(1)
+    plain = lambda *path: re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", *path)).read(), flags=re.S)
+    header = plain("replay_hip.h")
+    assert '#include "replay/slabs.h"' in header and re.search(r"^typedef replay_slabs rp_slab;", header, re.M)
+    fields = re.search(r"typedef struct replay_slabs \{(.*?)\} replay_slabs;", plain("replay", "slabs.h"), re.S).group(1)
     declared = [n for decl in fields.split(";") for n in re.findall(r"\*?\s*([a-z_]+)\s*(?:,|$)", decl.strip())]
     assert declared == [n for n, _ in replay_hip.Slab._fields_]
 

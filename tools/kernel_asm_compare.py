@@ -12,6 +12,7 @@ import hashlib
 import os
 import re
 import subprocess
+import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,12 +34,15 @@ def bodies(root, source, flags):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    # everything after the first "--" goes to hipcc: argparse fills a trailing nargs="*" positional (with nothing) the
+    # moment it sees `source`, and then rejects the flags
+    argv = sys.argv[1:]
+    cut = argv.index("--") if "--" in argv else len(argv)
+    ap = argparse.ArgumentParser(usage="%(prog)s source --parent PARENT [-- extra hipcc flags]")
     ap.add_argument("source")
     ap.add_argument("--parent", required=True)
-    ap.add_argument("flags", nargs="*")
-    args = ap.parse_args()
-    old, new = bodies(args.parent, args.source, args.flags), bodies(ROOT, args.source, args.flags)
+    args, flags = ap.parse_args(argv[:cut]), argv[cut + 1:]
+    old, new = bodies(args.parent, args.source, flags), bodies(ROOT, args.source, flags)
     names = subprocess.run(["c++filt"] + sorted(set(old) | set(new)), capture_output=True, text=True).stdout.splitlines()
     print("%-70s %8s %8s  %-9s %s" % ("kernel of " + args.source, "parent", "new", "", "sha256[:16] of the new body"))
     for raw, name in zip(sorted(set(old) | set(new)), names):
