@@ -1,5 +1,5 @@
 // sur_common.h -- what every stage of the surrogate kernels uses: the STAMP macro and its buffers, TPB, LN_EPS, the DPP / swap
-// lane reductions (group_sum2), sigmoid_ / tanh_, wrapi, and the global <-> LDS movers (lds_load, lds_dma_v4, lds_store,
+// lane reductions (group_sum2, group_sum1), sigmoid_ / tanh_, wrapi, and the global <-> LDS movers (lds_load, lds_dma_v4, lds_store,
 // lds_load_v4).  Needs no other sur_*.h.
 #ifndef SUR_COMMON_H
 #define SUR_COMMON_H
@@ -66,6 +66,16 @@ __device__ __forceinline__ void group_sum2(float& a, float& b, int lpc) {
         a = swap_add32(a);
         b = swap_add32(b);
     }
+}
+
+// the same for one value: a reduction that has to wait for the result of another (the two-pass variance of sur_layernorm.h)
+__device__ __forceinline__ void group_sum1(float& a, int lpc) {
+    a += dpp_rot<0x128>(a);
+    a += dpp_rot<0x124>(a);
+    a += dpp_rot<0x122>(a);
+    a += dpp_rot<0x121>(a);
+    if (lpc >= 32) a = swap_add16(a);
+    if (lpc >= 64) a = swap_add32(a);
 }
 
 // sigmoid / tanh on the hardware transcendentals (v_exp_f32, v_rcp_f32: ~1 ulp each) instead of libm's expf / tanhf and an

@@ -10,8 +10,15 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over the spatial axis fused with the preceding activation.  A channel is handled by a
 // group of LPC = min(64, H) lanes (64/LPC channels per wavefront at a time), each lane keeping its
-// H/LPC activated values in registers; mean and E[y^2] are reduced TOGETHER (two interleaved chains)
-// with DPP row rotations inside 16-lane rows and one ds_bpermute per doubling beyond a row.
+// H/LPC activated values in registers; sums go through DPP row rotations inside 16-lane rows and one
+// lane swap per doubling beyond a row (group_sum1 / group_sum2).
+// The variance is TWO-PASS: the mean first, then E[(y - mean)^2] from the registers the values sit in; the centred
+// values are the ones the normalisation needs anyway, so this costs no instruction over var = E[y^2] - mean^2 from one
+// joint reduction, only the second reduction's latency.  That one-pass form loses mean^2 / var ulps to its
+// cancellation: a row riding on an offset (a state on a constant background through the bias-free encoder blocks, a
+// decoder bias in front of SiLU) came out 1e-2 of scale wrong ("The LayerNorm variance is centred").
+// Forward and backward take the statistics in the same way, so the recomputing and the saved-activation backward see
+// the same bits.
 // ---------------------------------------------------------------------------------------------
 constexpr int LN_MAX_EPL = 4;  // H <= 256
 
@@ -33,20 +40,28 @@ __device__ void act_ln_fwd(const float* pre, int C, int H, const float* gamma, c
             if (e < epl) {
                 const float v = x[gl + e * lpc];
                 y[e] = silu ? v * sigmoid_(v) : v;
-                s += y[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < LN_MAX_EPL; ++e)
+            if (e < epl) s += y[e];
+        group_sum1(s, lpc);
+        const float mean = s * inv_h;
+#pragma unroll
+        for (int e = 0; e < LN_MAX_EPL; ++e) {
+            if (e < epl) {
+                y[e] -= mean;
                 ss = fmaf(y[e], y[e], ss);
             }
         }
-        group_sum2(s, ss, lpc);
-        const float mean = s * inv_h;
-        const float var = fmaxf(fmaf(-mean, mean, ss * inv_h), 0.0f);
-        const float rstd = rsqrtf(var + LN_EPS);
+        group_sum1(ss, lpc);
+        const float rstd = rsqrtf(ss * inv_h + LN_EPS);
         if (live) {
 #pragma unroll
             for (int e = 0; e < LN_MAX_EPL; ++e) {
                 if (e < epl) {
                     const int p = gl + e * lpc;
-                    out[c * H + p] = fmaf((y[e] - mean) * rstd, gamma[p], beta[p]);
+                    out[c * H + p] = fmaf(y[e] * rstd, gamma[p], beta[p]);
                 }
             }
         }
@@ -76,19 +91,27 @@ __device__ void act_ln_bwd(const float* dout, const float* pre, int C, int H, co
                 v_[e] = x[p];
                 y[e] = silu ? v_[e] * sigmoid_(v_[e]) : v_[e];
                 dxh[e] = dout[cc * H + p] * gamma[p];
-                s += y[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < LN_MAX_EPL; ++e)
+            if (e < epl) s += y[e];
+        group_sum1(s, lpc);
+        const float mean = s * inv_h;
+#pragma unroll
+        for (int e = 0; e < LN_MAX_EPL; ++e) {
+            if (e < epl) {
+                y[e] -= mean;
                 ss = fmaf(y[e], y[e], ss);
             }
         }
-        group_sum2(s, ss, lpc);
-        const float mean = s * inv_h;
-        const float var = fmaxf(fmaf(-mean, mean, ss * inv_h), 0.0f);
-        const float rstd = rsqrtf(var + LN_EPS);
+        group_sum1(ss, lpc);
+        const float rstd = rsqrtf(ss * inv_h + LN_EPS);
         float m1 = 0.0f, m2 = 0.0f;
 #pragma unroll
         for (int e = 0; e < LN_MAX_EPL; ++e) {
             if (e < epl) {
-                y[e] = (y[e] - mean) * rstd;  // xhat
+                y[e] *= rstd;  // xhat
                 m1 += dxh[e];
                 m2 = fmaf(dxh[e], y[e], m2);
             }

@@ -137,6 +137,13 @@ __device__ __forceinline__ void nr_conv(const float* in, int cin, int hin, const
     }
 }
 
+// The narrow LayerNorm centres its variance too, but keeps ONE butterfly for all channels' sums: every value is taken relative
+// to the row's FIRST value (position 0 sits in lane 0: one v_readlane, wave-uniform) before the joint reduction, var = E[t^2] -
+// E[t]^2 with t = y - y[0].  E[t]^2 / var is then at most H, whatever offset the row rides on (one value cannot lie further
+// from the mean than sqrt(H) deviations); a second butterfly for a two-pass variance (sur_layernorm.h) would double the
+// cross-lane work of a wave that has nothing to hide it behind.
+__device__ __forceinline__ float nr_row_first(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)); }
+
 // y = LayerNorm_H(act(x)) * gamma + beta, rows = channels, statistics over the 64 lanes x TE positions
 template <int TC, int TE>
 __device__ __forceinline__ void nr_ln_fwd(const NrTile<TC, TE>& x, int C, int H, const float* gamma, const float* beta, bool silu,
@@ -151,6 +158,11 @@ __device__ __forceinline__ void nr_ln_fwd(const NrTile<TC, TE>& x, int C, int H,
             const bool live = c < C && lane + 64 * e < H;
             const float v = x.v[c][e];
             a[c][e] = live ? (silu ? v * sigmoid_(v) : v) : 0.0f;
+        }
+        const float a0 = nr_row_first(a[c][0]);
+#pragma unroll
+        for (int e = 0; e < TE; ++e) {
+            if (c < C && lane + 64 * e < H) a[c][e] -= a0;
             s += a[c][e];
             ss = fmaf(a[c][e], a[c][e], ss);
         }
@@ -186,6 +198,11 @@ __device__ __forceinline__ void nr_ln_bwd(const NrTile<TC, TE>& dout, const NrTi
             const float v = pre.v[c][e];
             y[c][e] = live ? (silu ? v * sigmoid_(v) : v) : 0.0f;
             dxh[c][e] = live ? dout.v[c][e] * gamma[p] : 0.0f;
+        }
+        const float y0 = nr_row_first(y[c][0]);
+#pragma unroll
+        for (int e = 0; e < TE; ++e) {
+            if (c < C && lane + 64 * e < H) y[c][e] -= y0;
             s += y[c][e];
             ss = fmaf(y[c][e], y[c][e], ss);
         }

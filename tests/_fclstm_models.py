@@ -301,26 +301,28 @@ def bars():
 OBSERVED = "fclstm_regimes"
 
 
-def record(case, ref, yard, got=None, who="kernels"):
+def record(case, ref, yard, got=None, who="kernels", slices=grad_slices, figures=None, observed=OBSERVED):
     """The observed-file record of one case (fclstm_regimes_observed.jsonl next to the gradient parity log): the fp32 CPU
-    module (``yard``) and, when given, the kernels (``got``) against the fp64 module (``ref``), with the bars."""
+    module (``yard``) and, when given, the kernels (``got``) against the fp64 module (``ref``), with the bars.  ``slices``,
+    ``figures`` ({"yardstick", "bars"}) and ``observed`` are another family's (tests/_convlstm_models.py)."""
     runs = {"fp32_cpu": yard} if got is None else {who: got, "fp32_cpu": yard}
     rec = {"case": case.name,
            "forward_err_of_scale": {w: dm.worst_of(forward_errors(r["tensors"], ref["tensors"])) for w, r in runs.items()},
            "gradient_err_of_scale": {w: dm.worst_of(dm.tensor_errors(r["grads"], ref["grads"])) for w, r in runs.items()},
-           "worst_slice": {w: dm.worst_slice(r["grads"], ref["grads"], grad_slices) for w, r in runs.items()},
-           "yardstick": yardstick(), "bars": bars()}
-    dm.observe(rec, OBSERVED)
+           "worst_slice": {w: dm.worst_slice(r["grads"], ref["grads"], slices) for w, r in runs.items()}}
+    rec.update({"yardstick": yardstick(), "bars": bars()} if figures is None else figures)
+    dm.observe(rec, observed)
     return rec
 
 
-def judge(label, got, ref):
+def judge(label, got, ref, bar=None, slices=grad_slices, wider=None):
     """The assertions of a case, in this order: forward values within rtol 2e-4 / bars()["forward"] of the tensor's scale;
     a gradient that is identically zero in fp64 is exactly zero; every gradient within bars()["gradient"] of the tensor's
     scale (``check_grads``); every slice within bars()["slice"] of the SLICE's scale, and a slice that is identically zero
-    in fp64 exactly zero (``dm.check_slices``).  Returns (worst slice error, "name[slice]")."""
+    in fp64 exactly zero (``dm.check_slices``).  Returns (worst slice error, "name[slice]").  ``bar`` and ``slices``
+    replace this family's; ``wider`` {gradient name: bar} holds the named tensors, whole and per slice, to their own bar."""
     from conftest import check_grads
-    bar = bars()
+    bar, wider = bars() if bar is None else bar, wider or {}
     assert set(got["tensors"]) == set(ref["tensors"]), sorted(set(got["tensors"]) ^ set(ref["tensors"]))
     for n, r in ref["tensors"].items():
         np.testing.assert_allclose(got["tensors"][n], r, rtol=FWD_RTOL, atol=bar["forward"] * max(1.0, float(np.abs(r).max())),
@@ -329,5 +331,9 @@ def judge(label, got, ref):
     for n, r in ref["grads"].items():
         if not r.any():
             assert not got["grads"][n].any(), f"{label}: {n} is zero in fp64 (no path from the loss), yet a gradient was written"
-    check_grads(label, got["grads"], ref["grads"].__getitem__, tol=bar["gradient"])
-    return dm.check_slices(label, got["grads"], ref["grads"], bar["slice"], slices=grad_slices, zero_tol=0.0)
+    check_grads(label, {n: g for n, g in got["grads"].items() if n not in wider}, ref["grads"].__getitem__, tol=bar["gradient"])
+    for n, tol in wider.items():
+        if n in got["grads"]:
+            check_grads(f"{label} {n}", {n: got["grads"][n]}, ref["grads"].__getitem__, tol=tol)
+    tol = {n: max(bar["slice"], wider.get(n, 0.0)) for n in ref["grads"]} if wider else bar["slice"]
+    return dm.check_slices(label, got["grads"], ref["grads"], tol, slices=slices, zero_tol=0.0)
