@@ -16,6 +16,9 @@ The reference steps one env through ``episodes`` episodes.  Here the episodes ar
 tensors are read from the sink's slabs through its row map.  The step at which the envs truncate is a host step of the
 stack, so ``nxt`` of an episode's last step is the final observation, not the observation of the autoreset.  On the CPU
 the same call runs the per-step loop over the stepper's CPU twin.
+
+``--env BurgersEnv-v0`` (``pdegym.burgers.ENV_ID``) takes the same route over a ``BurgersBatchedVecEnv`` (``co_act_span`` ->
+``bg_step_span`` -> ``bg_record``), on a GPU only: the Burgers stepper has no CPU twin and ``--device cpu`` is refused.
 """
 import argparse
 import json
@@ -73,19 +76,27 @@ def generate_dataset(env_id, episodes, config=None, device=None, seed=None, tier
     """``episodes`` complete episodes of a uniform random policy on ``env_id`` as a ``TensorDataset`` (module docstring);
     its ``tier`` attribute names the collection tier that ran ("kernel" or "loop").
 
-    ``config``: the env's config dict; ``device``: None / "cpu" for the stepper's CPU twin, "cuda" or "cuda:i" for that
-    GPU, where the tensors then stay; ``seed``: wave w seeds its envs' streams ``seed + first episode of w + i`` and its
+    ``env_id``: the KS env's id or ``pdegym.burgers.ENV_ID``; ``config``: the env's config dict; ``device``: None / "cpu"
+    for the stepper's CPU twin (KS only), "cuda" or "cuda:i" for that GPU, where the tensors then stay; ``seed``: wave w seeds its envs' streams ``seed + first episode of w + i`` and its
     action space ``seed + first episode of w``; ``tier="loop"`` forces the per-step loop.  ``make_envs(n)`` replaces the
     vector env (tests: short episodes and a short burn-in)."""
+    from pdegym import burgers
     from pdegym.kuramoto import ENV_ID, make_vec
     if tier not in (None, "loop"):
         raise ValueError(f"tier is {tier!r}: None or 'loop'")
-    if env_id != ENV_ID and make_envs is None:
+    if env_id not in (ENV_ID, burgers.ENV_ID) and make_envs is None:
         raise ValueError(f"{env_id!r}: the offline evaluation is built for {ENV_ID}")
     if int(episodes) < 1:
         raise ValueError(f"{episodes} episodes (at least 1)")
     device = torch.empty(0, device="cpu" if device is None else device).device
     ordinal = device.index if device.type == "cuda" else -1
+    if env_id == burgers.ENV_ID and make_envs is None:
+        # the Burgers stepper has no CPU twin: its vector env lives on a GPU
+        if device.type != "cuda":
+            raise ValueError(f"{burgers.ENV_ID}: device={device.type!r} is refused, the Burgers stepper runs on a GPU only "
+                             f"(device='cuda' or 'cuda:i')")
+        ordinal = torch.cuda.current_device() if device.index is None else device.index
+        make_vec = burgers.make_vec
     if make_envs is None:
         make_envs = lambda n: make_vec(n, config=dict(config or {}), device=ordinal)
     waves, tiers = [], set()

@@ -19,6 +19,7 @@ How the reference's caller reaches the fast paths (``pl.Trainer.fit``, pdecontro
     ``hipGraphLaunch``).  The optimizer returned by ``configure_optimizers`` then only carries the learning rate
     (schedulers keep working: the graph reads it from a device scalar); its ``step`` is never called.
 """
+import collections
 import os
 from typing import Callable
 
@@ -29,6 +30,11 @@ from pdecontrol._compat.lightning import pl
 from pdecontrol.mbrl.types import ModelRollout
 from pdecontrol.surrogates.surrogate import AutoRegPDESurrogate, LatentAutoRegPDESurrogate, PDESurrogate
 from pdegym.common.transforms import BatchTransform, Identity, SampleTransform
+
+
+# what _test_kernel_plan hands to _test_metrics_device: the inverse observation map (kind, device coefficients or None),
+# the family ("ks" / "burgers") and the env that launches, and the sizes and names of what its two launches write
+_TestPlan = collections.namedtuple("_TestPlan", "kind coef family backend row_stats tables names")
 
 
 class _GraphOwnedAdam(torch.optim.Adam):
@@ -441,10 +447,22 @@ class PDETrainingModule(pl.LightningModule):
                 "actions": actions.detach(), "states": states.detach(), "outdeltas": outdeltas.detach(),
                 "deltas": deltas.detach()}
 
-    # -- test: the metric section on the device (ks_eval_rows_device / ks_eval_fold_device) -------------------
+    # -- test: the metric section on the device (ks_eval_rows_device / ks_eval_fold_device for a KS env, bg_eval_rows /
+    # bg_eval_fold for a Burgers env) ---------------------------------------------------------------------------------
+    def _burgers_backend(self, states):
+        """The ``BurgersBatchedVecEnv`` whose ``eval_rows_device`` / ``eval_fold_device`` take this batch: ``env`` itself
+        or the vector env behind a ``BurgersEnv``, on the states' grid and device; None for any other env."""
+        from pdegym.burgers import BurgersBatchedVecEnv, BurgersEnv
+        if not isinstance(self.env, (BurgersEnv, BurgersBatchedVecEnv)) or self.env.N != states.shape[3]:
+            return None
+        vec = self.env.vec if isinstance(self.env, BurgersEnv) else self.env
+        return vec if vec.device == states.device else None
+
     def _test_kernel_plan(self, states, out):
-        """(kind, device coefficients or None) of ``stransf.otransf.Inverse`` when the metric section of ``test_step``
-        runs as the two HIP launches; otherwise None, with a one-time notice that says why."""
+        """A ``_TestPlan`` -- (kind, device coefficients or None) of ``stransf.otransf.Inverse``, the backend that launches
+        (the KS env, whose reward handle does, or the Burgers vector env), its row-stat and table counts and its table
+        names -- when the metric section of ``test_step`` runs as the two HIP launches; otherwise None, with a one-time
+        notice that says why."""
         from pdecontrol.mbrl.recognition import Unrecognized, inverse_map, notice
         from pdecontrol.surrogates import ops
         from pdegym.kuramoto import KuramotoSivashinskyEnv
@@ -458,8 +476,12 @@ class PDETrainingModule(pl.LightningModule):
         if states.dtype != torch.float32 or states.dim() != 4 or states.shape[2] != 1:
             notice(sentence, f"states of shape {tuple(states.shape)} in {states.dtype} are not fp32 [B, T, 1, N]")
             return None
-        if not isinstance(self.env, KuramotoSivashinskyEnv) or self.env.N != states.shape[3]:
-            notice(sentence, f"the env is no KuramotoSivashinskyEnv on the states' grid of {states.shape[3]} points")
+        burgers = self._burgers_backend(states)
+        if burgers is None and (not isinstance(self.env, KuramotoSivashinskyEnv) or self.env.N != states.shape[3]):
+            if type(self.env).__name__ in ("BurgersEnv", "BurgersBatchedVecEnv"):
+                notice(sentence, f"the Burgers env is not on the states' grid of {states.shape[3]} points and on {states.device}")
+            else:
+                notice(sentence, f"the env is no KuramotoSivashinskyEnv on the states' grid of {states.shape[3]} points")
             return None
         pred = out.outputs
         if pred.dtype != torch.float32 or not pred.is_cuda or tuple(pred.shape) != tuple(states.shape):
@@ -470,12 +492,18 @@ class PDETrainingModule(pl.LightningModule):
         except (Unrecognized, NotImplementedError) as reason:
             notice(sentence, f"the inverse observation transform is {reason}")
             return None
+        if burgers is not None:
+            from pdegym.burgers import _hip as bg
+            backend = ("burgers", burgers, bg.EVAL_ROW_STATS, bg.EVAL_TABLES, bg.EVAL_TABLE_NAMES)
+        else:
+            import kspde
+            backend = ("ks", self.env, kspde.EVAL_ROW_STATS, kspde.EVAL_TABLES, kspde.EVAL_TABLE_NAMES)
         if coef is None:
-            return kind, None
+            return _TestPlan(kind, None, *backend)
         cached = self.__dict__.get("_test_inv_coef")
         if cached is None or cached[0] != states.device or cached[1].shape != coef.shape or not torch.equal(cached[1], coef):
             cached = self.__dict__["_test_inv_coef"] = (states.device, coef, coef.to(states.device))
-        return kind, cached[2]
+        return _TestPlan(kind, cached[2], *backend)
 
     @staticmethod
     def _rows(field):
@@ -487,40 +515,61 @@ class PDETrainingModule(pl.LightningModule):
         return field, field.stride(0), field.stride(1)
 
     def _test_metrics_device(self, states, actions, out, plan, accum=None, keep=True):
-        """The metric section of ``test_step`` for one batch on the device: two launches on the env's reward handle
-        (torch's current stream).  Returns (tables fp64 [1 + 25 T], inverse-scaled states, IC-augmented inverse-scaled
-        outputs), the last two None without ``keep``; ``accum`` is the epoch accumulator of ``ks_eval_fold_device``."""
-        import kspde
-        kind, coef = plan
+        """The metric section of ``test_step`` for one batch on the device: two launches of the plan's backend (the KS
+        env's reward handle, or the Burgers vector env) on torch's current stream.  Returns (tables fp64
+        [1 + plan.tables T], inverse-scaled states, IC-augmented inverse-scaled outputs), the last two None without
+        ``keep``; ``accum`` is the epoch accumulator of the fold launch: fp64, at least ``1 + plan.tables T`` long
+        (``test_surrogate`` sizes it for the KS backend's 25 tables; a backend with fewer writes the front of it and
+        ``_named_tables`` reads no further)."""
+        kind, coef = plan.kind, plan.coef
         b, t, _, n = states.shape
         dev = states.device
+        if accum is not None and (accum.dtype != torch.float64 or accum.numel() < 1 + plan.tables * t):
+            raise ValueError(f"the epoch accumulator holds {accum.numel()} {accum.dtype} values, the fold launch writes "
+                             f"{1 + plan.tables * t} doubles")
+        self.__dict__["_test_table_names"] = plan.names      # what _named_tables names an epoch's accumulator by
+        truth, truth_bs, truth_ts = self._rows(states.detach())
+        pred, pred_bs, pred_ts = self._rows(out.outputs.detach())
+        truth_out = torch.empty((b, t, 1, n), dtype=torch.float32, device=dev) if keep else None
+        pred_out = torch.empty((b, t, 1, n), dtype=torch.float32, device=dev) if keep else None
+        rowstats = torch.empty((b, t, plan.row_stats), dtype=torch.float64, device=dev)
+        tables = torch.empty(1 + plan.tables * t, dtype=torch.float64, device=dev)
+        ptr = lambda v: None if v is None else v.data_ptr()
+        d_accum = 0 if accum is None else accum.data_ptr()
+        # pred_shift: the prediction of step 0 is the initial condition, of step t >= 1 the rollout's output t - 1
+        if plan.family == "burgers":
+            from pdegym.burgers import _hip as bg
+            desc = bg.EvalBatch(ptr(truth), truth_bs, truth_ts, ptr(pred), pred_bs, pred_ts, 1, kind, ptr(coef),
+                                ptr(truth_out), ptr(pred_out))
+            plan.backend.eval_rows_device(desc, b, t, rowstats.data_ptr())
+            plan.backend.eval_fold_device(rowstats.data_ptr(), b, t, tables.data_ptr(), d_accum)
+            return tables, truth_out, pred_out
+        import kspde
         objective = self.env.step_objective
         phi = None
         if objective == "dissipation":
             flat = actions.reshape(b * t, *actions.shape[2:])
             phi = BatchTransform(self.env.forcing)(self.stransf.atransf.Inverse(flat))
             phi = phi.to(torch.float32).reshape(b * t, n).contiguous()
-        truth, truth_bs, truth_ts = self._rows(states.detach())
-        pred, pred_bs, pred_ts = self._rows(out.outputs.detach())
-        truth_out = torch.empty((b, t, 1, n), dtype=torch.float32, device=dev) if keep else None
-        pred_out = torch.empty((b, t, 1, n), dtype=torch.float32, device=dev) if keep else None
-        rowstats = torch.empty((b, t, kspde.EVAL_ROW_STATS), dtype=torch.float64, device=dev)
-        tables = torch.empty(1 + kspde.EVAL_TABLES * t, dtype=torch.float64, device=dev)
-        ptr = lambda v: None if v is None else v.data_ptr()
-        # pred_shift: the prediction of step 0 is the initial condition, of step t >= 1 the rollout's output t - 1
         desc = kspde.ks_eval_batch(ptr(truth), truth_bs, truth_ts, ptr(pred), pred_bs, pred_ts, 1, ptr(phi), kind, ptr(coef),
                                    ptr(truth_out), ptr(pred_out))
-        handle = self.env._reward_handle(dev)
+        handle = plan.backend._reward_handle(dev)
         handle.eval_rows_device(objective, desc, b, t, rowstats.data_ptr())
-        handle.eval_fold_device(rowstats.data_ptr(), b, t, tables.data_ptr(), 0 if accum is None else accum.data_ptr())
+        handle.eval_fold_device(rowstats.data_ptr(), b, t, tables.data_ptr(), d_accum)
         return tables, truth_out, pred_out
 
-    @staticmethod
-    def _named_tables(values, steps):
-        """fp64 [1 + 25 T] host values of ``ks_eval_fold_device`` as the reference's keys."""
-        import kspde
+    def _named_tables(self, values, steps, names=None):
+        """fp64 host values of the fold launch (the MSE, then ``[T]`` per table; anything behind the last table is not
+        read) as the reference's keys.  ``names``: the plan's; None: those of the plan ``_test_metrics_device`` last ran,
+        which is how ``test_surrogate`` names its accumulator at the end of an epoch."""
+        if names is None:
+            names = self.__dict__.get("_test_table_names")
+            if names is None:
+                import kspde
+                names = kspde.EVAL_TABLE_NAMES
+        assert len(values) >= 1 + len(names) * steps, (len(values), len(names), steps)
         named = {"MSE": values[0]}
-        for k, name in enumerate(kspde.EVAL_TABLE_NAMES):
+        for k, name in enumerate(names):
             named[name] = values[1 + k * steps:1 + (k + 1) * steps]
         return named
 
@@ -533,7 +582,7 @@ class PDETrainingModule(pl.LightningModule):
             return self._test_step_host(states, actions, out)
         self.last_test_tier = "kernel"
         tables, truth, pred = self._test_metrics_device(states, actions, out, plan)
-        named = self._named_tables(tables.cpu().numpy(), states.shape[1])
+        named = self._named_tables(tables.cpu().numpy(), states.shape[1], plan.names)
         data = {name: np.asarray(value, dtype=np.float32) for name, value in named.items()}
         data.update({"states": truth.cpu().numpy(), "outputs": pred.cpu().numpy(), "actions": actions.detach().cpu().numpy()})
         return data
@@ -571,8 +620,8 @@ class PDETrainingModule(pl.LightningModule):
         # spatial derivatives (env.rhs) of true vs predicted states.  The reference calls env.rhs once per sample
         # (training.py:237-245); the HIP rhs hook is row-parallel, so all B*T samples go in ONE call (same values)
         def derivatives(vals):
-            _, (ux, uxx, uxxxx) = self.env.rhs(vals.numpy(), phi.numpy())
-            d = torch.as_tensor(np.stack([ux, uxx, uxxxx], axis=1))            # [B*T, 3, C, H]
+            _, each = self.env.rhs(vals.numpy(), phi.numpy())                  # (ux, uxx, uxxxx); (ux, uxx) on Burgers
+            d = torch.as_tensor(np.stack(list(each), axis=1))                  # [B*T, 3, C, H]
             return d.reshape(b, t, *d.shape[1:])
         dv, pdv = derivatives(flat(states, sc, sh)), derivatives(flat(outputs, sc, sh))
         d1, n1 = torch.norm(dv - pdv, p=1, dim=4), torch.norm(dv, p=1, dim=4)

@@ -1,6 +1,7 @@
 """Burgers environments: the module the reference's ``pdegym/__init__.py:2`` imports and does not
 ship.  Registers ``BurgersEnv-v0``; ``make_vec`` builds the batched HIP vector env."""
 from pdegym._gym import gym
+from pdegym.burgers._hip import EVAL_ROW_STATS, EVAL_TABLE_NAMES, EVAL_TABLES  # noqa: F401  (the test phase's sizes and names)
 from pdegym.burgers.burgers import BurgersBatchedVecEnv, BurgersEnv
 
 TimeLimit = gym.wrappers.TimeLimit

@@ -164,6 +164,46 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
                                          _ptr(out)))
         return out
 
+    def derivatives(self, u):
+        """(u_x, u_xx) of fp32 rows [M, N] on the device, fp64 device tensors [M, N]: ``bg_derivatives``, the stencils of
+        the stepper taken in fp64 from the widened values."""
+        u = torch.as_tensor(u, dtype=torch.float32, device=self.device).contiguous()
+        ux, uxx = (torch.empty(u.shape, dtype=torch.float64, device=self.device) for _ in range(2))
+        _hip.check_eval(self._lib.bg_derivatives(_stream(self.device), _ptr(u), u.shape[0], u.shape[1], self.dx, _ptr(ux),
+                                                 _ptr(uxx)))
+        return ux, uxx
+
+    def rhs(self, u, phi=None):
+        """``(residual, (u_x, u_xx))`` of numpy or tensor rows ``[..., N]``, as ``KuramotoSivashinskyEnv.rhs`` hands them to
+        ``test_step``'s host lines: numpy arrays of the input's shape, the residual fp32 (``bg_residual``), the
+        derivatives fp64 (``bg_derivatives``)."""
+        host = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        rows = np.ascontiguousarray(host(u), dtype=np.float32)
+        shape = rows.shape
+        if not shape or shape[-1] != self.N:
+            raise ValueError(f"rhs takes rows of {self.N} points, not an array of shape {shape}")
+        flat = torch.from_numpy(rows.reshape(-1, self.N)).to(self.device)
+        phi_t = None
+        if phi is not None:
+            phi_rows = np.array(np.broadcast_to(np.asarray(host(phi), dtype=np.float32), shape), order="C")
+            phi_t = torch.from_numpy(phi_rows.reshape(-1, self.N)).to(self.device)
+        res = self.residual(flat, phi_t)
+        ux, uxx = self.derivatives(flat)
+        return res.cpu().numpy().reshape(shape), (ux.cpu().numpy().reshape(shape), uxx.cpu().numpy().reshape(shape))
+
+    # -- test phase: the metric section of PDETrainingModule.test_step (include/burgers/eval.h) ---------------------
+    def eval_rows_device(self, batch, B, T, d_rowstats):
+        """The 14 fp64 sums of every (b, t) row of a test batch (``batch`` an ``_hip.EvalBatch`` of raw device pointers)
+        into ``d_rowstats`` [B, T, 14]; see ``bg_eval_rows``.  Enqueued on torch's current stream of the env's device."""
+        _hip.check_eval(self._lib.bg_eval_rows(_stream(self.device), None if batch is None else _hip.ctypes.byref(batch),
+                                               int(B), int(T), self.N, self.dx, _void_p(d_rowstats)))
+
+    def eval_fold_device(self, d_rowstats, B, T, d_tables, d_accum=0):
+        """``d_rowstats`` [B, T, 14] folded into the MSE and the 20 per-step tables, ``d_tables`` [1 + 20 T], and
+        ``d_accum`` (same shape, 0 = NULL) += B * tables; see ``bg_eval_fold``.  Enqueued on torch's current stream."""
+        _hip.check_eval(self._lib.bg_eval_fold(_stream(self.device), _void_p(d_rowstats), int(B), int(T), self.N,
+                                               _void_p(d_tables), _void_p(d_accum)))
+
     # -- gym.vector API ---------------------------------------------------------------------------------------------
     def reset_wait(self, seed=None, return_info: bool = False, options=None, **kwargs):
         if seed is None:
@@ -228,7 +268,8 @@ class BurgersEnv(gym.Env):
         return self._vec
 
     def __getattr__(self, name):
-        if name in ("forcing", "reward_func", "scenario", "dx", "x", "nu", "batched_reward_func"):
+        if name in ("forcing", "reward_func", "scenario", "dx", "x", "nu", "batched_reward_func", "rhs", "derivatives",
+                    "eval_rows_device", "eval_fold_device"):
             return getattr(self.vec, name)
         raise AttributeError(name)
 
