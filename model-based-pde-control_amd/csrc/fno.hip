@@ -1,5 +1,6 @@
 // fno.hip -- one launch per FNO model evaluation (forward) and one per evaluation (backward) for gfx950; part of
-// libspectral_hip.so (C ABI: include/spectral_hip.h, fno_*, and, for fno_forward_select, include/spectral/forward_select.h).
+// libspectral_hip.so (C ABI: include/spectral_hip.h, fno_*, and, for fno_forward_select, include/spectral/forward_select.h;
+// for fno_forward_chain, include/spectral/forward_chain.h).
 //
 // The FNO-style surrogate of BASELINE configs[4] (pdecontrol/architectures/fno.py: lift -> 4 x [spectral convolution +
 // pointwise convolution, GELU] -> project) has no counterpart in the reference (parity unpinned); what IS fixed
@@ -23,11 +24,13 @@
 // fp32 throughout, v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains).
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <map>
 #include <mutex>
 #include <utility>
 
+#include "../../include/spectral/forward_chain.h"
 #include "../../include/spectral/forward_select.h"
 #include "../../include/spectral_hip.h"
 #include "capi_error.h"
@@ -521,6 +524,131 @@ __global__ void __launch_bounds__(TPB) fno_forward_select_kernel(const SelectArg
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// all free-running steps of a rollout (fno_forward_chain)
+// ------------------------------------------------------------------------------------------------------------------
+// A free-running step reads the row the step before wrote, so fno_forward needs one launch per step: each of them copies
+// the 32 x N twiddle matrix into LDS again and ends at a launch boundary.  Here workgroup b walks all `steps` steps of
+// sample b: the table is loaded once, and the base row of the next step stays in LDS (Lds::gv, N floats the forward walk
+// does not use).  The project stage reads base[pos] and writes the new base[pos] from the SAME thread (one wave owns a
+// position tile), so the row is updated in place with no reader left behind; the barrier that ends a step orders that
+// write, and the last reads of xs / wps / misc, before the next step's lift.  Nothing is read back from global memory,
+// so no fence is needed, and there are no atomics.
+//
+// Each step is fno_forward_kernel<false>'s walk, statement for statement, on the shared device functions, so delta[k]
+// and out[k] are the bytes of `steps` fno_forward launches (tests/test_fno_chain_gpu.py).  Its own spelling, as the
+// select kernel has and for the same reason (profiles/fno_chain_kernel_resources.txt).
+struct ChainArgs {
+    Weights w;
+    const float* u0;        // [nb][N] rows at u0_stride_b: the base of step 0
+    long u0_stride_b;
+    Rows act;               // [steps][nb][N] view
+    float* delta;           // [steps][nb][N]
+    float* out;             // [steps][nb][N]
+    const float* tabg;      // [32][N] twiddle matrix (global, per device and N)
+    int n, nb, steps;
+    float cscale, cshift;
+};
+
+__global__ void __launch_bounds__(TPB) fno_forward_chain_kernel(const ChainArgs a) {
+    extern __shared__ __align__(16) float lds_raw[];
+    const int N = a.n;
+    const Lds L(lds_raw, N);
+    const int NP = L.NP;
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int r = lane & 15, q = lane >> 4;
+    float* base = L.gv;                                              // the row this step starts from; the next one after it
+
+    {
+        const float* u0 = a.u0 + b * a.u0_stride_b;
+        for (int n = threadIdx.x; n < N; n += blockDim.x) base[n] = u0[n];
+    }
+    load_table(L.tb, a.tabg, N, NP);
+    __syncthreads();
+
+    const float s0 = 1.0f / (float)N, s1 = 2.0f / (float)N;
+    for (int k = 0; k < a.steps; ++k) {
+        const size_t p = (size_t)k * a.nb + b;
+        lift_into(L.xs, base, a.act.row(k, b), a.w, N, NP);
+        __syncthreads();
+        for (int l = 0; l < LAYERS; ++l) {
+            // ---- A: truncated DFT of the layer input; the pointwise weights ride along -----------------------------
+            MixRegs mw;
+            mix_load<false>(a.w.wr[l], a.w.wi[l], mw);
+            contract_n(L.xs, L.tb, L.S, N, NP);
+            load_mat(L.wps, a.w.pw[l]);
+            if (threadIdx.x < C) L.misc[threadIdx.x] = a.w.pb[l][threadIdx.x];
+            __syncthreads();
+            // ---- B: complex mode mixing ----------------------------------------------------------------------------
+            mix_compute<false>(mw, L.S, L.Z, s0, s1);
+            __syncthreads();
+            // ---- C: pre = iDFT(Z) + Wp x + b, position tile by position tile, in place ------------------------------
+            for (int ct = wave; ct < (N >> 4); ct += nwaves) {
+                const int pos = 16 * ct + r;
+                f32x4 acc[2][2];
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) {
+                    acc[rt][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    acc[rt][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const float* zrow = L.Z + (16 * rt + r) * KP;
+                    const float* wrow = L.wps + (16 * rt + r) * KP;
+#pragma unroll
+                    for (int k0 = 0; k0 < K2; k0 += 4) {
+                        acc[rt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(zrow[k0 + q], L.tb[(k0 + q) * NP + pos], acc[rt][0], 0, 0, 0);
+                        acc[rt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[k0 + q], L.xs[(k0 + q) * NP + pos], acc[rt][1], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int row = 16 * rt + 4 * q + j;
+                        const float v = (acc[rt][0][j] + acc[rt][1][j]) + L.misc[row];
+                        L.xs[row * NP + pos] = l + 1 < LAYERS ? gelu(v) : v;
+                    }
+            }
+            __syncthreads();
+        }
+
+        // ---- project: delta = p2 . gelu(p1 h + b1) + b2;  out = base + cscale * delta + cshift ----------------------
+        load_mat(L.wps, a.w.p1_w);
+        if (threadIdx.x < C) {
+            L.misc[threadIdx.x] = a.w.p1_b[threadIdx.x];
+            L.misc[C + threadIdx.x] = a.w.p2_w[threadIdx.x];
+        }
+        __syncthreads();
+        const float b2 = a.w.p2_b[0];
+        for (int ct = wave; ct < (N >> 4); ct += nwaves) {
+            const int pos = 16 * ct + r;
+            float part = 0.0f;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                const float* wrow = L.wps + (16 * rt + r) * KP;
+#pragma unroll
+                for (int k0 = 0; k0 < C; k0 += 4)
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[k0 + q], L.xs[(k0 + q) * NP + pos], acc, 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int row = 16 * rt + 4 * q + j;
+                    part = fmaf(L.misc[C + row], gelu(acc[j] + L.misc[row]), part);
+                }
+            }
+            part += __shfl_xor(part, 16, 64);
+            part += __shfl_xor(part, 32, 64);
+            if (q == 0) {
+                const float d = part + b2;
+                const float o = fmaf(a.cscale, d, base[pos]) + a.cshift;
+                a.delta[p * N + pos] = d;
+                a.out[p * N + pos] = o;
+                base[pos] = o;                                       // read above by this thread and by no other
+            }
+        }
+        __syncthreads();        // the new base row is complete; xs, wps and misc are free for the next step
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------
 // rowsum[row] = sum_n buf[row][n] * (v ? v[n] : 1), 16 threads per row (512 threads = 32 rows)
@@ -1006,6 +1134,48 @@ int fno_forward_select(void* stream, int width, int modes, int layers, int n, in
     k.tabg = twiddle_table(who, n, (hipStream_t)stream, &trc);
     if (!k.tabg) return trc;
     return launch(fno_forward_select_kernel, who, stream, nb, n, k);
+}
+
+int fno_forward_chain(void* stream, int width, int modes, int layers, int n, int nb, const fno_chain_args* a) {
+    const char* who = "fno_forward_chain";
+    if (!a || !a->u0 || !a->act || !a->delta || !a->out)
+        return fail(-1, "%s: NULL argument, state, action, delta or output pointer", who);
+    if (!complete(a->w)) return fail(-1, "%s: an incomplete set of weights", who);
+    if (a->steps < 1) return fail(-1, "%s: %d steps (at least 1)", who, a->steps);
+    if (nb < 1) return fail(-1, "%s: a batch of %d samples (at least 1)", who, nb);
+    if ((nb > 1 && (a->u0_stride_b < n || a->a_stride_b < n)) || (a->steps > 1 && a->a_stride_t < n))
+        return fail(-1, "%s: strides %ld (state rows), %ld / %ld (action steps / rows) are smaller than a row of %d floats", who,
+                    a->u0_stride_b, a->a_stride_t, a->a_stride_b, n);
+    // byte ranges [lo, hi) of the four tensors (strides of an axis that is not walked do not count); the outputs must not
+    // share a byte with an input or with each other
+    struct Span {
+        uintptr_t lo, hi;
+        bool meets(const Span& o) const { return lo < o.hi && o.lo < hi; }
+    };
+    const auto span = [](const float* p, long floats) { return Span{(uintptr_t)p, (uintptr_t)p + sizeof(float) * (uintptr_t)floats}; };
+    const long whole = (long)a->steps * nb * n;
+    const long ub = nb > 1 ? a->u0_stride_b : 0, ab = nb > 1 ? a->a_stride_b : 0, at = a->steps > 1 ? a->a_stride_t : 0;
+    const Span su = span(a->u0, (nb - 1) * ub + n), sa = span(a->act, (a->steps - 1) * at + (nb - 1) * ab + n);
+    const Span sd = span(a->delta, whole), so = span(a->out, whole);
+    if (so.meets(su) || so.meets(sa) || sd.meets(su) || sd.meets(sa) || so.meets(sd))
+        return fail(-1, "%s: delta and out must not overlap the state, the actions or each other", who);
+    if (int rc = check(who, n, nb, nb, width, modes, layers)) return rc;
+    ChainArgs k = {};
+    k.w = weights_of(a->w);
+    k.u0 = a->u0;
+    k.u0_stride_b = ub;
+    k.act = Rows{a->act, at, ab};
+    k.delta = a->delta;
+    k.out = a->out;
+    k.n = n;
+    k.nb = nb;
+    k.steps = a->steps;
+    k.cscale = a->cscale;
+    k.cshift = a->cshift;
+    int trc = 0;
+    k.tabg = twiddle_table(who, n, (hipStream_t)stream, &trc);
+    if (!k.tabg) return trc;
+    return launch(fno_forward_chain_kernel, who, stream, nb, n, k);
 }
 
 int fno_backward(void* stream, const fno_weights* w, int width, int modes, int layers, int n, int nb, int pairs, const float* u,

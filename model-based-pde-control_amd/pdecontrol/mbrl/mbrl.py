@@ -20,7 +20,8 @@ Keyword-only extensions of the constructor, all optional:
                  reads ``wandb.run.summary``; evaluation episodes go to ``<log.dir>/evaluation/eval_{iteration}.npz``
     make_env     factory of the single env (spaces, forcing, reward function, scenario); default ``gym.make(env_id)``
     make_envs    factory ``n -> vector env`` of ``n`` envs; default for the KS id a ``KSBatchedVecEnv`` on the GPU with
-                 ``args.cuda`` and on the stepper's CPU twin otherwise, else ``gym.vector.make``
+                 ``args.cuda`` and on the stepper's CPU twin otherwise, for the Burgers id (``pdegym.burgers.ENV_ID``) a
+                 ``BurgersBatchedVecEnv`` on the GPU (refused without ``args.cuda``: no CPU twin), else ``gym.vector.make``
     env_config   dict for the default factories
     phase_tiers  "kernel" (default): every phase through its phase call, which picks its tier; "loop": the loop each
                  phase replaces (``Worker.rollout`` for the collection and the world rollouts, the reference's expression
@@ -172,19 +173,34 @@ class PDEModelBasedController:
         config.setdefault("device", 0 if self.device.type == "cuda" else -1)
         return config
 
+    def _burgers_config(self):
+        """The env config of the Burgers id.  Its stepper has no CPU twin, so the default factories refuse it without
+        ``args.cuda``, by name, as ``generate_dataset`` refuses ``device="cpu"``."""
+        from pdegym import burgers
+        if self.device.type != "cuda":
+            raise ValueError(f"{burgers.ENV_ID}: a controller without args.cuda is refused, the Burgers stepper runs on a GPU "
+                             f"only (set cuda, or pass make_env / make_envs)")
+        return dict(self.env_config)
+
     def _default_env(self):
+        from pdegym import burgers
         from pdegym._gym import gym
         from pdegym.kuramoto import ENV_ID
         if self.env_id == ENV_ID:
             return gym.make(self.env_id, config=self._stepper_config())
+        if self.env_id == burgers.ENV_ID:
+            return burgers.make(config=self._burgers_config())
         return gym.make(self.env_id, **self.env_config)
 
     def _default_envs(self, n):
+        from pdegym import burgers
         from pdegym._gym import gym
         from pdegym.kuramoto import ENV_ID, make_vec
         if self.env_id == ENV_ID:
             config = self._stepper_config()
             return make_vec(n, config=config, device=config.pop("device"))
+        if self.env_id == burgers.ENV_ID:
+            return burgers.make_vec(n, config=self._burgers_config(), device=0)
         return gym.vector.make(self.env_id, num_envs=n, **self.env_config)
 
     # -- set-up ----------------------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@ call that needs no pytorch-lightning.
 Two tiers.  The kernel tier keeps the phase in HBM: per loader one ``locate_many`` and one upload of the windows' first
 rows; per training step one ``sur_gather_windows`` launch straight into the static buffers of the captured TBPTT step
 (``GraphedTBPTTStep``) and one replay; per validation batch one gather into time-major storage, the fused rollout on its
-``[B, T, 1, N]`` view and one ``sur_val_loss`` launch into the epoch's device accumulator; per validation epoch one small
+``[B, T, 1, N]`` view (for an FNO with ``PDECONTROL_FNO_CHAIN=1``: the teacher-forced launch and one
+``fno_forward_chain``) and one ``sur_val_loss`` launch into the epoch's device accumulator; per validation epoch one small
 device-to-host copy, the only synchronisation besides graph capture.
 The loop tier runs the same rule over the datamodule's own loaders, for everything the kernel tier does not take, and
 says so once per reason (``recognition.notice``).
@@ -52,6 +53,19 @@ def _fused_step_ok(module):
     return module.device.type == "cuda" and callable(getattr(module, "fused_step", None)) and callable(frozen) and not frozen()
 
 
+def _fno_refusal(surrogate, n, na):
+    """Why the kernel tier does not take the FNO ``surrogate`` over gathered state rows of ``n`` and action rows of ``na``
+    columns, or None: the whole-network kernels' geometry and an affine ``dscaling`` (``fno_hip.world_supported``), and an
+    action field on the state's grid."""
+    from pdecontrol.surrogates import fno_hip
+    if not fno_hip.world_supported(surrogate, n):
+        return (f"an FNO the whole-network kernels do not take at a state row of {n} points (width {fno_hip.WIDTH}, "
+                f"{fno_hip.MODES} modes, {fno_hip.LAYERS} layers, a power of two in [64, 512] points, an affine dscaling)")
+    if na != n:
+        return f"an action row of {na} columns beside a state row of {n}: the FNO reads the action field at every grid point"
+    return None
+
+
 class _KernelTier:
     """The gather of one call: the store's fields, the recognised connector, the uploaded tables."""
 
@@ -59,6 +73,7 @@ class _KernelTier:
         from pdecontrol.surrogates import hipops, ops
         from pdecontrol.surrogates.common.dataset import device_store
         from pdecontrol.surrogates.surrogate import AutoRegPDESurrogate
+        from pdecontrol.architectures.fno import FNOAutoRegSurrogate
         device = module.device
         if device.type != "cuda":
             raise Unrecognized("a module that is not on a GPU")
@@ -68,7 +83,10 @@ class _KernelTier:
                                                                           "_fused_validation_loss")):
             raise Unrecognized(f"a {type(module).__name__} without the captured TBPTT step of PDETrainingModule")
         surrogate = getattr(module, "surrogate", None)
-        if hipops.fused_latent_supported(surrogate):
+        fno = isinstance(surrogate, FNOAutoRegSurrogate)
+        if fno:
+            pass        # the whole-network FNO kernels: their geometry is checked below, at the gather's row widths
+        elif hipops.fused_latent_supported(surrogate):
             # the latent ConvLSTM: the captured decoded-mode step, on the conditions of PDETrainingModule._latent_training_step
             constants = getattr(module, "_latent_constants", None)
             if not callable(constants) or constants() is None:
@@ -95,12 +113,18 @@ class _KernelTier:
         if obs.dim() != 3 or obs.shape[1] != 1 or actions.dim() != 3 or actions.shape[1] != 1:
             raise Unrecognized(f"fields of shape {tuple(obs.shape[1:])} and {tuple(actions.shape[1:])} (one channel each)")
         obs_map, act_maps = world_connector(datamodule.stransf, obs.shape[2], actions.shape[2])
+        if fno:
+            reason = _fno_refusal(surrogate, obs_map.width, act_maps[2].width)
+            if reason is not None:
+                raise Unrecognized(reason)
         self.gather = hipops.WindowGather(obs, actions, rowmap, store.total, obs_map, act_maps)
         reason = self.gather.refused()
         if reason is not None:
             raise Unrecognized(reason)
         self.store, self.device = store, device
         self.widths = (obs_map.width, act_maps[2].width)
+        # the phase asks for sur_val_loss over the FNO rollout's time-major storage; validation_step on its own does not
+        self.loss_keywords = {"fno": True} if fno else {}
         self._val_buffers = {}
 
     def plan(self, loader):
@@ -181,7 +205,8 @@ def _validate_kernel(module, tier, loader, batch_size):
             b = min(batch_size, n - i0)
             states, actions = tier.val_buffers(b, l)
             tier.gather(first, i0, b, l, states, actions)
-            fused = module._fused_validation_loss(module._full_rollout(states, actions), states, accum=accum, outputs=False)
+            fused = module._fused_validation_loss(module._full_rollout(states, actions), states, accum=accum, outputs=False,
+                                                  **tier.loss_keywords)
             if fused is not None:
                 fused_samples += b
                 continue
@@ -292,7 +317,9 @@ def update_surrogate(module, datamodule, fit, *, max_steps, min_steps, patience,
     follows ``configure_optimizers``' ``StepLR`` over ``fit.current_epoch``.
 
     The kernel tier applies when the module is on CUDA, the fused kernels are enabled, ``fused_step`` accepts the module
-    (the fused TBPTT architecture, or the latent ConvLSTM under ``PDETrainingModule._latent_constants``; nothing frozen),
+    (the fused TBPTT architecture, the latent ConvLSTM under ``PDETrainingModule._latent_constants``, or an
+    ``FNOAutoRegSurrogate`` that ``fno_hip.world_supported`` takes at the gather's state width, with an action row as wide
+    as the state row; nothing frozen),
     there is a single process, the datamodule has ``device_data`` on that
     device, ``recognition.world_connector`` recognises ``datamodule.stransf`` and ``sur_gather_windows`` does not refuse
     the geometry.  Everything else runs on the loop tier over the datamodule's own loaders: ``fused_step`` on CUDA where

@@ -1,12 +1,14 @@
 """Whole-network FNO kernels behind ``FNOAutoRegSurrogate.rollout`` (C ABI: include/spectral_hip.h ``fno_*`` and, for the
-member-select forward of the imagined step, include/spectral/forward_select.h; kernels: csrc/fno.hip) -- SURVEY 8(f) row f4,
-BASELINE configs[4].
+member-select forward of the imagined step, include/spectral/forward_select.h, for the free-running chain,
+include/spectral/forward_chain.h; kernels: csrc/fno.hip) -- SURVEY 8(f) row f4, BASELINE configs[4].
 
 The rollout contract is the reference's (pdecontrol/surrogates/surrogate.py:79-133): teacher forced on the given states,
 free running afterwards, ``next = prev + delta * dscaling(model(prev, action))``.  Here a rollout of K steps is
 
   forward   ONE launch for all teacher-forced steps (n_given x B independent (step, sample) pairs), then one launch per
-            free-running step (B pairs; the recurrence is the only sequential part);
+            free-running step (B pairs; the recurrence is the only sequential part) -- or, when nobody will ask for a
+            gradient and ``PDECONTROL_FNO_CHAIN=1``, ONE ``fno_forward_chain`` launch for all free-running steps (the same
+            bytes; ``chain_enabled``);
   backward  the same launches in reverse (the gradient with respect to a step's starting state is handed to the step
             that predicted it), then ONE reduction of the per-pair parameter-gradient rows and ONE contraction of the
             saved spectra into the spectral weight gradients.
@@ -18,6 +20,7 @@ reference-side pin for any of this (the reference has no FNO): the kernels are p
 (tests/test_fno.py).
 """
 import ctypes
+import os
 
 import torch
 
@@ -56,6 +59,18 @@ class FnoSelectArgs(ctypes.Structure):
 SELECT_SYMBOLS = (
     ("fno_forward_select", _i, [_p, _i, _i, _i, _i, _i, ctypes.POINTER(FnoSelectArgs)]),
 )
+
+
+class FnoChainArgs(ctypes.Structure):
+    """``fno_chain_args`` of include/spectral/forward_chain.h"""
+    _fields_ = [("w", _WP), ("cscale", _f), ("cshift", _f), ("u0", _p), ("u0_stride_b", _l), ("act", _p), ("a_stride_t", _l),
+                ("a_stride_b", _l), ("delta", _p), ("out", _p), ("steps", _i)]
+
+
+# include/spectral/forward_chain.h, the same library (tests/test_fno_chain_host.py)
+CHAIN_SYMBOLS = (
+    ("fno_forward_chain", _i, [_p, _i, _i, _i, _i, _i, ctypes.POINTER(FnoChainArgs)]),
+)
 _lib = None
 
 
@@ -67,7 +82,7 @@ def load():
     global _lib
     if _lib is None:
         # same shared library; raises when it has not been built
-        _lib = hipbind.type_symbols(spectral.load(), SYMBOLS + SELECT_SYMBOLS)
+        _lib = hipbind.type_symbols(spectral.load(), SYMBOLS + SELECT_SYMBOLS + CHAIN_SYMBOLS)
     return _lib
 
 
@@ -153,6 +168,20 @@ def forward_select(stream, n, nb, args):
     _check(load().fno_forward_select(stream, WIDTH, MODES, LAYERS, int(n), int(nb), ctypes.byref(args)))
 
 
+def chain_enabled():
+    """``PDECONTROL_FNO_CHAIN=1`` sends the free-running steps of an inference rollout through ``fno_forward_chain``; unset or
+    ``0`` keeps one ``fno_forward`` launch per step.  The chain is off by default: on an MI355X it saves 0.03 ms of a 2.4 ms
+    rollout (N = 512, B = 128, T = 35) and of a 1.3 ms one (B = 64, T = 20), which is inside the spread of the rounds
+    (profiles/fno_chain_bench.json).  The bytes are the same either way (tests/test_fno_chain_gpu.py)."""
+    return os.environ.get("PDECONTROL_FNO_CHAIN", "0") == "1"
+
+
+def forward_chain(stream, n, nb, args):
+    """One ``fno_forward_chain`` launch on ``stream`` (a raw hipStream_t): ``args.steps`` free-running steps of ``nb``
+    samples, ``args.delta`` / ``args.out`` time major."""
+    _check(load().fno_forward_chain(stream, WIDTH, MODES, LAYERS, int(n), int(nb), ctypes.byref(args)))
+
+
 def _launch_groups(n_given, K):
     """(first step, steps) per launch: all teacher-forced steps at once, then one free-running step at a time."""
     return [(0, n_given)] + [(k, 1) for k in range(n_given, K)]
@@ -165,7 +194,10 @@ def _forward_launches(lib, w, states, acts, n_given, cscale, cshift, deltas, out
     B, K, N = acts.shape[0], acts.shape[1], acts.shape[-1]
     st = _stream()
     ast, asb = acts.stride(1), acts.stride(0)
-    for k0, cnt in _launch_groups(n_given, K):
+    groups = _launch_groups(n_given, K)
+    # inference with at least two free-running steps: the teacher-forced launch, then the whole chain in one
+    chain = pre is None and n_given >= 1 and K - n_given >= 2 and chain_enabled()
+    for k0, cnt in groups[:1] if chain else groups:
         if k0 < n_given:
             u_ptr, ust, usb = states.data_ptr(), states.stride(1), states.stride(0)
         else:                      # free running: the previous prediction
@@ -174,6 +206,11 @@ def _forward_launches(lib, w, states, acts, n_given, cscale, cshift, deltas, out
                                ctypes.c_void_p(acts.data_ptr() + 4 * k0 * ast), ast, asb, cscale, cshift,
                                _ptr(deltas[k0]), _ptr(outputs[k0]), _ptr(None if pre is None else pre[k0 * B:]), _ptr(xspec),
                                spec_pairs, pair0 + k0 * B))
+    if chain:
+        k0 = n_given                   # u0: the last teacher-forced prediction, the row just before out in ``outputs``
+        args = FnoChainArgs(ctypes.pointer(w), cscale, cshift, outputs[k0 - 1].data_ptr(), outputs.stride(1),
+                            acts.data_ptr() + 4 * k0 * ast, ast, asb, deltas[k0].data_ptr(), outputs[k0].data_ptr(), K - k0)
+        forward_chain(st, N, B, args)
 
 
 def _backward_launches(lib, w, states, acts, outputs, pre, n_given, cscale, g_deltas, gspec, spec_pairs, pair0, rows, gouts,
@@ -376,6 +413,14 @@ class _FNOTBPTTFn(torch.autograd.Function):
         return (None, None, None, None, None, None, *out)
 
 
+def _node_parameters(model):
+    """The parameter inputs of a rollout node.  With grad mode off nobody will ask for a gradient, but a node's
+    ``needs_input_grad`` still reports every input that requires one: the parameters go in detached, so that the forward
+    saves nothing and takes the inference launches (``fno_forward_chain`` among them).  The bytes are the same."""
+    params = parameters_of(model)
+    return params if torch.is_grad_enabled() else [p.detach() for p in params]
+
+
 def tbptt(surrogate, states, actions, tau, tbtt, grid):
     """(outputs [B, T, 1, N], deltas [B, T, 1, N], time-major deltas [T, B, 1, N]) of the training module's TBPTT pass on the
     whole-network kernels, or None when they do not cover this call.  ``grid(K)`` -> (times, targets) of a K-action chunk
@@ -406,7 +451,7 @@ def tbptt(surrogate, states, actions, tau, tbtt, grid):
     acts = actions if gidx == list(range(T)) else take_steps(actions, gidx)
     scale, shift = aff
     d, o = _FNOTBPTTFn.apply(states, acts, int(tau), int(tbtt), float(surrogate.delta) * scale, float(surrogate.delta) * shift,
-                             *parameters_of(model))
+                             *_node_parameters(model))
     return o.transpose(0, 1).unsqueeze(2), d.transpose(0, 1).unsqueeze(2), d.unsqueeze(2)
 
 
@@ -422,5 +467,7 @@ def rollout(model, states, actions, n_given, delta, dscaling):
     if aff is None:
         return None
     scale, shift = aff
-    d, o = _FNORolloutFn.apply(states, actions, int(n_given), float(delta) * scale, float(delta) * shift, *parameters_of(model))
+    if not torch.is_grad_enabled():
+        states, actions = states.detach(), actions.detach()
+    d, o = _FNORolloutFn.apply(states, actions, int(n_given), float(delta) * scale, float(delta) * shift, *_node_parameters(model))
     return d.transpose(0, 1).unsqueeze(2), o.transpose(0, 1).unsqueeze(2)

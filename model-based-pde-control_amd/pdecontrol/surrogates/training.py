@@ -389,13 +389,23 @@ class PDETrainingModule(pl.LightningModule):
             cached = self.__dict__["_inv_coef"] = (device, fmap.coef, fmap.coef.to(device))
         return cached[2]
 
-    def _fused_validation_loss(self, out, states, accum=None, outputs=True):
+    def _fused_validation_loss(self, out, states, accum=None, outputs=True, fno=False):
         """The loss section of validation_step as one HIP launch (``sur_val_loss``), on the conditions of
         ``_fused_delta_loss`` plus a recognised ``stransf.otransf.Inverse``; None otherwise (then the torch ops run).
         ``accum`` / ``outputs``: the epoch accumulator and the switch of ``hipops.fused_val_loss`` (the surrogate-update
-        phase keeps an epoch's sums on the device and needs neither ``deltas`` nor the decoded outputs)."""
+        phase keeps an epoch's sums on the device and needs neither ``deltas`` nor the decoded outputs).  ``fno``: the
+        launch is also taken over the rollout of an ``FNOAutoRegSurrogate`` on the whole-network kernels, on the same
+        conditions; only the surrogate-update phase asks for it, ``validation_step`` on such a module keeps the torch ops."""
         from pdecontrol.surrogates import hipops, ops
-        if isinstance(self.surrogate, LatentAutoRegPDESurrogate):
+        if fno and type(self.surrogate).__name__ == "FNOAutoRegSurrogate":
+            from pdecontrol.surrogates import fno_hip
+            if not (states.is_cuda and ops.fused_enabled() and states.dim() == 4
+                    and fno_hip.world_supported(self.surrogate, states.shape[3])):
+                return None
+            if self.training_mode != "delta" or not (isinstance(self.loss, torch.nn.MSELoss) and self.loss.reduction == "none"):
+                return None
+            consts = hipops.undscale_constants(self.undscaling)
+        elif isinstance(self.surrogate, LatentAutoRegPDESurrogate):
             # the latent rollout under no_grad hands out its deltas as a view of time-major storage (sur_latent_deltas)
             consts = self._latent_constants()
             if consts is None or not (states.is_cuda and ops.use_fused_latent_for(self.surrogate, states)):
