@@ -1,11 +1,13 @@
 // rollout.hip -- the kernels that close the imagined-rollout loop in HBM (C ABI: include/rollout_hip.h and, for
-// ro_settle_dissipation, include/rollout/settle_dissipation.h;
+// ro_settle_dissipation and ro_settle_burgers_dissipation, include/rollout/settle_dissipation.h and
+// include/rollout/settle_burgers_dissipation.h;
 // binding: pdecontrol/mbrl/rollout_hip.py; caller: pdecontrol/mbrl/imagination_phase.py).
 //
 // ro_act_chain is the wrapper stack's action side (raw-action record, action scaling, Gaussian forcing, forcing scaling,
 // sensor), ro_settle its observation side (per-env elite pick, world state in place, trajectory slot, agent sensor, step
-// counters, l2control reward); ro_settle_dissipation is ro_settle with the dissipation reward: the two are instantiations
-// of one kernel template, which differ in the reward alone.  A wave owns an env, lanes run along the columns.  The ensemble members travel in the kernel arguments and are picked by wave-uniform selects over
+// counters, l2control reward); ro_settle_dissipation is ro_settle with the KS env's dissipation reward,
+// ro_settle_burgers_dissipation with the Burgers env's: the three are instantiations of one kernel template, which differ
+// in the reward alone.  A wave owns an env, lanes run along the columns.  The ensemble members travel in the kernel arguments and are picked by wave-uniform selects over
 // constant indices, so the argument struct is never indexed dynamically and nothing spills.  No LDS, no atomics; every
 // store is a plain vector store.
 //
@@ -18,6 +20,7 @@
 #include <cstdio>
 #include <type_traits>
 
+#include "../../include/rollout/settle_burgers_dissipation.h"
 #include "../../include/rollout/settle_dissipation.h"
 #include "../../include/rollout_hip.h"
 #include "capi_error.h"
@@ -96,6 +99,15 @@ struct DissKernelArgs : SettleKernelArgs {
     double dx, r_dx, dx2, r_dx2;
 };
 
+// what ro_settle_burgers_dissipation adds: the recorded actions and the forcing as above, and the reward's two constants
+struct BurgersDissKernelArgs : SettleKernelArgs {
+    const float* actions;     // [T][B][A]
+    const float* in_coef;     // [4][A] or NULL
+    const float* forcing;     // [A][N]
+    int A;
+    double two_dx, nu_d;
+};
+
 // column i of a periodic row of n, for -n <= i < 2n.  (ks_kernels.hip's wrap_idx, respelled: that function lives in the KS
 // translation unit, and bench.py quotes its counter profiles only while ks_kernels.hip and ks_internal.h are the files
 // they were measured on, so neither is edited for one line)
@@ -111,8 +123,18 @@ __device__ __forceinline__ void dissipation_point(const double* w, const double*
     sup += w[c] * (double)phi;
 }
 
-// ro_settle (Args = SettleKernelArgs, the l2control reward) and ro_settle_dissipation (Args = DissKernelArgs): one body,
-// of which the reward's sums (one for l2control; sxx, sx and sup for dissipation) and its closing expression depend on Args.
+// the two partial sums of one point of the Burgers dissipation reward: neighbours um, up, centre u0, forcing phi
+__device__ __forceinline__ void burgers_dissipation_point(float um, float u0, float up, float phi, const BurgersDissKernelArgs& d,
+                                                          double& sx, double& sup)
+{
+    const double ux = ((double)up - (double)um) / d.two_dx;
+    sx += ux * ux;
+    sup += (double)u0 * (double)phi;
+}
+
+// ro_settle (Args = SettleKernelArgs, the l2control reward), ro_settle_dissipation (Args = DissKernelArgs) and
+// ro_settle_burgers_dissipation (Args = BurgersDissKernelArgs): one body, of which the reward's sums (one for l2control;
+// sxx, sx and sup for the KS dissipation; sx and sup for the Burgers one) and its closing expression depend on Args.
 //
 // The dissipation stencil needs the rescaled row's periodic halo of 4 columns on both sides: a lane re-reads its
 // neighbours from the member's output row (read-only and cache-hot: the lanes next to it have just fetched the same
@@ -124,6 +146,7 @@ template <class Args>
 __global__ __launch_bounds__(NT) void ro_settle_kernel(const Args k)
 {
     constexpr bool DISS = std::is_same<Args, DissKernelArgs>::value;
+    constexpr bool BURGERS = std::is_same<Args, BurgersDissKernelArgs>::value;
     const int lane = threadIdx.x & (WAVE - 1);
     const int b = blockIdx.x * WAVES + (threadIdx.x >> 6);
     const int t = k.a.step[0];
@@ -136,10 +159,10 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const Args k)
     float* __restrict__ traj = k.a.traj + (slot + k.B) * k.N;       // slot t + 1
     float* __restrict__ pol = k.a.policy_obs + (long)b * k.O;
     [[maybe_unused]] const float* __restrict__ act = nullptr;       // the raw actions ro_act_chain recorded for this step
-    if constexpr (DISS) act = k.actions + slot * k.A;
+    if constexpr (DISS || BURGERS) act = k.actions + slot * k.A;
     const int N = k.N;
 
-    double sum[DISS ? 3 : 1] = {};
+    double sum[DISS ? 3 : BURGERS ? 2 : 1] = {};
     if (k.vec) {                                                     // N a multiple of 4, every row 16-byte aligned
         for (int i = 4 * lane; i < N; i += 4 * WAVE) {
             // the halo is the dissipation reward's alone; its loads stay beside the row's own, under the one test of `known`
@@ -148,7 +171,7 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const Args k)
             [[maybe_unused]] f4 vl = v, vr = v;
             if (known) {
                 v = *reinterpret_cast<const f4*>(row + i);
-                if constexpr (DISS) {
+                if constexpr (DISS || BURGERS) {
                     vl = *reinterpret_cast<const f4*>(row + il);
                     vr = *reinterpret_cast<const f4*>(row + ir);
                 }
@@ -170,6 +193,14 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const Args k)
                 dissipation_point(w, q, 5, phi.y, k, sum[0], sum[1], sum[2]);
                 dissipation_point(w, q, 6, phi.z, k, sum[0], sum[1], sum[2]);
                 dissipation_point(w, q, 7, phi.w, k, sum[0], sum[1], sum[2]);
+            } else if constexpr (BURGERS) {                          // the halo of +-1: the last column before, the first after
+                const f4 ul = affine_col4(k.a.reward_coef, N, il, vl);
+                const f4 ur = affine_col4(k.a.reward_coef, N, ir, vr);
+                const f4 phi = forcing_col4(k.in_coef, k.A, act, k.forcing + i, N);
+                burgers_dissipation_point(ul.w, u.x, u.y, phi.x, k, sum[0], sum[1]);
+                burgers_dissipation_point(u.x, u.y, u.z, phi.y, k, sum[0], sum[1]);
+                burgers_dissipation_point(u.y, u.z, u.w, phi.z, k, sum[0], sum[1]);
+                burgers_dissipation_point(u.z, u.w, ur.x, phi.w, k, sum[0], sum[1]);
             } else {
                 sum[0] += (double)u.x * (double)u.x;
                 sum[0] += (double)u.y * (double)u.y;
@@ -192,6 +223,12 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const Args k)
                     q[j + 4] = w[j + 4] * w[j + 4];
                 }
                 dissipation_point(w, q, 4, forcing_col(k.in_coef, k.A, act, k.forcing + i, N), k, sum[0], sum[1], sum[2]);
+            } else if constexpr (BURGERS) {
+                const int cl = wrap_col(i - 1, N), cr = wrap_col(i + 1, N);
+                burgers_dissipation_point(affine_col(k.a.reward_coef, N, cl, known ? row[cl] : NAN),
+                                          affine_col(k.a.reward_coef, N, i, v),
+                                          affine_col(k.a.reward_coef, N, cr, known ? row[cr] : NAN),
+                                          forcing_col(k.in_coef, k.A, act, k.forcing + i, N), k, sum[0], sum[1]);
             } else {
                 const double w = (double)affine_col(k.a.reward_coef, N, i, v);
                 sum[0] += w * w;
@@ -204,6 +241,8 @@ __global__ __launch_bounds__(NT) void ro_settle_kernel(const Args k)
     if (lane == 0) {
         if constexpr (DISS)                                          // the KS reward-row kernel's expression
             k.a.rewards[slot] = (float)((-1.0) * ((sum[0] / N + sum[1] / N) + sum[2] / N));
+        else if constexpr (BURGERS)                                  // the row reward of include/burgers/objective.h
+            k.a.rewards[slot] = (float)((-1.0) * (k.nu_d * (sum[0] / N) + sum[1] / N));
         else
             k.a.rewards[slot] = (float)((-1.0) * (1.0 / N) * sum[0]);
         k.a.steps[slot] = k.a.steps0[b] + t + 1;
@@ -309,6 +348,33 @@ int ro_settle_dissipation(void* stream, const ro_geometry* g, const ro_settle_ar
     hipLaunchKernelGGL(ro_settle_kernel<DissKernelArgs>, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0,
                        static_cast<hipStream_t>(stream), k);
     return launch_status(-20, "ro_settle_dissipation");
+}
+
+int ro_settle_burgers_dissipation(void* stream, const ro_geometry* g, const ro_settle_args* a,
+                                  const ro_burgers_dissipation_args* d)
+{
+    const int rc = ro_supported(g);
+    if (rc != 0) return rc;
+    BurgersDissKernelArgs k = {};
+    const int bad = settle_kernel_args("ro_settle_burgers_dissipation", g, a, k);
+    if (bad != 0) return bad;
+    if (!d || !d->d.actions || !d->d.forcing)
+        return fail(-10, "ro_settle_burgers_dissipation: NULL dissipation argument, recorded-actions or forcing pointer");
+    if (g->L != g->N)
+        return fail(-11, "ro_settle_burgers_dissipation: forcing width %d for a state width of %d (the reward needs the "
+                         "forcing at every grid point)", g->L, g->N);
+    if (!std::isfinite(d->d.dx) || d->d.dx <= 0.0)
+        return fail(-12, "ro_settle_burgers_dissipation: grid spacing %g (finite and above 0)", d->d.dx);
+    if (!std::isfinite(d->nu) || d->nu < 0.0)
+        return fail(-13, "ro_settle_burgers_dissipation: viscosity %g (finite and not negative)", d->nu);
+    k.actions = d->d.actions; k.in_coef = d->d.in_coef; k.forcing = d->d.forcing;
+    k.A = g->A;
+    k.two_dx = 2.0 * d->d.dx;
+    k.nu_d = (double)(float)d->nu;
+    k.vec = k.vec && aligned16(d->d.forcing);
+    hipLaunchKernelGGL(ro_settle_kernel<BurgersDissKernelArgs>, dim3((g->B + WAVES - 1) / WAVES), dim3(NT), 0,
+                       static_cast<hipStream_t>(stream), k);
+    return launch_status(-20, "ro_settle_burgers_dissipation");
 }
 
 const char* ro_last_error(void) { return g_err; }

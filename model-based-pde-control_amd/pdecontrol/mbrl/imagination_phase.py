@@ -16,7 +16,8 @@ kernel tier   the closed loop stays in HBM for a whole round (one reset plus the
               step is ``noise.normal_()`` plus one hipGraph replay of
                   sac_policy_forward -> ro_act_chain -> every member's fused one-step rollout -> ro_settle
               (csrc/rollout.hip; under the KS env's dissipation objective the last launch is ro_settle_dissipation,
-              which recomputes the forcing of the recorded action for the reward's u * phi term; an ensemble of FNO
+              which recomputes the forcing of the recorded action for the reward's u * phi term, and under the Burgers
+              env's ro_settle_burgers_dissipation, which does the same for that env's reward; an ensemble of FNO
               members, which carry no hidden state, is stepped as ro_act_chain -> fno_forward_select -> ro_settle over
               the one buffer of picked rows: one evaluation per env in place of one per member and env); the per-step elite
               draws are made on the host in the loop's order and uploaded once per round; one D2H copy and one
@@ -68,9 +69,11 @@ class StackGeometry:
     ``act_out``     sensor and scaling of the forcing columns: the world's action row
     ``agent_obs``   the agent sensor over the world's observation columns
     ``reward``      the rescaling of the world's observation before the reward
-    ``objective``   the reward owner's objective: the KS env's "l2control" or "dissipation"
-                    (``KuramotoSivashinskyEnv.step_objective``), the Burgers env's "l2control" (its ``scenario``)
-    ``dx``          the env's grid spacing L / N (read by the dissipation reward)
+    ``objective``   the reward owner's objective, "l2control" or "dissipation": the KS env's
+                    ``KuramotoSivashinskyEnv.step_objective``, the Burgers env's ``scenario["objective"]``
+    ``dx``          the env's grid spacing L / N (read by the dissipation rewards)
+    ``owner``       the reward owner's kind, "ks" or "burgers": the two dissipation rewards are different expressions
+    ``nu``          the Burgers env's viscosity (read by its dissipation reward; 0.0 for a KS owner)
     """
     world: object
     act_in: FieldMap
@@ -80,6 +83,8 @@ class StackGeometry:
     reward: FieldMap
     objective: str = "l2control"
     dx: float = 0.0
+    owner: str = "ks"
+    nu: float = 0.0
 
 
 def recognize_stack(stack, objectives=("l2control",)):
@@ -89,7 +94,8 @@ def recognize_stack(stack, objectives=("l2control",)):
     ``StoreNObsVecWrapper``; a ``WorldVecEnv`` whose observation connector is a stride-1 sensor and at most one scaling
     and whose batched reward is a ``KuramotoSivashinskyEnv``'s, under one of ``objectives`` (the kernel tier passes
     both; the dissipation reward reads the forcing at every grid point, so its forcing must be as wide as the state), or a
-    ``BurgersBatchedVecEnv``'s (what ``BurgersEnv.batched_reward_func`` forwards to), whose scenario names l2control."""
+    ``BurgersBatchedVecEnv``'s (what ``BurgersEnv.batched_reward_func`` forwards to), whose scenario names l2control or
+    dissipation, the latter on the same two conditions."""
     from pdecontrol.mbrl.world.world import WorldVecEnv
     from pdegym.burgers.burgers import BurgersBatchedVecEnv
     from pdegym.kuramoto import KuramotoSivashinskyEnv
@@ -125,22 +131,24 @@ def recognize_stack(stack, objectives=("l2control",)):
         raise Unrecognized("a world whose observation connector carries a sensor of stride above 1")
     owner = getattr(world.batched_reward_func, "__self__", None)
     if isinstance(owner, BurgersBatchedVecEnv):
-        # its batched reward is the l2control expression -(1/N) * |obs|^2 that ro_settle forms; the scenario names it
+        # its batched reward is the l2control expression -(1/N) * |obs|^2 that ro_settle forms, or the dissipation
+        # expression of ro_settle_burgers_dissipation; the scenario names it
         objective = owner.scenario["objective"]
-        if objective != "l2control":
+        if objective not in ("l2control", "dissipation"):
             raise Unrecognized(f"a BurgersBatchedVecEnv whose scenario names the {objective} objective (its batched reward "
                                f"is l2control's)")
+        kind, nu = "burgers", float(owner.nu)
     elif not isinstance(owner, KuramotoSivashinskyEnv):
         raise Unrecognized("a world without the batched reward of a KuramotoSivashinskyEnv")
     else:
-        objective = owner.step_objective
+        objective, kind, nu = owner.step_objective, "ks", 0.0
     if objective not in objectives:
         raise Unrecognized(f"the {objective} objective")
     if owner.N != N:
         raise Unrecognized(f"a reward over {owner.N} grid points for observations of {N}")
     if objective == "dissipation" and int(matrix.shape[1]) != N:
         raise Unrecognized(f"a forcing over {int(matrix.shape[1])} columns under the dissipation reward of {N} grid points")
-    return StackGeometry(world, act_in, matrix, act_out, agent_obs, reward, objective, owner.L / owner.N)
+    return StackGeometry(world, act_in, matrix, act_out, agent_obs, reward, objective, owner.L / owner.N, kind, nu)
 
 
 def round_length(timesteps0, horizon, max_episode_steps):
@@ -198,7 +206,7 @@ class _CapturedStep:
         self.geometry = ro.Geometry(B, T, N, A, L, geo.act_out.start, geo.act_out.stride, geo.agent_obs.start,
                                     geo.agent_obs.stride, len(dev.members))
         self.maps = (geo.act_in, geo.act_out, geo.agent_obs, geo.reward)
-        self.objective, self.dx = geo.objective, float(geo.dx)
+        self.objective, self.dx, self.owner, self.nu = geo.objective, float(geo.dx), geo.owner, float(geo.nu)
         self.forcing_host = geo.forcing
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=device)
         self.forcing = geo.forcing.to(device)
@@ -256,7 +264,11 @@ class _CapturedStep:
             self.keep = outs
             settle_args = ro.settle_args(outs, self.chosen if len(outs) > 1 else None, dev.state, self.traj, self.policy_obs,
                                          self.steps0, self.steps, self.rewards, self.coefs[2], self.step)
-            if self.objective == "dissipation":
+            if self.objective == "dissipation" and self.owner == "burgers":
+                ro.settle_burgers_dissipation(stream, settle_geometry, settle_args,
+                                              ro.burgers_dissipation_args(self.actions, self.coefs[0], self.forcing, self.dx,
+                                                                          self.nu))
+            elif self.objective == "dissipation":
                 ro.settle_dissipation(stream, settle_geometry, settle_args,
                                       ro.dissipation_args(self.actions, self.coefs[0], self.forcing, self.dx))
             else:
@@ -288,6 +300,7 @@ class _CapturedStep:
         world = geo.world
         if (world._dev is not self.dev or not self.dev.valid() or fused is not self.fused or fused.version != self.version
                 or max(int(world.horizon), 1) != self.T or geo.objective != self.objective or float(geo.dx) != self.dx
+                or geo.owner != self.owner or float(geo.nu) != self.nu
                 or _select_wanted() != self.select_wanted):
             return False
         now = (geo.act_in, geo.act_out, geo.agent_obs, geo.reward)

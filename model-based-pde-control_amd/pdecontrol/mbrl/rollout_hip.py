@@ -1,5 +1,5 @@
 """ctypes binding of librollout_hip.so (C ABI: include/rollout_hip.h ``ro_*`` and, for the dissipation objective,
-include/rollout/settle_dissipation.h; kernels: csrc/rollout.hip): the action chain and the settle kernels (one per reward
+include/rollout/settle_dissipation.h and include/rollout/settle_burgers_dissipation.h; kernels: csrc/rollout.hip): the action chain and the settle kernels (one per reward
 objective) of the captured imagined step.  ``ro_supported`` and ``ro_last_error`` are pure host functions and work
 without a GPU.  A missing library raises: the kernel tier of pdecontrol/mbrl/imagination_phase.py has
 no silent fallback.
@@ -39,6 +39,11 @@ class DissipationArgs(ctypes.Structure):
     _fields_ = [("actions", _p), ("in_coef", _p), ("forcing", _p), ("dx", ctypes.c_double)]
 
 
+class BurgersDissipationArgs(ctypes.Structure):
+    """``ro_burgers_dissipation_args`` of include/rollout/settle_burgers_dissipation.h"""
+    _fields_ = [("d", DissipationArgs), ("nu", ctypes.c_double)]
+
+
 _geo = ctypes.POINTER(Geometry)
 SYMBOLS = (
     ("ro_supported", _i, [_geo]),
@@ -51,6 +56,10 @@ SYMBOLS = (
 DISSIPATION_SYMBOLS = (
     ("ro_settle_dissipation", _i, [_p, _geo, ctypes.POINTER(SettleArgs), ctypes.POINTER(DissipationArgs)]),
 )
+# include/rollout/settle_burgers_dissipation.h, the same library again (tests/test_burgers_objective_host.py)
+BURGERS_DISSIPATION_SYMBOLS = (
+    ("ro_settle_burgers_dissipation", _i, [_p, _geo, ctypes.POINTER(SettleArgs), ctypes.POINTER(BurgersDissipationArgs)]),
+)
 _lib = None
 
 
@@ -61,7 +70,7 @@ class RolloutHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + DISSIPATION_SYMBOLS, RolloutHipError, "The fused imagined-rollout step has no fallback.")
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + DISSIPATION_SYMBOLS + BURGERS_DISSIPATION_SYMBOLS, RolloutHipError, "The fused imagined-rollout step has no fallback.")
     return _lib
 
 
@@ -114,3 +123,13 @@ def settle(stream, geometry, args):
 def settle_dissipation(stream, geometry, args, dissipation):
     """``settle`` with the dissipation reward (``dissipation``: ``dissipation_args``)."""
     _check(load().ro_settle_dissipation(stream, ctypes.byref(geometry), ctypes.byref(args), ctypes.byref(dissipation)))
+
+
+def burgers_dissipation_args(actions, in_coef, forcing, dx, nu):
+    """``ro_burgers_dissipation_args``: ``dissipation_args`` and the viscosity."""
+    return BurgersDissipationArgs(dissipation_args(actions, in_coef, forcing, dx), float(nu))
+
+
+def settle_burgers_dissipation(stream, geometry, args, dissipation):
+    """``settle`` with the Burgers env's dissipation reward (``dissipation``: ``burgers_dissipation_args``)."""
+    _check(load().ro_settle_burgers_dissipation(stream, ctypes.byref(geometry), ctypes.byref(args), ctypes.byref(dissipation)))

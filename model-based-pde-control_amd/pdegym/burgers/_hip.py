@@ -1,5 +1,5 @@
-"""ctypes binding of libburgers_hip.so (C ABI: include/burgers_hip.h, and include/burgers/eval.h for the test-phase
-entries).  No fallback: a missing library raises."""
+"""ctypes binding of libburgers_hip.so (C ABI: include/burgers_hip.h, include/burgers/eval.h for the test-phase
+entries and include/burgers/objective.h for the objective entries).  No fallback: a missing library raises."""
 import ctypes
 import os
 
@@ -48,6 +48,16 @@ EVAL_SYMBOLS = (
     ("bg_derivatives_host", _i, [_p, _i, _i, _d, _p, _p]),
     ("bg_eval_last_error", ctypes.c_char_p, []),
 )
+# include/burgers/objective.h: a third table over the same library; the *_host entries make no HIP call
+OBJECTIVES = {"l2control": 0, "dissipation": 1}      # BG_OBJECTIVE_*
+OBJECTIVE_SYMBOLS = (
+    ("bg_step_objective", _i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, ctypes.c_long, _p, _p, _p, _i]),
+    ("bg_step_span_objective", _i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, ctypes.c_long, _p, _p, _p, _i]),
+    ("bg_reward_rows", _i, [_p, _p, _p, _p, _p, _i, _i, _i, _d, _d, _p]),
+    ("bg_step_objective_host", _i, [_p, _p, _p, _i, _i, _i, _f, _f, _f, ctypes.c_long, _p, _p, _p, _i]),
+    ("bg_reward_rows_host", _i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _p]),
+    ("bg_objective_last_error", ctypes.c_char_p, []),
+)
 _lib = None
 
 
@@ -58,7 +68,7 @@ class BurgersHipError(RuntimeError):
 def load():
     global _lib
     if _lib is None:
-        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + EVAL_SYMBOLS, BurgersHipError,
+        _lib = hipbind.open_library(LIB_PATH, SYMBOLS + EVAL_SYMBOLS + OBJECTIVE_SYMBOLS, BurgersHipError,
                                     "The Burgers stepper has no CPU fallback.")
     return _lib
 
@@ -66,3 +76,5 @@ def load():
 check = hipbind.checker(BurgersHipError, "libburgers_hip", "bg_last_error", lambda: load())
 # the test-phase entries report through a message buffer of their own
 check_eval = hipbind.checker(BurgersHipError, "libburgers_hip (eval)", "bg_eval_last_error", lambda: load())
+# and so do the objective entries
+check_objective = hipbind.checker(BurgersHipError, "libburgers_hip (objective)", "bg_objective_last_error", lambda: load())

@@ -6,8 +6,15 @@ What the reference does fix is the discretisation -- ``BurgersPhyPDELoss`` (pdec
 the explicit midpoint rule -- and that arithmetic is what ``libburgers_hip.so`` implements (pinned to the reference
 class's own outputs in tests/test_burgers.py).  Everything around the step follows the Kuramoto-Sivashinsky env of the
 same package: four Gaussian actuators (``GaussianForcing``), ``cfg_steps`` sub-steps per ``step`` with the forcing held,
-l2-control reward ``-(1/N) |u|^2`` averaged over the sub-steps (taken before each update), truncation at
-``Tmax``, fp32 observations ``[1, N]``.  **Parity unpinned** for all of that (no reference to compare with).
+a reward averaged over the sub-steps (taken before each update), truncation at ``Tmax``, fp32 observations ``[1, N]``.
+**Parity unpinned** for all of that (no reference to compare with).
+
+Two objectives (``objective=``), as the KS env has them: ``"l2control"``, the reward ``-(1/N) |u|^2``, and
+``"dissipation"``, the energy budget of the forced equation ``d/dt 1/2 <u^2> = -nu <u_x^2> + <u phi>`` turned into the
+reward ``-(nu <u_x^2> + <u phi>)``: shrink the field at low dissipation and low actuation power.  The name selects it (no
+truthiness rule: there is no reference to mirror).  The step's reward comes from the stepper kernel itself
+(include/burgers/objective.h), the reward of given rows from ``bg_reward_rows`` on the device and from
+``dissipation_rows`` on the host.
 
 ``BurgersBatchedVecEnv`` is the vector env (one HBM-resident fp32 batch, one launch per step, gym autoreset
 semantics); ``BurgersEnv`` is the single-env view of it that ``gym.make`` returns.
@@ -22,6 +29,27 @@ from hipbind import ptr as _ptr
 from pdegym._gym import gym
 from pdegym.burgers import _hip
 from pdegym.common.transforms import FuncTransform, GaussianForcing
+
+
+OBJECTIVES = ("l2control", "dissipation")
+
+
+def _checked_objective(objective):
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES}, not {objective!r}")
+    return objective
+
+
+def dissipation_rows(u, phi, dx, nu):
+    """The dissipation reward of fp32 rows ``u`` [M, N] under the fp32 forcing field ``phi`` [M, N], fp64 [M]: the fp64
+    spelling of ``bg_reward_rows`` with every row summed in index order, the bits of ``bg_reward_rows_host``."""
+    u = np.asarray(u, dtype=np.float32).astype(np.float64)
+    p = np.asarray(phi, dtype=np.float32).astype(np.float64)
+    n = u.shape[1]
+    ux = (np.roll(u, -1, axis=1) - np.roll(u, 1, axis=1)) / (2.0 * dx)
+    # cumsum adds in index order (from 0.0, as the kernel's accumulator starts), where sum() adds pairwise
+    in_order = lambda t: np.cumsum(np.concatenate((np.zeros((t.shape[0], 1)), t), axis=1), axis=1)[:, -1]
+    return (-1.0) * (float(np.float32(nu)) * (in_order(ux * ux) / n) + in_order(u * p) / n)
 
 
 def _stream(dev):
@@ -42,17 +70,28 @@ class BurgersStepper:
         return _stream(env.device), _ptr(env.u), _ptr(env._F)
 
     def step_device(self, d_actions=0, n_substeps=50, d_obs=0, d_ssq=0, d_status=0):
-        """One ``bg_step`` launch: ``d_actions`` [E, A] (0: no forcing), ``d_obs`` [E, N], ``d_ssq`` fp64 [E], ``d_status`` [E]."""
+        """One ``bg_step`` launch (``bg_step_objective`` under the dissipation objective, whose sum ``d_ssq`` then
+        receives): ``d_actions`` [E, A] (0: no forcing), ``d_obs`` [E, N], ``d_ssq`` fp64 [E], ``d_status`` [E]."""
         env, vp = self._env, _void_p
         stream, u, F = self._step_args()
+        if env.objective != "l2control":
+            _hip.check_objective(self._lib.bg_step_objective(
+                stream, u, vp(d_actions), F, self.n_act, self.num_envs, self.N, env.dx, env.dt, env.nu, int(n_substeps),
+                vp(d_obs), vp(d_ssq), vp(d_status), _hip.OBJECTIVES[env.objective]))
+            return
         _hip.check(self._lib.bg_step(stream, u, vp(d_actions), F, self.n_act, self.num_envs, self.N, env.dx, env.dt, env.nu,
                                      int(n_substeps), vp(d_obs), vp(d_ssq), vp(d_status)))
 
     def step_span(self, d_actions, T, n_substeps, d_traj, d_ssq=0, d_status=0):
         """``T`` steps in one ``bg_step_span`` launch: ``d_actions`` [T, E, A], ``d_traj`` [T + 1, E, N] (slots 1 ... T are
-        written), ``d_ssq`` fp64 [T, E], ``d_status`` [T, E]."""
+        written), ``d_ssq`` fp64 [T, E], ``d_status`` [T, E].  Under the dissipation objective: ``bg_step_span_objective``."""
         env, vp = self._env, _void_p
         stream, u, F = self._step_args()
+        if env.objective != "l2control":
+            _hip.check_objective(self._lib.bg_step_span_objective(
+                stream, u, vp(d_actions), F, self.n_act, self.num_envs, self.N, int(T), env.dx, env.dt, env.nu,
+                int(n_substeps), vp(d_traj), vp(d_ssq), vp(d_status), _hip.OBJECTIVES[env.objective]))
+            return
         _hip.check(self._lib.bg_step_span(stream, u, vp(d_actions), F, self.n_act, self.num_envs, self.N, int(T), env.dx,
                                           env.dt, env.nu, int(n_substeps), vp(d_traj), vp(d_ssq), vp(d_status)))
 
@@ -75,16 +114,19 @@ def _void_p(x):
 
 class BurgersBatchedVecEnv(gym.vector.VectorEnv):
     Xi = [0, 0.25, 0.5, 0.75]
+    objective = "l2control"
 
     def __init__(self, num_envs: int, L: float = 2 * math.pi, N: int = 512, cfg_steps: int = 50, dt: float = 1e-3,
-                 nu: float = 0.01, Tmax: float = 10.0, sigma: float = 0.15, ic_modes: int = 4, device: int = 0):
+                 nu: float = 0.01, Tmax: float = 10.0, sigma: float = 0.15, ic_modes: int = 4, device: int = 0,
+                 objective: str = "l2control"):
+        self.objective = _checked_objective(objective)
         self.L, self.N, self.cfg_steps, self.dt, self.nu, self.Tmax, self.sigma = L, N, cfg_steps, dt, nu, Tmax, sigma
         self.ic_modes = ic_modes
         self.dx = L / N
         self.x = np.linspace(0.0, L - L / N, N, dtype=np.float32)
         self.max_episode_steps = math.ceil(Tmax / (dt * cfg_steps))
         self.forcing = GaussianForcing(self.x, self.Xi, sigma, L, N)
-        self.reward_func = FuncTransform(lambda obs, *a, **k: (-1.0) * (1 / self.N) * torch.norm(obs) ** 2)
+        self.reward_func = self._reward_transform()
         obs_space = gym.spaces.Box(-np.inf, np.inf, shape=(1, N), dtype=np.float32)
         act_space = gym.spaces.Box(-1.0, 1.0, shape=(1, len(self.Xi)), dtype=np.float32)
         super().__init__(num_envs, obs_space, act_space)
@@ -102,9 +144,60 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
     @property
     def scenario(self):
         return {"cfg_steps": self.cfg_steps, "L": self.L, "N": self.N, "dx": self.dx, "Tmax": self.Tmax, "dt": self.dt,
-                "nu": self.nu, "Xi": self.Xi, "objective": "l2control"}
+                "nu": self.nu, "Xi": self.Xi, "objective": self.objective}
+
+    # -- rewards of given rows ----------------------------------------------------------------------------------
+    def _reward_transform(self):
+        """``reward_func`` of the env's objective: ``reward_func(obs, phi)`` of one row, a torch scalar."""
+        if self.objective == "l2control":
+            return FuncTransform(lambda obs, *a, **k: (-1.0) * (1 / self.N) * torch.norm(obs) ** 2)
+        return FuncTransform(self._dissipation)
+
+    def _forcing_field(self, phi):
+        """phi as a forcing field: actions ``[..., n_act]`` go through ``forcing`` (fp32 ``[..., N]``); the rule of
+        ``KuramotoSivashinskyEnv._forcing_field``."""
+        if phi.shape[-1] == len(self.Xi) and phi.shape[-1] != self.N:
+            return self.forcing(phi)
+        return phi
+
+    def _dissipation(self, obs, phi=None, *args, **kwargs):
+        if phi is None:
+            raise ValueError("the dissipation reward needs the forcing (phi or actions)")
+        as_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        u, p = as_np(obs).reshape(1, self.N), np.asarray(self._forcing_field(as_np(phi))).reshape(1, self.N)
+        return torch.as_tensor(np.float32(dissipation_rows(u, p, self.dx, self.nu)[0]))
+
+    def _batched_dissipation(self, obs, phi):
+        """``_dissipation`` of every row of ``obs [B, ..., N]`` in the input's dtype; ``phi`` is ``[B, ..., N]`` or actions
+        ``[B, ..., n_act]``.  CUDA tensors by ``bg_reward_rows`` on torch's current stream (actions through the kernel's
+        own forcing chain), numpy and CPU tensors by ``dissipation_rows``."""
+        if phi is None:
+            raise ValueError("the dissipation reward needs the forcing (phi or actions)")
+        b = obs.shape[0]
+        if isinstance(obs, torch.Tensor) and obs.is_cuda:
+            u = obs.reshape(b, self.N).to(torch.float32).contiguous()
+            p = torch.as_tensor(phi, device=obs.device).reshape(b, -1).to(torch.float32).contiguous()
+            out = torch.empty(b, dtype=torch.float64, device=obs.device)
+            if p.shape[1] == len(self.Xi) and p.shape[1] != self.N:
+                field, actions, F = None, p, self._F if self._F.device == obs.device else self._F.to(obs.device)
+            else:
+                field, actions, F = p.reshape(b, self.N), None, None
+            _hip.check_objective(self._lib.bg_reward_rows(_stream(obs.device), _ptr(u), _ptr(field), _ptr(actions), _ptr(F), b,
+                                                          self.N, len(self.Xi), self.dx, self.nu, _ptr(out)))
+            return out.to(obs.dtype)
+        as_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        u = as_np(obs).reshape(b, self.N)
+        p = np.asarray(self._forcing_field(as_np(phi))).reshape(b, self.N)
+        rew = dissipation_rows(u, p, self.dx, self.nu)
+        if isinstance(obs, torch.Tensor):
+            return torch.as_tensor(rew).to(obs.dtype)
+        return rew.astype(obs.dtype)
 
     def batched_reward_func(self, obs, phi=None):
+        """``reward_func`` for a whole batch ``[B, ..., N]`` at once (numpy or torch, host or device): the reward of every
+        row, in the input's dtype.  Dissipation: ``phi`` is ``[B, ..., N]`` or actions ``[B, ..., n_act]``."""
+        if self.objective != "l2control":
+            return self._batched_dissipation(obs, phi)
         flat = obs.reshape(obs.shape[0], -1)
         if isinstance(obs, np.ndarray):
             return ((-1.0) * (1 / self.N) * np.linalg.norm(flat, axis=1) ** 2).astype(obs.dtype)
@@ -134,12 +227,16 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
         None (no forcing).  Returns (state [E, N] fp32 -- the live buffer --, rewards [E] fp64); no host sync."""
         n = self.cfg_steps if n_substeps is None else int(n_substeps)
         a = None if actions is None else actions.reshape(self.num_envs, -1).contiguous()
+        if self.objective != "l2control":
+            self.stepper.step_device(0 if a is None else a.data_ptr(), n, 0, self._ssq.data_ptr(), self._status.data_ptr())
+            return self.u, self._ssq * self.reward_scale(n)
         _hip.check(self._lib.bg_step(_stream(self.device), _ptr(self.u), _ptr(a), _ptr(self._F), len(self.Xi), self.num_envs,
                                      self.N, self.dx, self.dt, self.nu, n, None, _ptr(self._ssq), _ptr(self._status)))
         return self.u, self._ssq * self.reward_scale(n)
 
     def reward_scale(self, n_substeps: Optional[int] = None):
-        """The fp64 factor ``c`` of a step's reward ``ssq * c``: minus the mean square, averaged over the sub-steps."""
+        """The fp64 factor ``c`` of a step's reward ``ssq * c``: minus the mean over the grid, averaged over the sub-steps
+        (of the squares under l2control, of ``nu u_x^2 + u phi`` under dissipation: the stepper's sum follows the objective)."""
         n = self.cfg_steps if n_substeps is None else int(n_substeps)
         return -(1.0 / self.N) / max(n, 1)
 
@@ -148,7 +245,8 @@ class BurgersBatchedVecEnv(gym.vector.VectorEnv):
         return ssq * self.reward_scale()
 
     def bind_stream(self, stream):
-        """Nothing to bind: every launch takes torch's current stream by itself, and the objective is fixed."""
+        """Nothing to bind: every launch takes torch's current stream by itself, and ``step_device`` / ``step_span`` pick
+        the entry of the env's objective on every call."""
 
     def _raise_on(self, status):
         """``status`` [E] of one step: the ``FloatingPointError`` of ``step_wait`` when any env's state is non-finite."""
@@ -254,6 +352,7 @@ class BurgersEnv(gym.Env):
         self._config = dict(config)
         self._vec = None
         probe = {k: v for k, v in config.items() if k != "device"}
+        self.objective = _checked_objective(probe.get("objective", "l2control"))
         L, N = probe.get("L", 2 * math.pi), probe.get("N", 512)
         self.L, self.N = L, N
         self.cfg_steps, self.dt = probe.get("cfg_steps", 50), probe.get("dt", 1e-3)

@@ -73,7 +73,7 @@ def beats(seconds, fast, slow):
 # ----------------------------------------------------------------------------------------------------------------------
 # (i) the phase
 # ----------------------------------------------------------------------------------------------------------------------
-def scene(dev, envs, members, horizon):
+def scene(dev, envs, members, horizon, objective="l2control"):
     """(world, starting states, PDEEnvStack, agent) over a real ``BurgersBatchedVecEnv`` as the reward owner."""
     from pdecontrol.architectures.fno import BurgersFNO
     from pdecontrol.mbrl.replay import ExperienceReplay
@@ -87,7 +87,7 @@ def scene(dev, envs, members, horizon):
     from pdegym.burgers.burgers import BurgersBatchedVecEnv
     from pdegym.common import transforms as T
     from pdegym.common import vec_wrappers as W
-    env = BurgersBatchedVecEnv(envs, N=N, cfg_steps=CFG_STEPS, device=dev.index)        # never stepped
+    env = BurgersBatchedVecEnv(envs, N=N, cfg_steps=CFG_STEPS, device=dev.index, objective=objective)   # never stepped
     tstep = env.cfg_steps * env.dt
     oscaling = T.ScaleTransform(bounds=(np.full((1, 1, 1), -3.0, np.float32), np.full((1, 1, 1), 3.0, np.float32)),
                                 batched=True, aggregate=True, frozen=True)

@@ -12,7 +12,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "model-based-pde-control_amd", "csrc")
 SOURCES = [("ks_kernels.hip", ["-ffp-contract=off"]), ("sur_kernels.hip", []), ("sur_windows.hip", ["-ffp-contract=off"]),
-           ("sur_decoded.hip", ["-ffp-contract=off"]), ("burgers.hip", ["-ffp-contract=off"]), ("bg_eval.hip", ["-ffp-contract=off"]), ("spectral.hip", []), ("fno.hip", []), ("rollout.hip", ["-ffp-contract=off"]),
+           ("sur_decoded.hip", ["-ffp-contract=off"]), ("burgers.hip", ["-ffp-contract=off"]), ("bg_eval.hip", ["-ffp-contract=off"]),
+           ("bg_objective.hip", ["-ffp-contract=off"]), ("spectral.hip", []), ("fno.hip", []), ("rollout.hip", ["-ffp-contract=off"]),
            ("collect.hip", ["-ffp-contract=off"])]
 if sys.argv[1:]:                                           # tools/kernel_resources.py collect.hip: these sources only
     SOURCES = [row for row in SOURCES if row[0] in sys.argv[1:]]
